@@ -1,14 +1,23 @@
 """Benchmark of the north-star path: one full G+D train step (train.py:166-269 semantics) on synthetic
 256x256 single-channel OCTA batches.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N=1: BASELINE.json configs[1] (256x256x1, batch 8, fp32, 1 MI355X).  N>1 (launched by the driver through
 torch.distributed.run, one rank per GPU): the same per-GPU batch on every rank (weak scaling), gradients of the two
 flat arenas all-reduced over RCCL per optimizer phase.  Rank 0 prints ONE JSON line.
 
 Plain `python bench.py --gpus N` (no launcher) spawns the N ranks itself before touching the GPU.
 
-Beside the headline value the line carries
+A plain run sets up, runs W warm-up steps, times K steps (`value`, `ms_per_step`), writes the last timed step's outputs when
+--dump-outputs is given, and prints the line.  The last timed step starts from the seeded initial state (InitialState), so with
+the same arguments it computes the same thing on every run.  --dump-outputs DIR: what that step returns -- the losses (float64)
+and its forward tensors (float32, large ones as a fixed seeded sample) -- as DIR/<name>.npy, so two builds can be compared
+output for output.
+
+--full adds the secondary measurements (--no-alt, --no-graph, --no-roofline, --no-cpu-baseline drop single ones again):
+  host_enqueue_ms_per_step: host time to enqueue a step, 5 extra steps without synchronisation;
+  exact_f32_mfma, alt_precision_*: the same step at the other precisions;
+  hipgraph_step:      the same step replayed as one captured hipGraph;
   roofline:           the dominant convolution kernel family BY TIME (HIP events on the launch stream around every
                       convolution-type C-ABI call over extra steps of the same workload, tagged with the kernel family the
                       dispatcher chose): algorithmic FLOP / measured time against the f32 MFMA peak (157.3 TFLOP/s), plus
@@ -138,7 +147,7 @@ PRECISION_EVIDENCE = {
                           "tests/test_gpu_step.py::test_train_step_f16x2_precision",
     "bare_mfma_probe": "32x32 tile, K = 576 .. 65536: f16x2 2.7e-7 .. 3.6e-6 vs the fp32 FMA chain / v_mfma_f32_32x32x2_f32 3.2e-7 .. 3.4e-6 -- "
                        "tools/probe/split_precision_error.hip, profiles/r04_split_precision_error.log",
-    "exact_f32_step": "the same step on the exact-f32 MFMA kernels is measured by this run too: field exact_f32_mfma"}
+    "exact_f32_step": "the same step on the exact-f32 MFMA kernels is measured by a --full run: field exact_f32_mfma"}
 
 
 def make_batch(B, H, device, rank):
@@ -146,6 +155,49 @@ def make_batch(B, H, device, rank):
     a = (torch.rand(B, 1, H, H, generator=g) * 2 - 1).to(device)
     b = (torch.rand(B, 1, H, H, generator=g) * 2 - 1).to(device)
     return a, b
+
+
+class InitialState:
+    """The seeded TrainStep's starting point: its two parameter arenas, zero AdamW moments and step counts, empty replay buffers.
+    ``restore()`` runs before the LAST timed step, so that step -- whose outputs --dump-outputs writes -- is the first train step
+    from the same state and computes the same thing on every run.  A chained step would not: the weight-gradient atomics make a
+    step not bit-reproducible, and GAN training amplifies that from step to step (two runs of 13 chained steps ended with losses
+    up to 0.2 apart).  The work of a step does not depend on the state it starts from."""
+
+    def __init__(self, ts):
+        self.ts = ts
+        self.arenas = [(a, a.flat.clone()) for a in (ts.opt_G, ts.opt_D)]
+
+    def restore(self):
+        import faoctasr
+        with torch.no_grad():
+            for a, flat in self.arenas:
+                a.flat.copy_(flat)
+                a.exp_avg.zero_()                # a new ParamArena's AdamW moments
+                a.exp_avg_sq.zero_()
+                a.step_count = 0
+                a._epoch[0] += 1                 # as ParamArena.step: the packed weight images are stale
+        self.ts.fake_A_buffer, self.ts.fake_B_buffer = faoctasr.ReplayBuffer(), faoctasr.ReplayBuffer()
+
+
+DUMP_SAMPLE = 1 << 19             # floats kept per array by --dump-outputs (at most 2 MB each)
+
+
+def dump_outputs(out_dir, out):
+    """What the last timed step returned to its caller (``TrainStep.step(keep=True)``): the losses (loss_*.npy, float64) and the
+    step's forward tensors as out_*.npy -- fakes, reconstructions, high-frequency features, critic predictions (float32).  A tensor
+    of more than DUMP_SAMPLE floats is written as the same DUMP_SAMPLE positions on every run (torch.randint, fixed seed, sorted)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        if k != "tensors":
+            np.save(os.path.join(out_dir, k + ".npy"), np.array([float(v)], dtype=np.float64))
+    for k, t in sorted(out["tensors"].items()):
+        v = t.reshape(-1)
+        if v.numel() > DUMP_SAMPLE:
+            g = torch.Generator(device="cpu").manual_seed(0)
+            v = v.index_select(0, torch.randint(0, v.numel(), (DUMP_SAMPLE,), generator=g).sort().values.to(v.device))
+        np.save(os.path.join(out_dir, "out_" + k + ".npy"), v.float().cpu().numpy())
 
 
 def cpu_baseline(H, budget_s=15.0):
@@ -268,6 +320,10 @@ def main():
                     help="conv contraction: f16x2 = fp32 operands as scaled fp16 hi/lo pairs on the f16 MFMA, fp32 accumulate, error class of "
                          "the exact-f32 kernels (default, the headline); f32 = exact fp32 MFMA (the headline of rounds 1-3, reported beside it); "
                          "bf16x3 = bf16 hi/lo pairs (16 significant bits)")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements: host enqueue time, the other precisions, the "
+                                                        "hipGraph-captured step, the kernel-family and HBM rooflines, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's losses and (sampled) forward "
+                                                                        "tensors as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip the secondary measurements (the same step at the other precisions)")
@@ -282,8 +338,13 @@ def main():
                                                           "'single-chain', 'one-stream'")
     ap.add_argument("--no-overlap", action="store_true", help="weight gradients on the main stream (the form the per-kernel profiles are taken in)")
     ap.add_argument("--force-launch", action="store_true", help="take the self-launch path (torch.distributed.run children) even for one GPU")
-    ap.add_argument("--ddp-graph", action="store_true", help="data-parallel runs: also measure the hipGraph-captured step (RCCL inside the capture)")
+    ap.add_argument("--ddp-graph", action="store_true", help="data-parallel runs with --full: also measure the hipGraph-captured step (RCCL inside the capture)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and not args.graph_only:
+        # a plain run times the headline step and nothing else
+        args.no_roofline = args.no_alt = args.no_graph = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.force_launch):
         # plain `python bench.py --gpus N`: become a launcher BEFORE anything touches the GPU in this process -- the N ranks
@@ -337,12 +398,16 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    init = InitialState(ts)
     for _ in range(args.warmup):
         ts.step(real_A, real_B)
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        L = ts.step(real_A, real_B)
+    for i in range(args.steps):
+        last = i == args.steps - 1
+        if last:
+            init.restore()
+        L = ts.step(real_A, real_B, keep=last)     # keep: the forward tensors are freed after the timed loop
     barrier()
     elapsed = time.perf_counter() - t0
     if distributed:
@@ -350,9 +415,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     loss_G = float(L["loss_G"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, L)
+    del L["tensors"]
     # host time to ENQUEUE a step (no device synchronisation inside the loop): how far ahead of the GPU the host runs
     host_ms = None
-    if args.steps >= 5:                       # (short runs are the rocprofv3 --pmc passes: every extra dispatch is recorded there)
+    if args.full and args.steps >= 5:         # (short runs are the rocprofv3 --pmc passes: every extra dispatch is recorded there)
         th = time.perf_counter()
         for _ in range(5):
             ts.step(real_A, real_B)

@@ -7,7 +7,7 @@ for b in ${@:-1 2 4 16 32 64}; do
     echo "== batch $b"
     steps=10; [ "$b" -ge 16 ] && steps=5; [ "$b" -ge 64 ] && steps=3
     extra=""; [ "$b" -ge 16 ] && extra="--no-graph"
-    timeout -k 10 600 python bench.py --size ${SIZE:-256} --batch $b --steps $steps --warmup 2 --no-cpu-baseline --no-roofline $extra 2>/dev/null | grep '^{' | tail -1 | python3 -c "
+    timeout -k 10 600 python bench.py --full --size ${SIZE:-256} --batch $b --steps $steps --warmup 2 --no-cpu-baseline --no-roofline $extra 2>/dev/null | grep '^{' | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 g = d.get('hipgraph_step') or {}

@@ -10,7 +10,7 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p "$O"
 cd /tmp
 export TMPDIR=/tmp
-STATS="--steps 3 --warmup 1 --no-cpu-baseline --no-alt --no-graph --no-overlap"
+STATS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-alt --no-graph --no-overlap"
 PMC="--steps 2 --warmup 1 --no-cpu-baseline --no-alt --no-graph --no-roofline --no-overlap"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/stats" -o stats -- python3 "$R/bench.py" $STATS > "$O/stats.log" 2>&1
 echo "stats pass done"
