@@ -27,6 +27,7 @@ _SIG = {
     "conv_set_workspace": (_I, "p l"),
     "conv_set_residual": (_I, "p"),
     "conv_wgrad_workspace_floats": (_L, "iiiii"),
+    "conv_gather_workspace_floats": (_L, "i iiiiiiiii i i"),
     "conv2d_fwd": (_I, "pppp iiiiiiiii i i f p i i p"),
     "conv2d_dgrad": (_I, "ppp iiiiiiiii p i i p"),
     "conv2d_wgrad": (_I, "ppp iiiiiiiii i i i p"),

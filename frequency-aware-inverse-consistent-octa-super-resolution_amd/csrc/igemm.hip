@@ -459,7 +459,7 @@ thread_local const unsigned* g_scale_b = nullptr;
 thread_local bool g_wgrad_dry_run = false;
 thread_local float* g_wgrad_ws = nullptr;
 thread_local long g_wgrad_ws_floats = 0;
-// a weight-gradient entry takes the workspace for the duration of the call and clears it on every way out
+// a weight-gradient or gather entry takes the workspace for the duration of the call and clears it on every way out
 struct WgradWsScope {
     ~WgradWsScope() { g_wgrad_ws = nullptr; g_wgrad_ws_floats = 0; }
 };
@@ -484,6 +484,8 @@ static const float* take_residual() {
 static int run_gather(const float* x, const float* w, const float* bias, float* y, IgemmGeom& g, int act, float slope, float* wpack,
                       int wpack_state, int precision, hipStream_t s, PackJob* sink = nullptr, const unsigned* slot_a = nullptr,
                       const float* res = nullptr) {
+    // FAOCTASR_CONV_NO_SPLIT_K: a reproducible result (one block owns the whole reduction of an output element) for this call
+    struct Scope { int prev; Scope(int v) : prev(g_no_split_k) { g_no_split_k = v; } ~Scope() { g_no_split_k = prev; } } scope((precision & FAOCTASR_CONV_NO_SPLIT_K) ? 1 : 0);
     // res (faoctasr_conv_set_residual): y = gather(...) + res.  The split kernels add it in their epilogue; every other route runs
     // as usual and is followed by one in-place y += res pass.
     if (res && !sink) {
@@ -491,18 +493,25 @@ static int run_gather(const float* x, const float* w, const float* bias, float* 
             const int rc = split_try(g, x, w, bias, y, act, slope, wpack, wpack_state, s, nullptr, (precision & 0xff) == 3, slot_a, res);
             if (rc != 0) { set_route(ROUTE_BF16X3); return rc < 0 ? rc : FAOCTASR_OK; }
         }
+        if (wpack && wpack_state && (precision & 0xff) == 3) {
+            const int rc = narrow_x2_try(g, x, w, bias, y, act, slope, wpack, wpack_state, s, nullptr, slot_a, res, g_wgrad_ws, g_wgrad_ws_floats);
+            if (rc != 0) { set_route(ROUTE_NARROW_X2); return rc < 0 ? rc : FAOCTASR_OK; }
+        }
         const int rc = run_gather(x, w, bias, y, g, act, slope, wpack, wpack_state, precision, s, nullptr, slot_a, nullptr);
         if (rc) return rc;
         return faoctasr_axpby(y, res, y, (long)g.N * g.M * g.OH * g.OW, 1.f, 1.f, (faoctasr_stream_t)s);
     }
-    // FAOCTASR_CONV_NO_SPLIT_K: a reproducible result (one block owns the whole reduction of an output element) for this call
-    struct Scope { int prev; Scope(int v) : prev(g_no_split_k) { g_no_split_k = v; } ~Scope() { g_no_split_k = prev; } } scope((precision & FAOCTASR_CONV_NO_SPLIT_K) ? 1 : 0);
     precision &= 0xff;
     if (precision < 0 || precision > 3) return fail(FAOCTASR_EINVAL, "unknown conv precision %d (0 = f32, 1 = f32 direct, 2 = bf16x3, 3 = f16x2)", precision);
     if (wpack && wpack_state && precision >= 2) {
         const int rc = split_try(g, x, w, bias, y, act, slope, wpack, wpack_state, s, sink, precision == 3, slot_a);
         if (rc != 0 && sink) { sink->blocks = pack_job_blocks(sink->total / (8L * sink->g.split.Mpad)); return FAOCTASR_OK; }
         if (rc != 0) { set_route(ROUTE_BF16X3); return rc < 0 ? rc : FAOCTASR_OK; }
+    }
+    if (wpack && wpack_state && precision == 3) {
+        const int rc = narrow_x2_try(g, x, w, bias, y, act, slope, wpack, wpack_state, s, sink, slot_a, nullptr, g_wgrad_ws, g_wgrad_ws_floats);
+        if (rc != 0 && sink) { sink->blocks = pack_job_blocks(sink->total / (8L * sink->g.split.Mpad)); return FAOCTASR_OK; }
+        if (rc != 0) { set_route(ROUTE_NARROW_X2); return rc < 0 ? rc : FAOCTASR_OK; }
     }
     if (wpack && wpack_state && precision == 0) {
         const int rc = wino_try(g, x, w, bias, y, act, slope, wpack, wpack_state, s, sink);
@@ -537,6 +546,10 @@ static long wpack_floats(IgemmGeom& g, int precision) {
     long n = patch_pack_floats(pg);
     if (precision >= 2) {
         const long m = split_pack_floats_for(g);
+        n = m > n ? m : n;
+    }
+    if (precision == 3) {
+        const long m = split_pack_floats_for(g, true);                 // the narrow-map kernel's image (same layout)
         n = m > n ? m : n;
     }
     if (precision == 0) {
@@ -619,7 +632,7 @@ int faoctasr_conv_set_scales(const unsigned* slot_a, const unsigned* slot_b) {
 }
 
 // Which absmax slots the precision-3 form of a convolution-type call reads (bit 0: slot a, bit 1: slot b; 0: the call runs on a kernel
-// that needs none -- narrow map, stem, head).  kind 0..3 as faoctasr_conv_pack_job, 4 = conv2d_wgrad, 5 = conv_transpose2d_wgrad;
+// that needs none -- stem, head, a narrow map's weight gradient).  kind 0..3 as faoctasr_conv_pack_job, 4 = conv2d_wgrad, 5 = conv_transpose2d_wgrad;
 // the remaining arguments exactly as the call receives them.  The answer comes from the dispatch code itself (the packing-job and
 // dry-run paths of the launchers), so a caller that asks never computes a maximum for nothing and never misses one.
 int faoctasr_conv_needs_scales(int kind, int N, int C, int IH, int IW, int M, int KH, int KW, int stride, int pad, int reflect, int out_pad) {
@@ -660,7 +673,30 @@ int faoctasr_conv_needs_scales(int kind, int N, int C, int IH, int IW, int M, in
     PackJob job{};
     float dummy;
     rc = split_try(g, nullptr, &dummy, nullptr, nullptr, FAOCTASR_ACT_NONE, 0.f, &dummy, 1, nullptr, &job, 1, nullptr);
+    if (rc == 0) rc = narrow_x2_try(g, nullptr, &dummy, nullptr, nullptr, FAOCTASR_ACT_NONE, 0.f, &dummy, 1, nullptr, &job, nullptr, nullptr, nullptr, 0);
     return rc < 0 ? rc : (rc ? 1 : 0);
+}
+
+// Floats of the split-K workspace the precision-3 form of a gather call (kind 0..3 as faoctasr_conv_needs_scales) reduces through when
+// one is handed over (faoctasr_conv_set_workspace); 0: the call's route needs none
+long faoctasr_conv_gather_workspace_floats(int kind, int N, int C, int IH, int IW, int M, int KH, int KW, int stride, int pad, int reflect,
+                                           int out_pad) {
+    if (N <= 0 || C <= 0 || M <= 0 || stride <= 0 || pad < 0 || KH <= 0 || KW <= 0) return fail(FAOCTASR_EINVAL, "conv_gather_workspace_floats: bad shape");
+    IgemmGeom g;
+    const long kk = (long)KH * KW;
+    int rc, OH, OW;
+    if (kind == 0 || kind == 1) { OH = (IH + 2 * pad - KH) / stride + 1; OW = (IW + 2 * pad - KW) / stride + 1; }
+    else { OH = (IH - 1) * stride - 2 * pad + KH + out_pad; OW = (IW - 1) * stride - 2 * pad + KW + out_pad; }
+    if (OH <= 0 || OW <= 0) return fail(FAOCTASR_EINVAL, "conv_gather_workspace_floats: bad shape");
+    switch (kind) {
+        case 0: rc = geom_fwd(g, N, C, IH, IW, M, OH, OW, KH, KW, stride, pad, reflect, (long)C * kk, kk); break;
+        case 1: rc = geom_transposed(g, N, M, OH, OW, C, IH, IW, KH, KW, stride, pad, kk, (long)C * kk); break;
+        case 2: rc = geom_transposed(g, N, C, IH, IW, M, OH, OW, KH, KW, stride, pad, kk, (long)M * kk); break;
+        case 3: rc = geom_fwd(g, N, M, OH, OW, C, IH, IW, KH, KW, stride, pad, 0, (long)M * kk, kk); break;
+        default: return fail(FAOCTASR_EINVAL, "conv_gather_workspace_floats: unknown kind %d", kind);
+    }
+    if (rc) return rc;
+    return narrow_x2_workspace_floats_for(g);
 }
 
 int faoctasr_conv_set_residual(const float* residual) {
@@ -690,6 +726,7 @@ int faoctasr_conv2d_fwd(const float* x, const float* w, const float* bias, float
                         int KH, int KW, int stride, int pad, int reflect, int act, float slope, float* wpack, int wpack_state,
                         int precision, faoctasr_stream_t stream) {
     const unsigned* const slot_a = take_scale_a();
+    WgradWsScope ws_scope;                                              // the split-K workspace, if any: this call's, cleared on every way out
     const float* const res = take_residual();
     if (bad_ptr(x, w, y)) return fail(FAOCTASR_EINVAL, "conv2d_fwd: null pointer");
     if (N < 0 || C <= 0 || M <= 0 || stride <= 0 || pad < 0) return fail(FAOCTASR_EINVAL, "conv2d_fwd: bad shape");
@@ -711,6 +748,7 @@ int faoctasr_conv2d_fwd(const float* x, const float* w, const float* bias, float
 int faoctasr_conv2d_dgrad(const float* dy, const float* w, float* dx, int N, int C, int IH, int IW, int M, int KH, int KW,
                           int stride, int pad, float* wpack, int wpack_state, int precision, faoctasr_stream_t stream) {
     const unsigned* const slot_a = take_scale_a();
+    WgradWsScope ws_scope;                                              // the split-K workspace, if any: this call's, cleared on every way out
     const float* const res = take_residual();
     if (bad_ptr(dy, w, dx)) return fail(FAOCTASR_EINVAL, "conv2d_dgrad: null pointer");
     const int OH = (IH + 2 * pad - KH) / stride + 1, OW = (IW + 2 * pad - KW) / stride + 1;
@@ -778,6 +816,7 @@ int faoctasr_conv_transpose2d_fwd(const float* x, const float* w, const float* b
                                   int M, int KH, int KW, int stride, int pad, int out_pad, int act, float slope, float* wpack,
                                   int wpack_state, int precision, faoctasr_stream_t stream) {
     const unsigned* const slot_a = take_scale_a();
+    WgradWsScope ws_scope;                                              // the split-K workspace, if any: this call's, cleared on every way out
     const float* const res = take_residual();
     if (bad_ptr(x, w, y)) return fail(FAOCTASR_EINVAL, "conv_transpose2d_fwd: null pointer");
     const int OH = (IH - 1) * stride - 2 * pad + KH + out_pad, OW = (IW - 1) * stride - 2 * pad + KW + out_pad;
@@ -793,6 +832,7 @@ int faoctasr_conv_transpose2d_dgrad(const float* dy, const float* w, float* dx, 
                                     int KW, int stride, int pad, int out_pad, float* wpack, int wpack_state, int precision,
                                     faoctasr_stream_t stream) {
     const unsigned* const slot_a = take_scale_a();
+    WgradWsScope ws_scope;                                              // the split-K workspace, if any: this call's, cleared on every way out
     const float* const res = take_residual();
     if (bad_ptr(dy, w, dx)) return fail(FAOCTASR_EINVAL, "conv_transpose2d_dgrad: null pointer");
     const int OH = (IH - 1) * stride - 2 * pad + KH + out_pad, OW = (IW - 1) * stride - 2 * pad + KW + out_pad;

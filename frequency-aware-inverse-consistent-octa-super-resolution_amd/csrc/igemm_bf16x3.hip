@@ -28,7 +28,8 @@
 #define SP_NCW8 0                 // 1: large stride-1 layers on the 8-consumer-wave form (sp_launch_wide_block)
 #endif
 #ifndef SP_MIN_W
-#define SP_MIN_W 24               // narrower output maps are left to the fp32 narrow-map kernels (a 32-pixel tile row would be mostly empty)
+#define SP_MIN_W 24               // narrower output maps are left to the narrow-map kernels (a 32-pixel tile row would be mostly empty):
+                                  // igemm_nm_x2.hip at f16x2, igemm_nm.hip otherwise
 #endif
 #ifndef SP_CDMA
 #define SP_CDMA 0                 // (experiment) 1: the CONSUMER waves issue the weight LDS-DMA of the next slab, one row per tap step
@@ -872,8 +873,9 @@ static bool sp_fits(const SplitGeom& g, int NI, int SI) {
     return sp_lds(g, NI, SI, false) <= SP_LDS_MAX;                     // the output staging is optional (sp_launch)
 }
 
-// 1 when the layer can run on the split kernel (decided by the layer shape only)
-int split_geom_from(const IgemmGeom& f, SplitGeom& g, int f16 = 0) {
+// 1 when the layer can run on the split kernel (decided by the layer shape only).  narrow: the geometry of the same image for the
+// f16x2 narrow-map kernel (igemm_nm_x2.hip), which takes any phase width and stages no patch
+int split_geom_from(const IgemmGeom& f, SplitGeom& g, int f16, bool narrow) {
     g = SplitGeom{};
     g.f16 = f16 ? 1 : 0;
     {
@@ -890,7 +892,7 @@ int split_geom_from(const IgemmGeom& f, SplitGeom& g, int f16 = 0) {
     const int ngroups = (g.C + 15) / 16;
     for (int p = 0; p < g.nphase; ++p) {
         const int T = g.t0[p + 1] - g.t0[p];
-        if (T == 0 || g.gw[p] < SP_MIN_W) return 0;
+        if (T == 0 || (!narrow && g.gw[p] < SP_MIN_W)) return 0;
         int oy0 = 1 << 30, ox0 = 1 << 30, oy1 = -(1 << 30), ox1 = -(1 << 30);
         for (int t = g.t0[p]; t < g.t0[p + 1]; ++t) {
             const int oy = (f.taps[t] & 0xff) - 64, ox = ((f.taps[t] >> 8) & 0xff) - 64;
@@ -915,6 +917,7 @@ int split_geom_from(const IgemmGeom& f, SplitGeom& g, int f16 = 0) {
     }
     for (int p = g.nphase; p < 5; ++p) g.pack_off[p] = off;
     g.plane_stride = (off + 7) & ~7L;
+    if (narrow) return 1;
     if (!sp_fits(g, 2, g.SI) && !sp_fits(g, 1, g.SI)) return 0;
     return 1;
 }
@@ -1062,7 +1065,7 @@ int launch_split(const float* x, const float* wp, const float* bias, float* y, S
 int split_try(const IgemmGeom& f, const float* x, const float* w, const float* bias, float* y, int act, float slope, float* wpack,
               int wpack_state, hipStream_t s, PackJob* sink, int f16, const unsigned* x_slot, const float* res) {
     SplitGeom g;
-    if (!split_geom_from(f, g, f16)) return 0;
+    if (!split_geom_from(f, g, f16, false)) return 0;
     if (f16 && !sink && !x_slot) return fail(FAOCTASR_EINVAL, "precision 3 (f16x2) needs the gathered tensor's absmax slot: faoctasr_conv_set_scales");
     if (sink) {
         sink->type = PACK_SPLIT; sink->w = w; sink->wp = wpack; sink->g.split = g; sink->total = g.pack_off[4];
@@ -1078,10 +1081,40 @@ int split_try(const IgemmGeom& f, const float* x, const float* w, const float* b
     return rc == FAOCTASR_OK ? 1 : rc;
 }
 
-long split_pack_floats_for(const IgemmGeom& f) {
+long split_pack_floats_for(const IgemmGeom& f, bool narrow) {
     SplitGeom g;
-    if (!split_geom_from(f, g)) return 0;
+    if (!split_geom_from(f, g, 0, narrow)) return 0;
     return split_pack_floats(g);
+}
+
+// The f16x2 narrow-map geometry of a layer the wide split kernel leaves alone because a phase is narrower than SP_MIN_W; 0 when the
+// narrow kernel does not take it either
+static int narrow_x2_geom(const IgemmGeom& f, SplitGeom& g) {
+    if (split_geom_from(f, g, 1, false) || !split_geom_from(f, g, 1, true)) return 0;
+    bool narrow = false;
+    for (int p = 0; p < g.nphase; ++p) narrow = narrow || g.gw[p] < SP_MIN_W;
+    return narrow && narrow_x2_eligible(g);
+}
+
+long narrow_x2_workspace_floats_for(const IgemmGeom& f) {
+    SplitGeom g;
+    return narrow_x2_geom(f, g) ? narrow_x2_workspace_floats(g) : 0;
+}
+
+int narrow_x2_try(const IgemmGeom& f, const float* x, const float* w, const float* bias, float* y, int act, float slope, float* wpack,
+                  int wpack_state, hipStream_t s, PackJob* sink, const unsigned* x_slot, const float* res, float* ws, long ws_floats) {
+    SplitGeom g;
+    if (!narrow_x2_geom(f, g)) return 0;
+    if (!sink && !x_slot) return fail(FAOCTASR_EINVAL, "precision 3 (f16x2) needs the gathered tensor's absmax slot: faoctasr_conv_set_scales");
+    if (sink) {
+        sink->type = PACK_SPLIT; sink->w = w; sink->wp = wpack; sink->g.split = g; sink->total = g.pack_off[4];
+        return 1;
+    }
+    if (wpack_state == 1) {
+        const int rc = launch_split_pack(w, wpack, g, s);
+        if (rc) return rc;
+    }
+    return launch_narrow_x2(x, wpack, bias, y, g, act, slope, s, x_slot, res, ws, ws_floats);
 }
 
 }  // namespace faoctasr

@@ -110,11 +110,21 @@ int launch_wgrad_s1(const float* x, const float* dy, float* dw, int N, int C, in
 int split_try(const IgemmGeom& f, const float* x, const float* w, const float* bias, float* y, int act, float slope, float* wpack,
               int wpack_state, hipStream_t s, PackJob* sink = nullptr, int f16 = 0, const unsigned* x_slot = nullptr,
               const float* res = nullptr);          // 1 launched, 0 not eligible, <0 error; res: y += res fused into the epilogue
-long split_pack_floats_for(const IgemmGeom& f);       // 0 when not eligible
+long split_pack_floats_for(const IgemmGeom& f, bool narrow = false);       // 0 when not eligible
+// f16x2 narrow-map kernel (igemm_nm_x2.hip) on the split image of the layer (precision 3, a phase narrower than the split kernel's
+// tiles): 1 launched / recorded, 0 not eligible, <0 error.  ws / ws_floats: the split-K workspace (faoctasr_conv_set_workspace; may be null)
+int narrow_x2_try(const IgemmGeom& f, const float* x, const float* w, const float* bias, float* y, int act, float slope, float* wpack,
+                  int wpack_state, hipStream_t s, PackJob* sink, const unsigned* x_slot, const float* res, float* ws, long ws_floats);
+long narrow_x2_workspace_floats_for(const IgemmGeom& f);        // floats of the split-K workspace the narrow kernel would use; 0: none
+int narrow_x2_eligible(const SplitGeom& g);
+long narrow_x2_workspace_floats(const SplitGeom& g);
+int launch_narrow_x2(const float* x, const float* wp, const float* bias, float* y, SplitGeom& g, int act, float slope, hipStream_t s,
+                     const unsigned* x_slot, const float* res, float* ws, long ws_floats);
 // the activation operands' absmax slots handed over by faoctasr_conv_set_scales for this thread's next convolution-type call
 extern thread_local const unsigned* g_scale_a;
 extern thread_local const unsigned* g_scale_b;
-// the workspace faoctasr_conv_set_workspace left for this thread's next weight-gradient call (two-pass reduction, wgrad_x3.hip)
+// the workspace faoctasr_conv_set_workspace left for this thread's next weight-gradient call (two-pass reduction, wgrad_x3.hip) or
+// gather call (split-K partials of the f16x2 narrow-map kernel, igemm_nm_x2.hip)
 extern thread_local float* g_wgrad_ws;
 extern thread_local long g_wgrad_ws_floats;
 

@@ -114,9 +114,9 @@ def absmax_slot(t):
 
 def _producer_slot(x, C, H, W):
     """A fresh absmax slot for a producer call (BatchNorm forward / backward, cat2_act forward) whose output can feed a
-    split-precision convolution (>= 16 channels, a map >= 24 wide, H*W a multiple of 4); None otherwise.  ``_producer_call`` hands it
-    over."""
-    if conv_precision != 3 or C < 16 or W < 24 or (H * W) & 3:
+    split-precision convolution (>= 16 channels -- wide maps on the split kernel, narrow ones on the narrow-map kernel --, H*W a
+    multiple of 4); None otherwise.  ``_producer_call`` hands it over."""
+    if conv_precision != 3 or C < 16 or (H * W) & 3:
         return None
     return _new_slot(x.device)
 
@@ -147,6 +147,27 @@ def _wgrad_workspace(device, C, M, KH, KW, stride, prec):
     n = _wgrad_ws_need.get(key)
     if n is None:
         n = _wgrad_ws_need[key] = _lib.load().faoctasr_conv_wgrad_workspace_floats(C, M, KH, KW, stride)
+    if n > 0:
+        ws = _lib.workspace(device, n + (1 << 16), tag="wgrad")
+        call("conv_set_workspace", ptr(ws), ws.numel())
+
+
+_gather_ws_need = {}
+
+
+def _gather_workspace(device, kind, dims, reflect=0, out_pad=0):
+    """Hand the CURRENT stream's scratch buffer to the next gather call (kind 0..3 as ``_needs_scales``) when its precision-3 route
+    splits the reduction through one (the f16x2 narrow-map kernel: ``faoctasr_conv_gather_workspace_floats``).  Shared with the
+    weight-gradient calls of the stream; it is only live between the call's two launches."""
+    if conv_precision != 3:
+        return
+    key = (kind, dims, reflect, out_pad)
+    n = _gather_ws_need.get(key)
+    if n is None:
+        n = _lib.load().faoctasr_conv_gather_workspace_floats(kind, *dims, reflect, out_pad)
+        if n < 0:
+            raise _lib.KernelError("conv_gather_workspace_floats: " + _lib.load().faoctasr_last_error().decode())
+        _gather_ws_need[key] = n
     if n > 0:
         ws = _lib.workspace(device, n + (1 << 16), tag="wgrad")
         call("conv_set_workspace", ptr(ws), ws.numel())
@@ -405,6 +426,7 @@ class _Conv2d(Function):
         y = torch.empty((N, M, OH, OW), dtype=torch.float32, device=x.device)
         wp, wst, ent = _wpack(w, 0, (N, C, IH, IW, M, KH, KW, stride, pad), reflect)
         sx = absmax_slot(x) if _needs_scales(0, (N, C, IH, IW, M, KH, KW, stride, pad), reflect) else None
+        _gather_workspace(x.device, 0, (N, C, IH, IW, M, KH, KW, stride, pad), reflect)
         _conv_call("conv2d_fwd", (ptr(x), ptr(w), ptr(bias), ptr(y), N, C, IH, IW, M, KH, KW, stride, pad, reflect, act, slope, ptr(wp), wst,
                                   conv_precision | (NO_SPLIT_K if reproducible_forward else 0), stream_ptr()), sx)
         _packed(ent, wst)
@@ -441,6 +463,7 @@ class _Conv2d(Function):
             if reflect:
                 dxp = torch.empty((N, C, IH + 2 * pad, IW + 2 * pad), dtype=torch.float32, device=x.device)
                 wp, wst, ent = _wpack(ctx.w_ref, 1, (N, C, IH + 2 * pad, IW + 2 * pad, M, KH, KW, stride, 0))
+                _gather_workspace(x.device, 1, dg_dims)
                 _conv_call("conv2d_dgrad", (ptr(dy), ptr(w), ptr(dxp), N, C, IH + 2 * pad, IW + 2 * pad, M, KH, KW, stride, 0, ptr(wp), wst,
                                             conv_precision, st), sd)
                 _packed(ent, wst)
@@ -451,6 +474,7 @@ class _Conv2d(Function):
             else:
                 dx = torch.empty_like(x)
                 wp, wst, ent = _wpack(ctx.w_ref, 1, (N, C, IH, IW, M, KH, KW, stride, pad))
+                _gather_workspace(x.device, 1, dg_dims)
                 _conv_call("conv2d_dgrad", (ptr(dy), ptr(w), ptr(dx), N, C, IH, IW, M, KH, KW, stride, pad, ptr(wp), wst, conv_precision, st), sd, None, res)
                 _packed(ent, wst)
         if ctx.needs_input_grad[1]:
@@ -499,6 +523,7 @@ class _ConvTranspose2d(Function):
         wp, wst, ent = _wpack(w, 2, (N, C, IH, IW, M, KH, KW, stride, pad), 0, out_pad)
         sx = absmax_slot(x) if _needs_scales(2, (N, C, IH, IW, M, KH, KW, stride, pad), 0, out_pad) else None
         ctx.sx = sx
+        _gather_workspace(x.device, 2, (N, C, IH, IW, M, KH, KW, stride, pad), 0, out_pad)
         _conv_call("conv_transpose2d_fwd", (ptr(x), ptr(w), ptr(bias), ptr(y), N, C, IH, IW, M, KH, KW, stride, pad, out_pad, act, slope,
                                             ptr(wp), wst, conv_precision | (NO_SPLIT_K if reproducible_forward else 0), stream_ptr()), sx)
         _packed(ent, wst)
@@ -526,6 +551,7 @@ class _ConvTranspose2d(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             wp, wst, ent = _wpack(ctx.w_ref, 3, (N, C, IH, IW, M, KH, KW, stride, pad), 0, out_pad)
+            _gather_workspace(x.device, 3, (N, C, IH, IW, M, KH, KW, stride, pad), 0, out_pad)
             _conv_call("conv_transpose2d_dgrad", (ptr(dy), ptr(w), ptr(dx), N, C, IH, IW, M, KH, KW, stride, pad, out_pad, ptr(wp), wst,
                                                   conv_precision, st), sdy if need_d else None)
             _packed(ent, wst)

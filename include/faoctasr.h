@@ -28,7 +28,7 @@ int faoctasr_version(void);
 const char* faoctasr_last_error(void);
 /* diagnostics (bench.py's per-family roofline): the kernel family the calling thread's last convolution-type call went to:
  * 1 flat implicit GEMM, 2 LDS-patch implicit GEMM, 3 Winograd F(2x2,3x3), 4 bf16x3 split, 5 M=1 head (VALU), 6 narrow-map GEMM,
- * 7 stem input gradient (1..4 input channels, VALU); 11 flat weight gradient, 12 LDS-patch weight gradient, 13 stride-1 / 4x4
+ * 7 stem input gradient (1..4 input channels, VALU), 8 narrow-map f16x2 GEMM (precision 3); 11 flat weight gradient, 12 LDS-patch weight gradient, 13 stride-1 / 4x4
  * stride-2 weight gradient (wgrad_s1), 14 M=1 weight gradient, 15 bf16x3 weight gradient (wgrad_x3), 16 stem weight gradient (VALU) */
 int faoctasr_last_route(void);
 
@@ -107,6 +107,12 @@ int faoctasr_conv_needs_scales(int kind, int N, int C, int IH, int IW, int M, in
  * too small) the call accumulates with atomics as before.  The workspace is only used between the call's two launches: calls on
  * the same stream may share it.                                                                                            */
 int faoctasr_conv_set_workspace(float* workspace, long nfloats);
+/* The same hand-over for the NEXT gather call (conv2d_fwd / dgrad, conv_transpose2d_fwd / dgrad) at precision 3 whose route is the
+ * f16x2 narrow-map kernel: with a workspace of faoctasr_conv_gather_workspace_floats(...) floats (kind 0..3 and the call's arguments as
+ * faoctasr_conv_needs_scales) a small grid splits its reduction, every slice stores its partial there and a second kernel sums them in
+ * a fixed order and applies bias, activation and residual -- no atomics, bit-reproducible.  Without one the grid is not split.      */
+long faoctasr_conv_gather_workspace_floats(int kind, int N, int C, int IH, int IW, int M, int KH, int KW, int stride, int pad,
+                                           int reflect, int out_pad);
 /* y = gather(...) + residual for the NEXT gather call (conv2d_fwd / dgrad, conv_transpose2d_fwd / dgrad) of the calling thread;
  * `residual` has the output's shape.  x + conv_block(x) (model.py:420,505) sends two gradients to x -- the skip's and the first
  * convolution's input gradient -- and autograd adds them with an elementwise kernel (66 per train step); handing the skip's gradient
