@@ -57,6 +57,10 @@ _SIG = {
     "freq_mix_bwd": (_I, "pppppppp l p"),
     "ssim_fwd": (_I, "ppp iiii p"),
     "ssim_bwd": (_I, "ppp i f pp iiii p"),
+    "dft_tables": (_I, "p i p"),
+    "phase_loss_workspace_floats": (_L, "iiii"),
+    "phase_loss_fwd": (_I, "pppp f ppp iiii p"),
+    "phase_loss_bwd": (_I, "ppp f ppp iiii p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

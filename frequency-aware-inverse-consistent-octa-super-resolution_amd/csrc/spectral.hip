@@ -1,0 +1,379 @@
+// Spectral phase-consistency loss (model.py:36-58 of the reference) on the exact-f32 MFMA (v_mfma_f32_32x32x2_f32).
+//
+//   m[u,v] = 1 - exp(-0.5 (u_c^2 + v_c^2) / radius^2)           u_c, v_c: centred frequency of the UNSHIFTED bin,
+//   a_x    = m * log|fft2(x)|  over (C,H,W)                      u_c = ((u + H/2) mod H) - H/2 (the reference's fftshift is the
+//   loss   = -<a_x, a_y> / (|a_x| |a_y|)                         same permutation on both operands of a dot product: dropped)
+//
+// The DFT of a real image is four real GEMMs with the symmetric tables C_n[k,l] = cos(2 pi kl/n), S_n = sin(2 pi kl/n):
+//   [P | Q] = X [C_W | S_W]                  row pass    (faoctasr_sgemm_batched, x and y in one launch)
+//   Re = C_H P - S_H Q,  J = S_H P + C_H Q   column pass (J = -Im; only Re^2 + J^2 and the pair's gradient are ever used)
+// The column pass accumulates Re and J of the x image and the y image of one (sample, channel) in the same block, forms
+// a = m * 0.5 * log(Re^2 + J^2) in the accumulator registers and reduces <a_x,a_y>, |a_x|^2, |a_y|^2 over its tile: the spectrum
+// makes no separate trip through memory for abs / log / mul / flatten.  One partial triple per block goes to the workspace with
+// plain stores; a finishing kernel adds them in a fixed order in double (no float atomics: the loss is bit-reproducible).
+//
+// Saved for the backward: Re and J, 8 bytes per pixel and image (512 KiB per 256x256 image); the backward recomputes m and a.
+//   dRe = g * dloss/da * m * Re / |F|^2,  dJ likewise,  dloss/da_x = -(a_y / (|a_x||a_y|) - <a_x,a_y> a_x / (|a_x|^3 |a_y|))
+//   [T1 | T2] = [C_H dRe + S_H dJ | C_H dJ - S_H dRe]            fused with the formation of dRe, dJ (one kernel)
+//   dX = [T1 | T2] [C_W ; S_W]                                   one more faoctasr_sgemm_batched, K = 2W
+//
+// A bin whose amplitude is exactly zero gives log 0 = -inf and a NaN loss, as in the reference: no clamp, no epsilon (either
+// would change the value everywhere).
+//
+// Block 256 threads, output tile 64x64, K chunk 16; waves 2x2, four 32x32 accumulators each (Re_x, J_x, Re_y, J_y).
+#include <cstdint>
+#include "common.h"
+
+namespace faoctasr {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int PH_KC = 16, PH_T = 64;
+
+__device__ __forceinline__ int centred(int u, int n) { return (u + n / 2) % n - n / 2; }
+
+// the reference builds its mask in double and rounds it to float once
+__device__ __forceinline__ float phase_mask(int uc, int vc, double inv2r2) {
+    return (float)(1.0 - exp(-(double)(uc * uc + vc * vc) * inv2r2));
+}
+
+// out[0, 2n^2): [C_n | S_n], n rows of 2n;  out[2n^2, 4n^2): [C_n ; S_n], 2n rows of n.  Phase reduced mod n in integers.
+__global__ __launch_bounds__(256) void dft_tables_kernel(float* __restrict__ out, int n) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)n * n) return;
+    const int k = (int)(e / n), l = (int)(e % n);
+    const long ph = ((long)k * l) % n;
+    const double t = 2.0 * (double)ph / (double)n;
+    const float c = (float)cospi(t), s = (float)sinpi(t);
+    out[(long)k * 2 * n + l] = c;
+    out[(long)k * 2 * n + n + l] = s;
+    float* st = out + 2L * n * n;
+    st[e] = c;
+    st[(long)n * n + e] = s;
+}
+
+struct PhaseWs {
+    double* stats;      // [N][4]: <a_x,a_y>, |a_x|^2, |a_y|^2, unused
+    float* part;        // [N*C][tiles][3]
+    float* planes;      // [2 (x,y)][N*C][2 (Re,J)][H][W]
+    float* pq;          // [2 (x,y)][N*C][H][2W]: [P | Q] in the forward, [T1 | T2] in the backward
+    long total;
+};
+
+static PhaseWs phase_ws(float* ws, long N, long C, long H, long W) {
+    PhaseWs p;
+    const long tiles = ((H + PH_T - 1) / PH_T) * ((W + PH_T - 1) / PH_T);
+    long off = 0;
+    p.stats = (double*)ws;
+    off += 8 * N;
+    p.part = ws + off;
+    off += 3 * N * C * tiles;
+    off = (off + 3) & ~3L;
+    p.planes = ws + off;
+    off += 4 * N * C * H * W;
+    p.pq = ws + off;
+    off += 4 * N * C * H * W;
+    p.total = off;
+    return p;
+}
+
+// stage one 16 x 64 chunk of the symmetric tables: rows k0.. of [C_H | S_H], columns r0.. (C_H[r][k] = C_H[k][r])
+__device__ __forceinline__ void stage_tables(float* Cs, float* Ss, const float* __restrict__ tabH, int H, int k0, int r0, int tid) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i;
+        const int k = k0 + (e >> 6), r = r0 + (e & 63);
+        const bool ok = k < H && r < H;
+        Cs[e] = ok ? tabH[(long)k * 2 * H + r] : 0.f;
+        Ss[e] = ok ? tabH[(long)k * 2 * H + H + r] : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void phase_col_fwd_kernel(const float* __restrict__ pq, const float* __restrict__ tabH,
+                                                            float* __restrict__ planes, float* __restrict__ part, int H, int W,
+                                                            long imgs, double inv2r2) {
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[4][PH_KC * PH_T];
+    __shared__ float red[12];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int u0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const float* pqx = pq + img * H * 2 * W;
+    const float* pqy = pq + (imgs + img) * H * 2 * W;
+    f32x16 rx, jx, ry, jy;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rx[r] = jx[r] = ry[r] = jy[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, u0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int k = k0 + (e >> 6), v = v0 + (e & 63);
+            const bool ok = k < H && v < W;
+            const long o = (long)k * 2 * W + v;
+            Bs[0][e] = ok ? pqx[o] : 0.f;
+            Bs[1][e] = ok ? pqx[o + W] : 0.f;
+            Bs[2][e] = ok ? pqy[o] : 0.f;
+            Bs[3][e] = ok ? pqy[o + W] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float px = Bs[0][bo], qx = Bs[1][bo], py = Bs[2][bo], qy = Bs[3][bo];
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, px, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(as, px, jx, 0, 0, 0);
+            ry = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, py, ry, 0, 0, 0);
+            jy = __builtin_amdgcn_mfma_f32_32x32x2f32(as, py, jy, 0, 0, 0);
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qx, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qx, jx, 0, 0, 0);
+            ry = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qy, ry, 0, 0, 0);
+            jy = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qy, jy, 0, 0, 0);
+        }
+    }
+    // epilogue: a = m * 0.5 * log(Re^2 + J^2) for both images, the three sums, Re and J for the backward
+    const int v = v0 + wn * 32 + l31;
+    float dot = 0.f, nx = 0.f, ny = 0.f;
+    if (v < W) {
+        const int vc = centred(v, W);
+        const long hw = (long)H * W;
+        float* plx = planes + img * 2 * hw;
+        float* ply = planes + (imgs + img) * 2 * hw;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int u = u0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (u < H) {
+                const float m = phase_mask(centred(u, H), vc, inv2r2);
+                const float ax = m * 0.5f * logf(rx[rr] * rx[rr] + jx[rr] * jx[rr]);
+                const float ay = m * 0.5f * logf(ry[rr] * ry[rr] + jy[rr] * jy[rr]);
+                dot += ax * ay;
+                nx += ax * ax;
+                ny += ay * ay;
+                const long o = (long)u * W + v;
+                plx[o] = rx[rr];
+                plx[hw + o] = jx[rr];
+                ply[o] = ry[rr];
+                ply[hw + o] = jy[rr];
+            }
+        }
+    }
+    dot = wave_sum(dot);
+    nx = wave_sum(nx);
+    ny = wave_sum(ny);
+    if (lane == 0) {
+        red[wave * 3 + 0] = dot;
+        red[wave * 3 + 1] = nx;
+        red[wave * 3 + 2] = ny;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        const long tile = (long)blockIdx.y * gridDim.x + blockIdx.x, tiles = (long)gridDim.x * gridDim.y;
+        part[(img * tiles + tile) * 3 + tid] = (red[tid] + red[3 + tid]) + (red[6 + tid] + red[9 + tid]);
+    }
+}
+
+// one thread per sample adds that sample's partial triples in a fixed order (double), keeps the sums for the backward and writes
+// the loss; thread 0 then averages the per-sample losses in index order
+__global__ __launch_bounds__(64) void phase_finish_kernel(const float* __restrict__ part, double* __restrict__ stats,
+                                                          float* __restrict__ loss_per_sample, float* __restrict__ loss_mean, int N,
+                                                          long per_sample) {
+    for (int b = threadIdx.x; b < N; b += 64) {
+        const float* p = part + (long)b * per_sample * 3;
+        double d = 0.0, sx = 0.0, sy = 0.0;
+        for (long i = 0; i < per_sample; ++i) {
+            d += (double)p[3 * i];
+            sx += (double)p[3 * i + 1];
+            sy += (double)p[3 * i + 2];
+        }
+        stats[4 * b] = d;
+        stats[4 * b + 1] = sx;
+        stats[4 * b + 2] = sy;
+        stats[4 * b + 3] = 0.0;
+        const double eps = 1e-8;                             // torch.cosine_similarity's default
+        loss_per_sample[b] = (float)(-d / (fmax(sqrt(sx), eps) * fmax(sqrt(sy), eps)));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int b = 0; b < N; ++b) s += (double)loss_per_sample[b];
+        *loss_mean = (float)(s / (double)N);
+    }
+}
+
+// [T1 | T2] = [C_H dRe + S_H dJ | C_H dJ - S_H dRe] for the x image (want_x) and / or the y image (want_y) of one
+// (sample, channel); dRe, dJ are formed from the saved planes while they are staged into LDS
+__global__ __launch_bounds__(256) void phase_col_bwd_kernel(const float* __restrict__ planes, const float* __restrict__ tabH,
+                                                            const double* __restrict__ stats, const float* __restrict__ g,
+                                                            float* __restrict__ T, int H, int W, int C, int N, long imgs, double inv2r2,
+                                                            int want_x, int want_y) {
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[4][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int h0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const long hw = (long)H * W;
+    const float* plx = planes + img * 2 * hw;
+    const float* ply = planes + (imgs + img) * 2 * hw;
+    // dloss/da_x = -(k1 a_y - k2x a_x), dloss/da_y = -(k1 a_x - k2y a_y), times the incoming gradient of the batch mean
+    const double* st = stats + 4 * (img / C);
+    const double eps = 1e-8;
+    const double d = st[0], sx = fmax(sqrt(st[1]), eps), sy = fmax(sqrt(st[2]), eps);
+    const double k1d = 1.0 / (sx * sy);
+    const float gs = g[0] / (float)N;
+    const float k1 = (float)k1d, k2x = (float)(d / (sx * sx) * k1d), k2y = (float)(d / (sy * sy) * k1d);
+    const int sv = v0 + (tid & 63);
+    const int svc = centred(sv < W ? sv : 0, W);
+    f32x16 t1x, t2x, t1y, t2y;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t1x[r] = t2x[r] = t1y[r] = t2y[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, h0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int u = k0 + (e >> 6);
+            float drx = 0.f, djx = 0.f, dry = 0.f, djy = 0.f;
+            if (u < H && sv < W) {
+                const long o = (long)u * W + sv;
+                const float Rx = plx[o], Jx = plx[hw + o], Ry = ply[o], Jy = ply[hw + o];
+                const float fx = Rx * Rx + Jx * Jx, fy = Ry * Ry + Jy * Jy;
+                const float m = phase_mask(centred(u, H), svc, inv2r2);
+                const float ax = m * 0.5f * logf(fx), ay = m * 0.5f * logf(fy);
+                const float wx = -gs * (k1 * ay - k2x * ax) * m / fx;
+                const float wy = -gs * (k1 * ax - k2y * ay) * m / fy;
+                drx = wx * Rx;
+                djx = wx * Jx;
+                dry = wy * Ry;
+                djy = wy * Jy;
+            }
+            Bs[0][e] = drx;
+            Bs[1][e] = djx;
+            Bs[2][e] = dry;
+            Bs[3][e] = djy;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            if (want_x) {
+                const float dr = Bs[0][bo], dj = Bs[1][bo];
+                t1x = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1x, 0, 0, 0);
+                t2x = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2x, 0, 0, 0);
+                t1x = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1x, 0, 0, 0);
+                t2x = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2x, 0, 0, 0);
+            }
+            if (want_y) {
+                const float dr = Bs[2][bo], dj = Bs[3][bo];
+                t1y = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1y, 0, 0, 0);
+                t2y = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2y, 0, 0, 0);
+                t1y = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1y, 0, 0, 0);
+                t2y = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2y, 0, 0, 0);
+            }
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < W) {
+        float* Tx = T + img * H * 2 * W;
+        float* Ty = T + (imgs + img) * H * 2 * W;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int h = h0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (h < H) {
+                const long o = (long)h * 2 * W + v;
+                if (want_x) {
+                    Tx[o] = t1x[rr];
+                    Tx[o + W] = t2x[rr];
+                }
+                if (want_y) {
+                    Ty[o] = t1y[rr];
+                    Ty[o + W] = t2y[rr];
+                }
+            }
+        }
+    }
+}
+
+static int phase_check(const char* what, const void* ws, int N, int C, int H, int W, float radius) {
+    if (N < 1 || C < 1 || H < 2 || W < 2) return fail(FAOCTASR_EINVAL, "%s: bad shape N %d C %d H %d W %d (H, W >= 2)", what, N, C, H, W);
+    if (H > 8192 || W > 8192) return fail(FAOCTASR_EUNSUPPORTED, "%s: H %d, W %d > 8192", what, H, W);
+    if ((long)N * C > 65535) return fail(FAOCTASR_EUNSUPPORTED, "%s: N*C %ld > 65535", what, (long)N * C);
+    if ((long)N * C * H > (1L << 21)) return fail(FAOCTASR_EUNSUPPORTED, "%s: N*C*H %ld > 2^21", what, (long)N * C * H);
+    if (!(radius > 0.f)) return fail(FAOCTASR_EINVAL, "%s: radius %g must be positive", what, (double)radius);
+    if ((uintptr_t)ws & 7) return fail(FAOCTASR_EINVAL, "%s: workspace must be 8-byte aligned", what);
+    return FAOCTASR_OK;
+}
+
+}  // namespace faoctasr
+
+using namespace faoctasr;
+
+extern "C" int faoctasr_dft_tables(float* out, int n, faoctasr_stream_t stream) {
+    if (!out) return fail(FAOCTASR_EINVAL, "dft_tables: null pointer");
+    if (n < 1 || n > 8192) return fail(FAOCTASR_EINVAL, "dft_tables: n %d outside [1, 8192]", n);
+    const long total = (long)n * n;
+    hipLaunchKernelGGL(dft_tables_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, n);
+    return check_launch("dft_tables");
+}
+
+extern "C" long faoctasr_phase_loss_workspace_floats(int N, int C, int H, int W) {
+    if (N < 1 || C < 1 || H < 2 || W < 2) {
+        fail(FAOCTASR_EINVAL, "phase_loss_workspace_floats: bad shape N %d C %d H %d W %d (H, W >= 2)", N, C, H, W);
+        return -1;
+    }
+    return phase_ws(nullptr, N, C, H, W).total;
+}
+
+extern "C" int faoctasr_phase_loss_fwd(const float* x, const float* y, const float* tabH, const float* tabW, float radius,
+                                       float* loss_per_sample, float* loss_mean, float* workspace, int N, int C, int H, int W,
+                                       faoctasr_stream_t stream) {
+    if (!x || !y || !tabH || !tabW || !loss_per_sample || !loss_mean || !workspace) return fail(FAOCTASR_EINVAL, "phase_loss_fwd: null pointer");
+    int rc = phase_check("phase_loss_fwd", workspace, N, C, H, W, radius);
+    if (rc) return rc;
+    const PhaseWs p = phase_ws(workspace, N, C, H, W);
+    const long imgs = (long)N * C;
+    // row pass [P | Q] = X [C_W | S_W]: x and y as the two batch entries of one launch (the stride is their address difference)
+    const intptr_t diff = (intptr_t)y - (intptr_t)x;
+    if (diff % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "phase_loss_fwd: x and y are not 4-byte aligned to each other");
+    rc = faoctasr_sgemm_batched(x, tabW, p.pq, (int)(imgs * H), 2 * W, W, W, 2 * W, 2 * W, (long)(diff / (intptr_t)sizeof(float)), 0,
+                                imgs * H * 2 * W, 2, stream);
+    if (rc) return rc;
+    const double inv2r2 = 0.5 / ((double)radius * (double)radius);
+    dim3 grid((W + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(phase_col_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)p.pq, tabH, p.planes, p.part, H, W, imgs,
+                       inv2r2);
+    rc = check_launch("phase_loss_fwd (column pass)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(phase_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const float*)p.part, p.stats, loss_per_sample,
+                       loss_mean, N, (long)C * grid.x * grid.y);
+    return check_launch("phase_loss_fwd (finish)");
+}
+
+extern "C" int faoctasr_phase_loss_bwd(const float* g, const float* tabH, const float* tabW, float radius, float* dx, float* dy,
+                                       float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream) {
+    if (!g || !tabH || !tabW || !workspace) return fail(FAOCTASR_EINVAL, "phase_loss_bwd: null pointer");
+    int rc = phase_check("phase_loss_bwd", workspace, N, C, H, W, radius);
+    if (rc) return rc;
+    if (!dx && !dy) return FAOCTASR_OK;
+    const PhaseWs p = phase_ws(workspace, N, C, H, W);
+    const long imgs = (long)N * C;
+    const double inv2r2 = 0.5 / ((double)radius * (double)radius);
+    dim3 grid((W + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(phase_col_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)p.planes, tabH, (const double*)p.stats, g,
+                       p.pq, H, W, C, N, imgs, inv2r2, dx ? 1 : 0, dy ? 1 : 0);
+    rc = check_launch("phase_loss_bwd (column pass)");
+    if (rc) return rc;
+    // dX = [T1 | T2] [C_W ; S_W]: the stacked table is the second half of the table buffer
+    const float* stacked = tabW + 2L * W * W;
+    const long sT = imgs * H * 2 * W;
+    if (dx && dy) {
+        const intptr_t diff = (intptr_t)dy - (intptr_t)dx;
+        if (diff % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "phase_loss_bwd: dx and dy are not 4-byte aligned to each other");
+        return faoctasr_sgemm_batched(p.pq, stacked, dx, (int)(imgs * H), W, 2 * W, 2 * W, W, W, sT, 0, (long)(diff / (intptr_t)sizeof(float)), 2,
+                                      stream);
+    }
+    return faoctasr_sgemm_batched(dx ? p.pq : p.pq + sT, stacked, dx ? dx : dy, (int)(imgs * H), W, 2 * W, 2 * W, W, W, 0, 0, 0, 1, stream);
+}

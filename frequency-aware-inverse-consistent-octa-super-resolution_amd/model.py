@@ -32,6 +32,20 @@ class TVLoss(nn.Module):
         return self.TVLoss_weight * 2 * (h_tv / count_h + w_tv / count_w) / b
 
 
+class phase_consistency_loss(nn.Module):
+    """model.py:36-58 (``criterion_phase`` of train.py:94): minus the cosine similarity of the Gaussian-high-pass-weighted
+    log-amplitude spectra of ``x`` and ``y``.  One fused HIP path (``ops.phase_loss``) instead of a Python mask loop, ``fft2``,
+    ``fftshift``, ``abs``, ``log`` and ``cosine_similarity``.  The reference reads sample 0 only; here the loss is evaluated per
+    sample and averaged over the batch (identical at batch 1).  ``radius`` is the mask's, fixed at 5 in the reference."""
+
+    def __init__(self):
+        super().__init__()
+        self.radius = 5
+
+    def forward(self, x, y):
+        return ops.phase_loss(x, y, self.radius)
+
+
 class Discriminator(nn.Module):
     """PatchGAN of model.py:86-127: 4x4 convs with bias, five stride-2 stages then two stride-1,
     BatchNorm2d + LeakyReLU(0.2) from the second conv on."""

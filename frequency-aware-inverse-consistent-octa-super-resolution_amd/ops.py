@@ -973,6 +973,68 @@ def freq_split(x, r_hp, r_lp):
 
 
 # ----------------------------------------------------------------------------------------
+# spectral phase-consistency loss (model.py:36-58) as DFT GEMMs
+# ----------------------------------------------------------------------------------------
+_dft_cache = {}
+
+
+def dft_tables(n, device):
+    """The cos / sin tables of the n-point DFT, ``[C_n | S_n]`` followed by ``[C_n ; S_n]`` (4 n^2 floats), built on the device by
+    ``faoctasr_dft_tables`` once per (n, device) on the calling stream; cached here next to the circulants.  A caller that uses
+    the tables from several streams builds them before it forks (``TrainStep.step`` does)."""
+    device = torch.device(device)
+    key = (n, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    t = _dft_cache.get(key)
+    if t is None:
+        if device.type != "cuda":
+            raise _lib.KernelError("dft_tables: the tables are built by a HIP kernel; got device %s" % device)
+        t = torch.empty(4 * n * n, dtype=torch.float32, device=device)
+        call("dft_tables", ptr(t), n, stream_ptr())
+        _dft_cache[key] = t
+    return t
+
+
+class _PhaseLoss(Function):
+    @staticmethod
+    def forward(ctx, x, y, radius):
+        x, y = _c(x), _c(y)
+        if x.dim() != 4 or x.shape != y.shape:
+            raise _lib.KernelError("phase_loss operands must be (B,C,H,W) tensors of one shape: %s vs %s" % (tuple(x.shape), tuple(y.shape)))
+        N, C, H, W = x.shape
+        tab_h, tab_w = dft_tables(H, x.device), dft_tables(W, x.device)
+        n = _lib.load().faoctasr_phase_loss_workspace_floats(N, C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_phase_loss_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        # the workspace carries the spectrum planes to the backward, so it belongs to this call (not to the per-stream scratch)
+        ws = torch.empty(n, dtype=torch.float32, device=x.device)
+        per_sample = torch.empty(N, dtype=torch.float32, device=x.device)
+        mean = torch.empty((), dtype=torch.float32, device=x.device)
+        call("phase_loss_fwd", ptr(x), ptr(y), ptr(tab_h), ptr(tab_w), radius, ptr(per_sample), ptr(mean), ptr(ws), N, C, H, W, stream_ptr())
+        ctx.save_for_backward(ws, tab_h, tab_w)
+        ctx.cfg = (radius, N, C, H, W)
+        return mean
+
+    @staticmethod
+    def backward(ctx, g):
+        ws, tab_h, tab_w = ctx.saved_tensors
+        radius, N, C, H, W = ctx.cfg
+        g = _c(g)
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=ws.device) if ctx.needs_input_grad[0] else None
+        dy = torch.empty((N, C, H, W), dtype=torch.float32, device=ws.device) if ctx.needs_input_grad[1] else None
+        call("phase_loss_bwd", ptr(g), ptr(tab_h), ptr(tab_w), radius, ptr(dx), ptr(dy), ptr(ws), N, C, H, W, stream_ptr())
+        return dx, dy, None
+
+
+def phase_loss(x, y, radius=5.0):
+    """``phase_consistency_loss()(x, y)`` of model.py:36-58: minus the cosine similarity of the mask-weighted log-amplitude
+    spectra of ``x`` and ``y`` (B,C,H,W), as a 0-dim tensor with gradients to both inputs.  The reference reads sample 0 only
+    (its train.py runs batch 1); here the loss is evaluated per sample and averaged over the batch, which is the same thing at
+    B = 1 (the rule of ``high_pass`` / ``low_pass``).  A spectrum bin of exactly zero amplitude gives NaN, as in the reference.
+    Always exact fp32 (``conv_precision`` does not apply)."""
+    return _PhaseLoss.apply(x, y, float(radius))
+
+
+# ----------------------------------------------------------------------------------------
 # losses and the discriminator head
 # ----------------------------------------------------------------------------------------
 LOSS_MSE, LOSS_L1, LOSS_BCE_LOGITS = 0, 1, 2

@@ -261,7 +261,7 @@ class TrainStep:
     def __init__(self, netG_A2B=None, netG_B2A=None, netD_A=None, netD_B=None, device="cuda", lr=1.3e-4, betas=(0.9, 0.999),
                  beta1=0.25, beta2=10.0, beta3=2.0, beta4=0.5, beta5=0.5, ssim_weight=0.0, whf_weight=0.0, dwt_levels=1,
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
-                 reproducible_forward=False):
+                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -284,6 +284,8 @@ class TrainStep:
                 n.apply(weights_init_normal)
         self.w = dict(beta1=beta1, beta2=beta2, beta3=beta3, beta4=beta4, beta5=beta5)     # train.py:50-54
         self.ssim_weight, self.whf_weight, self.dwt_levels = ssim_weight, whf_weight, dwt_levels
+        #: opt-in spectral term: phase_weight * (1 + phase_consistency_loss) per image pair (model.py:36-58; 0 = reference behaviour)
+        self.phase_weight, self.phase_radius = phase_weight, phase_radius
         self.dwt_loss = DWTForward(J=dwt_levels, wave="haar", mode="reflect").to(dev) if whf_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
@@ -563,7 +565,7 @@ class TrainStep:
         return o, L, root
 
     def _extension_terms(self, rec, real):
-        """One image pair's share of the opt-in terms of ``generator_loss`` (SSIM: train.py:234; wavelet-HF L1)."""
+        """One image pair's share of the opt-in terms of ``generator_loss`` (SSIM: train.py:234; wavelet-HF L1; spectral phase)."""
         t = {}
         if self.ssim_weight:
             t["loss_ssim"] = self.ssim_weight * (1 - ops.ssim(rec, real))
@@ -574,6 +576,8 @@ class TrainStep:
             for a, b in zip(yh_r, yh_t):
                 acc = acc + ops.l1_loss(a, b, self.whf_weight)
             t["loss_whf"] = acc
+        if self.phase_weight:
+            t["loss_phase"] = self.phase_weight * (1 + ops.phase_loss(rec, real, self.phase_radius))
         return t
 
     def generator_loss(self, o, real_A, real_B):
@@ -607,6 +611,10 @@ class TrainStep:
                     t = t + ops.l1_loss(a, b, self.whf_weight)
             L["loss_whf"] = t
             total = total + t
+        if self.phase_weight:
+            L["loss_phase"] = self.phase_weight * ((1 + ops.phase_loss(o["recovered_A"], real_A, self.phase_radius)) +
+                                                   (1 + ops.phase_loss(o["recovered_B"], real_B, self.phase_radius)))
+            total = total + L["loss_phase"]
         L["_root"] = total
         L["loss_G"] = total if done is None else total.detach() + done
         return L
@@ -668,6 +676,9 @@ class TrainStep:
         # cleared every step, not only on steps without a plan: otherwise the images of other batch shapes and of evaluation calls
         # touched since the last plan-less step would be swept into the rebuilt plan and repacked on every step
         ops.clear_touched()
+        if self.phase_weight:           # the DFT tables are read on both chains' streams: built (once) before the streams fork
+            for n in sorted(set(real_A.shape[-2:]) | set(real_B.shape[-2:])):
+                ops.dft_tables(n, self.device)
         # below ~2 x 256^2 pixels per batch the step is bound by the host's enqueue rate, and the extra events / stream switches
         # of the schedule cost more than the concurrency returns (batch 1 at 256^2: 41.8 vs 39.3 ms; batch 2: 48.3 vs 52.8)
         # ... a CAPTURED step has no host in its way: there the schedule pays at every size (batch 1: 29.9 against 35.4 ms per replay)

@@ -244,6 +244,31 @@ int faoctasr_ssim_fwd(const float* a, const float* b, float* sums, int N, int C,
 int faoctasr_ssim_bwd(const float* a, const float* b, const float* g, int gN, float gscale, float* da, float* db,
                       int N, int C, int H, int W, faoctasr_stream_t stream);
 
+/* ---- spectral phase-consistency loss (model.py:36-58; train.py:28,94) -------------------------
+ * loss_b = -cos(a_x, a_y), a = flatten(m * log|fft2(.)|) over (C,H,W) of sample b, m[u,v] = 1 - exp(-0.5 d^2 / radius^2) with d
+ * the distance of bin (u,v) from the zero frequency (the reference's fftshift permutes both operands of the dot product alike
+ * and is dropped).  The reference reads sample 0 only (its train.py runs batch 1); here the loss is evaluated per sample and
+ * loss_mean is the batch mean -- identical at N = 1.  A bin whose amplitude is exactly zero gives log 0 = -inf and a NaN
+ * loss, as in the reference: there is no clamp and no epsilon.  The DFT runs as real GEMMs on v_mfma_f32_32x32x2_f32 with
+ * cos / sin tables (csrc/spectral.hip); the operands are always exact fp32, whatever the convolutions' precision.
+ * DFT tables for one n, built once per (n, device) in double on the device into a caller-owned buffer of 4*n*n floats:
+ * [C_n | S_n] (n rows of 2n) followed by [C_n ; S_n] (2n rows of n), C_n[k,l] = cos(2 pi kl/n), S_n[k,l] = sin(2 pi kl/n). */
+int faoctasr_dft_tables(float* out, int n, faoctasr_stream_t stream);
+/* workspace of one forward / backward pair (model.py:36-58): per-sample sums, per-block partial sums, the spectrum planes the
+ * backward reads (Re, -Im: 8 bytes per pixel of x and of y) and the row-pass buffer; -1 on a bad shape */
+long faoctasr_phase_loss_workspace_floats(int N, int C, int H, int W);
+/* model.py:36-58 forward for x, y[N,C,H,W] (H, W >= 2, even or odd): loss_per_sample[N], loss_mean[1].  Enqueues the row pass
+ * (faoctasr_sgemm_batched), the fused column pass + log-amplitude + partial sums, and a fixed-order finishing reduction
+ * (no float atomics: bit-reproducible).  tabH, tabW: faoctasr_dft_tables of H and of W.  `workspace` (8-byte aligned) must
+ * stay untouched until the matching backward has run. */
+int faoctasr_phase_loss_fwd(const float* x, const float* y, const float* tabH, const float* tabW, float radius,
+                            float* loss_per_sample, float* loss_mean, float* workspace, int N, int C, int H, int W,
+                            faoctasr_stream_t stream);
+/* model.py:36-58 backward: dx, dy[N,C,H,W] (either may be NULL) = g[0] * d loss_mean / d(x|y), g a device scalar; reads the
+ * workspace the forward of the same arguments filled (and reuses its row-pass buffer). */
+int faoctasr_phase_loss_bwd(const float* g, const float* tabH, const float* tabW, float radius, float* dx, float* dy,
+                            float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
