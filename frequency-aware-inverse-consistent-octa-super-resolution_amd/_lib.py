@@ -61,6 +61,9 @@ _SIG = {
     "phase_loss_workspace_floats": (_L, "iiii"),
     "phase_loss_fwd": (_I, "pppp f ppp iiii p"),
     "phase_loss_bwd": (_I, "ppp f ppp iiii p"),
+    "tv_loss_workspace_floats": (_L, "iiii"),
+    "tv_loss_fwd": (_I, "ppp iiii f p"),
+    "tv_loss_bwd": (_I, "ppp iiii f p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

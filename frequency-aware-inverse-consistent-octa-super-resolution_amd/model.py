@@ -17,14 +17,18 @@ from .wavelets import DWTForward
 
 
 class TVLoss(nn.Module):
-    """model.py:17-33.  A dead value on the train step (train.py:178 computes it, nothing reads it);
-    kept as host-side tensor plumbing, not a kernel."""
+    """model.py:17-33 (``criterion_ssim_TV_loss`` of train.py:98, evaluated as ``TVLoss()(fake_B) * 0.5`` at train.py:178, where
+    nothing reads it).  A 4-D fp32 device tensor with H, W >= 2 runs as one fused HIP forward / backward pair
+    (``ops.tv_loss``: one pass over ``x``, no strided temporaries, bit-reproducible); anything else -- CPU tensors, other dtypes,
+    a degenerate size -- keeps the reference's composition of stock ops.  ``TrainStep(tv_weight=...)`` is the opt-in term."""
 
     def __init__(self, TVLoss_weight=1):
         super().__init__()
         self.TVLoss_weight = TVLoss_weight
 
     def forward(self, x):
+        if x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and x.shape[2] >= 2 and x.shape[3] >= 2:
+            return ops.tv_loss(x, self.TVLoss_weight)
         b, c, h, w = x.shape
         count_h, count_w = c * (h - 1) * w, c * h * (w - 1)
         h_tv = ((x[:, :, 1:, :] - x[:, :, :h - 1, :]) ** 2).sum()

@@ -1035,6 +1035,45 @@ def phase_loss(x, y, radius=5.0):
 
 
 # ----------------------------------------------------------------------------------------
+# total-variation loss (model.py:17-33)
+# ----------------------------------------------------------------------------------------
+class _TVLoss(Function):
+    @staticmethod
+    def forward(ctx, x, weight):
+        x = _c(x)
+        if x.dim() != 4 or x.dtype != torch.float32 or x.shape[2] < 2 or x.shape[3] < 2:
+            raise _lib.KernelError("tv_loss operand must be a (B,C,H,W) fp32 tensor with H, W >= 2, got %s %s" % (tuple(x.shape), x.dtype))
+        B, C, H, W = x.shape
+        n = _lib.load().faoctasr_tv_loss_workspace_floats(B, C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_tv_loss_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        ws = _lib.workspace(x.device, n)              # per stream: the partial sums are consumed by the same call's second launch
+        call("tv_loss_fwd", ptr(x), ptr(out), ptr(ws), B, C, H, W, weight, stream_ptr())
+        ctx.save_for_backward(x)
+        ctx.weight = weight
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        x, = ctx.saved_tensors
+        B, C, H, W = x.shape
+        dx = torch.empty_like(x)
+        call("tv_loss_bwd", ptr(x), ptr(_c(g)), ptr(dx), B, C, H, W, ctx.weight, stream_ptr())
+        return dx, None
+
+
+def tv_loss(x, weight=1.0):
+    """``TVLoss(weight)(x)`` of model.py:17-33 for x (B,C,H,W), H, W >= 2, as a 0-dim fp32 tensor with a gradient to ``x``:
+    ``weight * 2 * (sum of squared vertical differences / (C (H-1) W) + sum of squared horizontal differences / (C H (W-1))) / B``.
+    One pass over ``x`` and a fixed-order reduction forward, one stencil kernel backward (csrc/tv.hip); bit-reproducible, always
+    exact fp32 (``conv_precision`` does not apply)."""
+    return _TVLoss.apply(x, float(weight))
+
+
+# ----------------------------------------------------------------------------------------
 # losses and the discriminator head
 # ----------------------------------------------------------------------------------------
 LOSS_MSE, LOSS_L1, LOSS_BCE_LOGITS = 0, 1, 2

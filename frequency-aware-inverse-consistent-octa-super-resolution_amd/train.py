@@ -261,11 +261,16 @@ class TrainStep:
     def __init__(self, netG_A2B=None, netG_B2A=None, netD_A=None, netD_B=None, device="cuda", lr=1.3e-4, betas=(0.9, 0.999),
                  beta1=0.25, beta2=10.0, beta3=2.0, beta4=0.5, beta5=0.5, ssim_weight=0.0, whf_weight=0.0, dwt_levels=1,
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
-                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0):
+                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
-        the exact-f32 kernels', csrc/split16.h).  Maps narrower than 24 and 1-channel stems / heads run on the f32 kernels in every mode."""
+        the exact-f32 kernels', csrc/split16.h).  Maps narrower than 24 and 1-channel stems / heads run on the f32 kernels in every mode.
+
+        ``tv_weight`` (default 0: nothing is launched): adds ``loss_tv = tv_weight * (TVLoss()(fake_B) + TVLoss()(fake_A))`` to
+        ``loss_G`` (model.py:17-33, ``ops.tv_loss``).  The reference evaluates ``TVLoss()(fake_B) * 0.5`` only (train.py:178) and
+        never adds it to a loss; ``tv_weight=0.5`` reproduces that scaling on the B side.  Both fakes carry the term here because
+        each generator chain of the schedule owns exactly one of them: each share is computed on its chain's stream."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -286,6 +291,8 @@ class TrainStep:
         self.ssim_weight, self.whf_weight, self.dwt_levels = ssim_weight, whf_weight, dwt_levels
         #: opt-in spectral term: phase_weight * (1 + phase_consistency_loss) per image pair (model.py:36-58; 0 = reference behaviour)
         self.phase_weight, self.phase_radius = phase_weight, phase_radius
+        #: opt-in smoothness term on the generators' outputs: tv_weight * (TVLoss(fake_B) + TVLoss(fake_A)) (model.py:17-33; 0 = off)
+        self.tv_weight = tv_weight
         self.dwt_loss = DWTForward(J=dwt_levels, wave="haar", mode="reflect").to(dev) if whf_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
@@ -532,6 +539,8 @@ class TrainStep:
                 ops.bce_with_logits(o["hf_feature_B"], o["hf_feature_recovered_B"], w["beta1"])
             root = L["loss_GAN_B2A"] + L["loss_cycle_BAB"]
             extra_B = self._extension_terms(o["recovered_B"], real_B)       # opt-in SSIM / wavelet-HF terms: one half per chain
+            if self.tv_weight:                  # fake_A was made on this stream: its share of the TV term joins chain B's root
+                extra_B["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_A"])
             for k, v in extra_B.items():
                 root = root + v
         # ---- chain A, losses and backward
@@ -542,6 +551,8 @@ class TrainStep:
             L["loss_cycle_ABA"] = ops.l1_loss(o["recovered_A"], real_A, w["beta3"]) + ops.bce_with_logits(o["hf_feature_A"], o["hf_feature_recovered_A"])
             chain_A = L["loss_GAN_A2B"] + L["loss_cycle_ABA"]
             extra_A = self._extension_terms(o["recovered_A"], real_A)
+            if self.tv_weight:                  # ... and fake_B's share joins chain A's, on chain A's stream
+                extra_A["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_B"])
             for k, v in extra_A.items():
                 chain_A = chain_A + v
             ops.wgrad_stream = side
@@ -581,7 +592,8 @@ class TrainStep:
         return t
 
     def generator_loss(self, o, real_A, real_B):
-        """train.py:221-236 (+ the opt-in SSIM term of the commented line train.py:234 and a wavelet-HF L1 term).  ``L["_root"]`` is
+        """train.py:221-236 (+ the opt-in SSIM term of the commented line train.py:234, a wavelet-HF L1 term, the spectral phase term and
+        the total-variation term of the two fakes).  ``L["_root"]`` is
         what remains to be back-propagated (everything, unless ``forward_generators`` already did the identity terms)."""
         w = self.w
         ones, _ = self.targets(real_A.shape[0])
@@ -615,6 +627,9 @@ class TrainStep:
             L["loss_phase"] = self.phase_weight * ((1 + ops.phase_loss(o["recovered_A"], real_A, self.phase_radius)) +
                                                    (1 + ops.phase_loss(o["recovered_B"], real_B, self.phase_radius)))
             total = total + L["loss_phase"]
+        if self.tv_weight:
+            L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
+            total = total + L["loss_tv"]
         L["_root"] = total
         L["loss_G"] = total if done is None else total.detach() + done
         return L

@@ -269,6 +269,20 @@ int faoctasr_phase_loss_fwd(const float* x, const float* y, const float* tabH, c
 int faoctasr_phase_loss_bwd(const float* g, const float* tabH, const float* tabW, float radius, float* dx, float* dy,
                             float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
 
+/* ---- total-variation loss (model.py:17-33; train.py:98,178) ------------------------------------
+ * L = weight * 2 * (S_h / count_h + S_w / count_w) / B for x[B,C,H,W] (H, W >= 2), S_h = sum (x[.,.,i+1,j] - x[.,.,i,j])^2,
+ * S_w = sum (x[.,.,i,j+1] - x[.,.,i,j])^2, count_h = C (H-1) W, count_w = C H (W-1)  (csrc/tv.hip).  float4 loads when W % 4 == 0
+ * and the pointers are 16-byte aligned, a scalar path otherwise.  Always exact fp32, whatever the convolutions' precision.
+ * workspace of one forward (two partial sums per block; free again once the forward has run on its stream); -1 on a bad shape */
+long faoctasr_tv_loss_workspace_floats(int B, int C, int H, int W);
+/* out[0] = L (overwritten).  One pass over x with S_h and S_w kept apart, per-block partials in `workspace`, then a single-block
+ * kernel that adds them in a fixed order in double and applies the divisors (no atomics: bit-reproducible). */
+int faoctasr_tv_loss_fwd(const float* x, float* out, float* workspace, int B, int C, int H, int W, float weight,
+                         faoctasr_stream_t stream);
+/* dx[B,C,H,W] (overwritten) = g[0] * dL/dx, g a device scalar: one stencil kernel, reads x only. */
+int faoctasr_tv_loss_bwd(const float* x, const float* g, float* dx, int B, int C, int H, int W, float weight,
+                         faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
