@@ -64,6 +64,8 @@ _SIG = {
     "tv_loss_workspace_floats": (_L, "iiii"),
     "tv_loss_fwd": (_I, "ppp iiii f p"),
     "tv_loss_bwd": (_I, "ppp iiii f p"),
+    "dwt2d_analysis": (_I, "ppp l ii ppi ppi i p"),
+    "dwt2d_synthesis": (_I, "ppp l iiii ppi ppi i p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -874,6 +874,144 @@ def haar_sfb2d(ll, hi):
     return _HaarSFB2D.apply(ll, hi)
 
 
+# ----------------------------------------------------------------------------------------
+# general filter-bank DWT (csrc/dwt.hip): any even tap count up to 16, five padding modes, any size
+# ----------------------------------------------------------------------------------------
+DWT_MAX_TAPS = 16
+DWT_MODES = (0, 1, 2, 4, 6)             # zero, symmetric, periodization, reflect, periodic (wavelets.mode_to_int)
+_tap_arrays = {}
+
+
+def host_taps(t):
+    """The taps of a filter as a tuple of Python floats.  A tensor is read once (a device tensor: one synchronising copy) and
+    the tuple cached on the tensor object for as long as its version counter stands, so that later calls -- those of a graph
+    capture among them -- touch no device memory: the kernels take their taps by value.  Two consequences: the FIRST call on a
+    device tensor must not fall inside a graph capture (``GraphedTrainStep`` warms up eagerly before it captures; anything else
+    that captures calls the module once beforehand), and a write that does not bump the version counter (through ``.data``) is
+    not seen -- assign a new tensor or use ``copy_`` to change taps."""
+    if not isinstance(t, torch.Tensor):
+        return tuple(float(v) for v in t)
+    c = getattr(t, "_fa_taps", None)
+    if c is not None and c[0] == t._version:
+        return c[1]
+    vals = tuple(t.detach().reshape(-1).to(torch.float32).tolist())
+    t._fa_taps = (t._version, vals)
+    return vals
+
+
+def prime_taps(t, vals):
+    """Record ``vals`` as the taps of tensor ``t`` without reading it (its owner knows them), unless a record stands."""
+    c = getattr(t, "_fa_taps", None)
+    if c is None or c[0] != t._version:
+        t._fa_taps = (t._version, tuple(float(v) for v in vals))
+
+
+def _tap_array(vals):
+    a = _tap_arrays.get(vals)
+    if a is None:
+        if len(_tap_arrays) > 256:
+            _tap_arrays.clear()
+        a = _tap_arrays[vals] = (ctypes.c_float * len(vals))(*vals)
+    return ctypes.cast(a, ctypes.c_void_p)
+
+
+def dwt_bank(lo_w, hi_w, lo_h, hi_h):
+    """Validate one level's filter bank -- the W-axis pair first, as AFB2D / SFB2D receive them -- and return it as host tuples."""
+    bank = tuple(host_taps(t) for t in (lo_w, hi_w, lo_h, hi_h))
+    for lo, hi in (bank[:2], bank[2:]):
+        if len(lo) != len(hi):
+            raise ValueError("lowpass and highpass filters must have the same length, got %d and %d" % (len(lo), len(hi)))
+        if len(lo) % 2 or not 2 <= len(lo) <= DWT_MAX_TAPS:
+            raise ValueError("filter length %d: the filter banks take an even number of taps, 2 to %d (pad an odd-length filter with "
+                             "a zero tap)" % (len(lo), DWT_MAX_TAPS))
+    return bank
+
+
+def dwt_out_size(n, L, mode):
+    """pywt.dwt_coeff_len as the reference uses it (lowlevel.py:134-153)."""
+    return (n + 1) // 2 if mode == 2 else (n + L - 1) // 2
+
+
+def _dwt_analysis(x, bank, mode):
+    N, C, H, W = x.shape
+    Lw, Lh = len(bank[0]), len(bank[2])
+    if mode not in DWT_MODES:
+        raise NotImplementedError("padding mode %d is not built (zero, symmetric, reflect, periodic, periodization are)" % mode)
+    if H < Lh // 2 + 1 or W < Lw // 2 + 1:
+        raise ValueError("a %d x %d image is below the minimum side L/2 + 1 of a %d (H) x %d (W) tap bank" % (H, W, Lh, Lw))
+    x = _c(x)
+    oh, ow = dwt_out_size(H, Lh, mode), dwt_out_size(W, Lw, mode)
+    ll = torch.empty((N, C, oh, ow), dtype=torch.float32, device=x.device)
+    hi = torch.empty((N, C, 3, oh, ow), dtype=torch.float32, device=x.device)
+    call("dwt2d_analysis", ptr(x), ptr(ll), ptr(hi), N * C, H, W, _tap_array(bank[2]), _tap_array(bank[3]), Lh,
+         _tap_array(bank[0]), _tap_array(bank[1]), Lw, mode, stream_ptr())
+    return ll, hi
+
+
+def _dwt_synthesis(ll, hi, bank, mode, crop=None):
+    ref = ll if ll is not None else hi
+    N, C = ref.shape[0], ref.shape[1]
+    nh, nw = ref.shape[-2], ref.shape[-1]
+    if ll is not None and hi is not None and (tuple(hi.shape) != (N, C, 3, nh, nw)):
+        raise ValueError("lowpass %s and highpass %s coefficients do not belong together" % (tuple(ll.shape), tuple(hi.shape)))
+    Lw, Lh = len(bank[0]), len(bank[2])
+    if mode not in DWT_MODES:
+        raise NotImplementedError("padding mode %d is not built (zero, symmetric, reflect, periodic, periodization are)" % mode)
+    per = mode == 2
+    if nh < ((Lh + 3) // 4 if per else Lh // 2) or nw < ((Lw + 3) // 4 if per else Lw // 2):
+        raise ValueError("%d x %d coefficients are below the minimum side of a %d (H) x %d (W) tap bank" % (nh, nw, Lh, Lw))
+    fh, fw = (2 * nh, 2 * nw) if per else (2 * nh - Lh + 2, 2 * nw - Lw + 2)
+    oh, ow = (fh, fw) if crop is None else (min(fh, crop[0]), min(fw, crop[1]))
+    ll = _c(ll) if ll is not None else None
+    hi = _c(hi) if hi is not None else None
+    y = torch.empty((N, C, oh, ow), dtype=torch.float32, device=ref.device)
+    call("dwt2d_synthesis", ptr(ll), ptr(hi), ptr(y), N * C, nh, nw, oh, ow, _tap_array(bank[2]), _tap_array(bank[3]), Lh,
+         _tap_array(bank[0]), _tap_array(bank[1]), Lw, mode, stream_ptr())
+    return y
+
+
+class _AFB2D(Function):
+    """One analysis level (lowlevel.py:312-365).  ``bank`` = (lo_w, hi_w, lo_h, hi_h) host tuples, correlation kernels.  The
+    backward is the reference's own: the synthesis bank run on the ANALYSIS taps, cropped to the input's size -- the adjoint for
+    zero padding (and for periodization at even sizes), not for the folding and wrapping modes."""
+
+    @staticmethod
+    def forward(ctx, x, bank, mode):
+        ctx.cfg = (bank, mode, x.shape[-2], x.shape[-1])
+        return _dwt_analysis(x, bank, mode)
+
+    @staticmethod
+    def backward(ctx, dll, dhi):
+        bank, mode, H, W = ctx.cfg
+        return _dwt_synthesis(dll, dhi, bank, mode, crop=(H, W)), None, None
+
+
+class _SFB2D(Function):
+    """One synthesis level (lowlevel.py:647-694); the backward is the analysis bank run on the SYNTHESIS taps with the mode's
+    padding, as the reference defines it."""
+
+    @staticmethod
+    def forward(ctx, ll, hi, bank, mode):
+        ctx.cfg = (bank, mode, ll is not None, hi is not None)
+        return _dwt_synthesis(ll, hi, bank, mode)
+
+    @staticmethod
+    def backward(ctx, dy):
+        bank, mode, has_ll, has_hi = ctx.cfg
+        dll, dhi = _dwt_analysis(dy, bank, mode)
+        return dll if has_ll else None, dhi if has_hi else None, None, None
+
+
+def afb2d(x, lo_w, hi_w, lo_h, hi_h, mode):
+    """(ll, hi) of one analysis level; the filters are tensors or sequences, W-axis pair first, in correlation order."""
+    return _AFB2D.apply(x, dwt_bank(lo_w, hi_w, lo_h, hi_h), int(mode))
+
+
+def sfb2d(ll, hi, lo_w, hi_w, lo_h, hi_h, mode):
+    """One synthesis level; ``hi`` (or ``ll``) may be None for zeros."""
+    return _SFB2D.apply(ll, hi, dwt_bank(lo_w, hi_w, lo_h, hi_h), int(mode))
+
+
 class _HaarDFront(Function):
     @staticmethod
     def forward(ctx, x, mode):

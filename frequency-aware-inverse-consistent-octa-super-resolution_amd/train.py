@@ -261,7 +261,7 @@ class TrainStep:
     def __init__(self, netG_A2B=None, netG_B2A=None, netD_A=None, netD_B=None, device="cuda", lr=1.3e-4, betas=(0.9, 0.999),
                  beta1=0.25, beta2=10.0, beta3=2.0, beta4=0.5, beta5=0.5, ssim_weight=0.0, whf_weight=0.0, dwt_levels=1,
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
-                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0):
+                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect"):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -270,7 +270,11 @@ class TrainStep:
         ``tv_weight`` (default 0: nothing is launched): adds ``loss_tv = tv_weight * (TVLoss()(fake_B) + TVLoss()(fake_A))`` to
         ``loss_G`` (model.py:17-33, ``ops.tv_loss``).  The reference evaluates ``TVLoss()(fake_B) * 0.5`` only (train.py:178) and
         never adds it to a loss; ``tv_weight=0.5`` reproduces that scaling on the B side.  Both fakes carry the term here because
-        each generator chain of the schedule owns exactly one of them: each share is computed on its chain's stream."""
+        each generator chain of the schedule owns exactly one of them: each share is computed on its chain's stream.
+
+        ``dwt_wave`` / ``dwt_mode``: the filter bank and padding of the opt-in wavelet-HF term (``whf_weight``), handed to
+        ``DWTForward`` -- 'haar', a tap tuple, a wavelet object or ``daubechies(N)`` (wavelets.py).  The defaults are the Haar bank
+        the term has always used."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -293,7 +297,7 @@ class TrainStep:
         self.phase_weight, self.phase_radius = phase_weight, phase_radius
         #: opt-in smoothness term on the generators' outputs: tv_weight * (TVLoss(fake_B) + TVLoss(fake_A)) (model.py:17-33; 0 = off)
         self.tv_weight = tv_weight
-        self.dwt_loss = DWTForward(J=dwt_levels, wave="haar", mode="reflect").to(dev) if whf_weight else None
+        self.dwt_loss = DWTForward(J=dwt_levels, wave=dwt_wave, mode=dwt_mode).to(dev) if whf_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)

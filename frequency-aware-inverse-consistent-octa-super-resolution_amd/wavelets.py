@@ -1,13 +1,27 @@
-"""2-D Haar DWT / IDWT modules on fused HIP kernels, behind the interface of the reference's
-vendored pytorch_wavelets (pytorch_wavelets/pytorch_wavelets/dwt/transform2d.py:7-148,
-lowlevel.py:312-365,647-694).
+"""2-D DWT / IDWT modules on fused HIP kernels, behind the interface of the reference's vendored pytorch_wavelets
+(pytorch_wavelets/pytorch_wavelets/dwt/transform2d.py:7-148, lowlevel.py:91-172,226-271,312-365,647-694).
 
-Scope: wave 'haar'/'db1', even H and W, the padding modes for which the
-2-tap bank needs no padding at even sizes ('zero', 'symmetric', 'reflect', 'periodic':
-lowlevel.py:153-154 gives p = 0).  Anything else raises -- the OCTA code never reaches it.
+Two paths.  The Haar modules (``wave='haar'`` / ``'db1'``, or 2-tap Haar arrays) run the 2x2 block kernels the OCTA networks use
+and keep their scope: even H and W, the modes in which the 2-tap bank needs no padding; anything else raises
+``NotImplementedError``.  Every other filter bank runs the general kernels of csrc/dwt.hip: any even number of taps from 2 to
+16, per axis, any image size, the modes 'zero', 'symmetric', 'reflect', 'periodic' and 'periodization' ('per').
+
+``wave`` takes the reference's three forms, of which the name is resolved for Haar only -- the reference looks names up in
+PyWavelets, whose tables are not part of this package:
+  * a 2-tuple ``(lo, hi)`` or 4-tuple ``(lo_col, hi_col, lo_row, hi_row)`` of tap sequences: ``dec_lo, dec_hi`` for
+    ``DWTForward``, ``rec_lo, rec_hi`` for ``DWTInverse``;
+  * any object with ``dec_lo, dec_hi, rec_lo, rec_hi`` (a ``pywt.Wavelet``, or ``daubechies(N)`` below).
+An odd number of taps raises ``ValueError`` (pad with a zero tap, as PyWavelets does for biorthogonal pairs), and so does a
+side below ``L/2 + 1``: one fold or wrap then covers the padding.  ``'constant'`` and ``'replicate'`` are not built.
+
+The backward passes are the reference's own definitions, so that a drop-in user gets its training trajectory: AFB2D's is the
+synthesis bank on the analysis taps plus a crop, SFB2D's the analysis bank on the synthesis taps with the mode's padding.  That
+is the adjoint of the forward for 'zero' at any size and for 'periodization' at even sizes; for 'symmetric', 'reflect',
+'periodic' and odd-sized 'periodization' it is NOT the adjoint (the folded samples' contributions are dropped).
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -34,14 +48,71 @@ def int_to_mode(mode):
     raise ValueError("Unkown pad type: {}".format(mode))
 
 
-def _check_haar(wave):
+class _Bank:
+    def __init__(self, dec_lo, dec_hi, rec_lo, rec_hi, name):
+        self.dec_lo, self.dec_hi, self.rec_lo, self.rec_hi, self.name = dec_lo, dec_hi, rec_lo, rec_hi, name
+        self.dec_len = self.rec_len = len(dec_lo)
+
+    def __repr__(self):
+        return "<filter bank %s, %d taps>" % (self.name, self.dec_len)
+
+
+_daubechies = {}
+
+
+def daubechies(N):
+    """The orthogonal Daubechies bank with N vanishing moments (2N taps), N = 1..8, as an object with ``dec_lo, dec_hi, rec_lo,
+    rec_hi`` lists in PyWavelets' convention: ``rec_lo`` minimum phase, ``dec_lo = rec_lo[::-1]``,
+    ``dec_hi[k] = (-1)**(k+1) * dec_lo[L-1-k]``, ``rec_hi = dec_hi[::-1]``.  Computed once, in float64, by spectral factorisation:
+    |H(w)|^2 = 2 cos^2N(w/2) P(sin^2(w/2)), P(y) = sum_{k<N} C(N-1+k, k) y^k; with y = (2 - z - 1/z) / 4 every root of P gives a
+    pair z, 1/z, of which the one inside the unit circle is kept, next to N zeros at z = -1; the taps are scaled to sum sqrt(2)."""
+    N = int(N)
+    if not 1 <= N <= 8:
+        raise ValueError("daubechies(N) is built for N = 1..8, got %d" % N)
+    if N not in _daubechies:
+        roots = [-1.0] * N
+        if N > 1:
+            p = [float(math.comb(N - 1 + k, k)) for k in range(N)]
+            for y in np.roots(p[::-1]):
+                b = 2.0 - 4.0 * y                                   # z + 1/z = b
+                d = np.sqrt(complex(b * b - 4.0))
+                z = (b + d) / 2.0
+                roots.append(z if abs(z) < 1.0 else (b - d) / 2.0)
+        h = np.real(np.poly(np.array(roots, dtype=np.complex128)))
+        rec_lo = h * (math.sqrt(2.0) / h.sum())
+        dec_lo = rec_lo[::-1]
+        L = 2 * N
+        dec_hi = np.array([(-1.0) ** (k + 1) * dec_lo[L - 1 - k] for k in range(L)])
+        _daubechies[N] = tuple(tuple(float(v) for v in a) for a in (dec_lo, dec_hi, rec_lo, dec_hi[::-1]))
+    d = _daubechies[N]
+    return _Bank(list(d[0]), list(d[1]), list(d[2]), list(d[3]), "db%d" % N)
+
+
+def _resolve(wave, analysis):
+    """``wave`` -> (is_haar, (lo_col, hi_col, lo_row, hi_row)) as float64 arrays in the order given (transform2d.py:22-33,91-102)."""
     if isinstance(wave, str):
         if wave not in ("haar", "db1"):
-            raise NotImplementedError("only the Haar wavelet is built (the OCTA path uses wave='haar', model.py:140,190); got %r" % (wave,))
-        return
-    taps = [list(map(float, torch.as_tensor(w).flatten().tolist())) for w in wave]
-    if any(len(t) != 2 or abs(abs(t[0]) - _S) > 1e-6 or abs(abs(t[1]) - _S) > 1e-6 for t in taps):
-        raise NotImplementedError("only 2-tap Haar filter banks are built")
+            raise NotImplementedError("wavelet names are resolved for 'haar' / 'db1' only (the reference looks them up in PyWavelets, "
+                                      "whose tables are not part of this package); got %r.  Pass the taps instead: a (lo, hi) or "
+                                      "(lo_col, hi_col, lo_row, hi_row) tuple, an object with dec_lo/dec_hi/rec_lo/rec_hi such as a "
+                                      "pywt.Wavelet, or faoctasr.daubechies(N)" % (wave,))
+        return True, None
+    if all(hasattr(wave, a) for a in ("dec_lo", "dec_hi", "rec_lo", "rec_hi")):
+        wave = (wave.dec_lo, wave.dec_hi) if analysis else (wave.rec_lo, wave.rec_hi)
+    if len(wave) not in (2, 4):
+        raise ValueError("wave must be a name, a wavelet object, or a tuple of 2 or 4 tap sequences; got %d sequences" % len(wave))
+    taps = [np.asarray(torch.as_tensor(w).detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float64).ravel() for w in wave]
+    if len(taps) == 2:
+        taps = taps + taps
+    if all(len(t) == 2 and abs(abs(t[0]) - _S) <= 1e-6 and abs(abs(t[1]) - _S) <= 1e-6 for t in taps):
+        return True, None
+    for lo, hi in (taps[:2], taps[2:]):
+        if len(lo) != len(hi):
+            raise ValueError("lowpass and highpass filters must have the same length, got %d and %d" % (len(lo), len(hi)))
+        if len(lo) % 2 or not 2 <= len(lo) <= ops.DWT_MAX_TAPS:
+            raise ValueError("filter length %d: the filter banks take an even number of taps, 2 to %d (pad an odd-length filter with a "
+                             "zero tap, as PyWavelets does for biorthogonal pairs)" % (len(lo), ops.DWT_MAX_TAPS))
+    return False, taps
 
 
 def _check_geometry(x, mode):
@@ -51,48 +122,106 @@ def _check_geometry(x, mode):
         raise NotImplementedError("odd sizes need boundary padding; the OCTA path only transforms even sizes")
 
 
+def _is_haar(*filters):
+    """Four 2-tap filters holding the Haar values (read through ``ops.host_taps``: once per tensor, then cached)."""
+    if not all(f.numel() == 2 for f in filters):
+        return False
+    return all(abs(abs(v) - _S) <= 1e-6 for f in filters for v in ops.host_taps(f))
+
+
 class AFB2D(Function):
     """lowlevel.py:312-365: one analysis level; ``apply(x, h0_row, h1_row, h0_col, h1_col, mode_int) -> (low, highs)``.
-    The filter tensors are accepted for signature compatibility (they are the Haar taps)."""
+    As in the reference the first filter pair runs along W and the second along H (``DWTForward`` hands its ``*_col`` buffers to
+    the first pair).  Four 2-tap filters holding the Haar values select the Haar block kernel; anything else runs the general bank
+    on the tensors' values (read once per tensor and cached, ``ops.host_taps``).  The backward is the reference's (see the module
+    docstring)."""
 
     @staticmethod
     def forward(ctx, x, h0_row, h1_row, h0_col, h1_col, mode):
+        ctx.general = not _is_haar(h0_row, h1_row, h0_col, h1_col)
+        if ctx.general:
+            return ops._AFB2D.forward(ctx, x, ops.dwt_bank(h0_row, h1_row, h0_col, h1_col), mode)
         _check_geometry(x, mode)
         ll, hi = ops._HaarAFB2D.forward(ctx, x)
         return ll, hi
 
     @staticmethod
     def backward(ctx, low, highs):
+        if ctx.general:
+            return ops._AFB2D.backward(ctx, low, highs)[0], None, None, None, None, None
         return ops._HaarAFB2D.backward(ctx, low, highs), None, None, None, None, None
 
 
 class SFB2D(Function):
-    """lowlevel.py:647-694: one synthesis level; ``apply(low, highs, g0_row, g1_row, g0_col, g1_col, mode_int) -> y``."""
+    """lowlevel.py:647-694: one synthesis level; ``apply(low, highs, g0_row, g1_row, g0_col, g1_col, mode_int) -> y``.
+    The first filter pair runs along W, the second along H; four 2-tap Haar filters select the Haar block kernel."""
 
     @staticmethod
     def forward(ctx, low, highs, g0_row, g1_row, g0_col, g1_col, mode):
+        ctx.general = not _is_haar(g0_row, g1_row, g0_col, g1_col)
+        if ctx.general:
+            return ops._SFB2D.forward(ctx, low, highs, ops.dwt_bank(g0_row, g1_row, g0_col, g1_col), mode)
         if mode not in _NATIVE_MODES:
             raise NotImplementedError("padding mode %r is outside the built Haar path" % int_to_mode(mode))
         return ops._HaarSFB2D.forward(ctx, low, highs)
 
     @staticmethod
     def backward(ctx, dy):
-        dl, dh = ops._HaarSFB2D.backward(ctx, dy)
+        if ctx.general:
+            dl, dh = ops._SFB2D.backward(ctx, dy)[:2]
+        else:
+            dl, dh = ops._HaarSFB2D.backward(ctx, dy)
         return dl, dh, None, None, None, None, None
 
 
-class DWTForward(nn.Module):
-    """transform2d.py:7-74.  forward(x) -> (yl, [yh_0 .. yh_{J-1}]), yh_j of shape (N, C, 3, H/2^{j+1}, W/2^{j+1})
-    with band order LH, HL, HH; buffers h0_col, h1_col, h0_row, h1_row as registered by the reference."""
+def _register(module, names, taps, reverse):
+    for name, t, col in zip(names, taps, (True, True, False, False)):
+        t = torch.tensor(np.ascontiguousarray(t[::-1] if reverse else t), dtype=torch.get_default_dtype())
+        module.register_buffer(name, t.reshape(1, 1, -1, 1) if col else t.reshape(1, 1, 1, -1))
+    _record(module, names)
+
+
+def _record(module, names):
+    module._taps = {n: tuple(getattr(module, n).reshape(-1).tolist()) for n in names}
+    module._tap_versions = {n: getattr(module, n)._version for n in names}
+
+
+def _prime(module, names):
+    """The buffers of a module take the taps it registered as their host record (``ops.prime_taps``), so that no call reads a
+    device buffer back -- unless the buffer was written since (``load_state_dict``), which its version counter shows."""
+    for n in names:
+        buf = getattr(module, n)
+        if buf._version == module._tap_versions.get(n) or buf._version == 0:      # 0: a fresh copy made by .to() / .cuda()
+            ops.prime_taps(buf, module._taps[n])
+
+
+class _TapModule(nn.Module):
+    _tap_names = ()
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        super()._load_from_state_dict(*args, **kwargs)
+        _record(self, self._tap_names)              # loaded taps replace the registered ones as the host record
+
+
+class DWTForward(_TapModule):
+    """transform2d.py:7-74.  forward(x) -> (yl, [yh_0 .. yh_{J-1}]), yh_j of shape (N, C, 3, H_j, W_j) with band order LH, HL, HH and
+    H_j = (H_{j-1} + L - 1) // 2 (``(H_{j-1} + 1) // 2`` for periodization); buffers h0_col, h1_col, h0_row, h1_row as registered by
+    the reference (the decomposition taps reversed, shapes (1,1,L,1) and (1,1,1,L)).  ``wave``: see the module docstring."""
+
+    _tap_names = ("h0_col", "h1_col", "h0_row", "h1_row")
 
     def __init__(self, J=1, wave="db1", mode="zero"):
         super().__init__()
-        _check_haar(wave)
-        # prep_filt_afb2d reverses the decomposition taps (lowlevel.py:925-953): dec_lo [s,s], dec_hi [-s,s] -> [s,-s]
-        self.register_buffer("h0_col", torch.tensor([_S, _S]).reshape(1, 1, 2, 1))
-        self.register_buffer("h1_col", torch.tensor([_S, -_S]).reshape(1, 1, 2, 1))
-        self.register_buffer("h0_row", torch.tensor([_S, _S]).reshape(1, 1, 1, 2))
-        self.register_buffer("h1_row", torch.tensor([_S, -_S]).reshape(1, 1, 1, 2))
+        self._haar, taps = _resolve(wave, analysis=True)
+        if self._haar:
+            # prep_filt_afb2d reverses the decomposition taps (lowlevel.py:925-953): dec_lo [s,s], dec_hi [-s,s] -> [s,-s]
+            self.register_buffer("h0_col", torch.tensor([_S, _S]).reshape(1, 1, 2, 1))
+            self.register_buffer("h1_col", torch.tensor([_S, -_S]).reshape(1, 1, 2, 1))
+            self.register_buffer("h0_row", torch.tensor([_S, _S]).reshape(1, 1, 1, 2))
+            self.register_buffer("h1_row", torch.tensor([_S, -_S]).reshape(1, 1, 1, 2))
+            _record(self, ("h0_col", "h1_col", "h0_row", "h1_row"))
+        else:
+            _register(self, ("h0_col", "h1_col", "h0_row", "h1_row"), taps, reverse=True)
         self.J = J
         self.mode = mode
 
@@ -100,34 +229,50 @@ class DWTForward(nn.Module):
         yh = []
         ll = x
         mode = mode_to_int(self.mode)
+        _prime(self, ("h0_col", "h1_col", "h0_row", "h1_row"))
         for _ in range(self.J):
             ll, high = AFB2D.apply(ll, self.h0_col, self.h1_col, self.h0_row, self.h1_row, mode)
             yh.append(high)
         return ll, yh
 
 
-class DWTInverse(nn.Module):
-    """transform2d.py:77-148.  forward((yl, yh)) -> x; a ``None`` entry in yh stands for zero bands."""
+class DWTInverse(_TapModule):
+    """transform2d.py:77-148.  forward((yl, yh)) -> x; a ``None`` entry in yh stands for zero bands.  A level returns
+    ``2 n - L + 2`` samples per side (``2 n`` for periodization), so an odd-sized input comes back one sample longer; a surplus
+    row or column of the running lowpass is dropped between levels, as in the reference.  Buffers g0_col, g1_col, g0_row, g1_row
+    hold the synthesis taps as given."""
+
+    _tap_names = ("g0_col", "g1_col", "g0_row", "g1_row")
 
     def __init__(self, wave="db1", mode="zero"):
         super().__init__()
-        _check_haar(wave)
-        self.register_buffer("g0_col", torch.tensor([_S, _S]).reshape(1, 1, 2, 1))
-        self.register_buffer("g1_col", torch.tensor([_S, -_S]).reshape(1, 1, 2, 1))
-        self.register_buffer("g0_row", torch.tensor([_S, _S]).reshape(1, 1, 1, 2))
-        self.register_buffer("g1_row", torch.tensor([_S, -_S]).reshape(1, 1, 1, 2))
+        self._haar, taps = _resolve(wave, analysis=False)
+        if self._haar:
+            self.register_buffer("g0_col", torch.tensor([_S, _S]).reshape(1, 1, 2, 1))
+            self.register_buffer("g1_col", torch.tensor([_S, -_S]).reshape(1, 1, 2, 1))
+            self.register_buffer("g0_row", torch.tensor([_S, _S]).reshape(1, 1, 1, 2))
+            self.register_buffer("g1_row", torch.tensor([_S, -_S]).reshape(1, 1, 1, 2))
+            _record(self, ("g0_col", "g1_col", "g0_row", "g1_row"))
+        else:
+            _register(self, ("g0_col", "g1_col", "g0_row", "g1_row"), taps, reverse=False)
         self.mode = mode
 
     def forward(self, coeffs):
         yl, yh = coeffs
         ll = yl
         mode = mode_to_int(self.mode)
+        general = not self._haar
+        _prime(self, ("g0_col", "g1_col", "g0_row", "g1_row"))
         for h in yh[::-1]:
-            if h is None:
+            if h is None and not general:
                 h = torch.zeros(ll.shape[0], ll.shape[1], 3, ll.shape[-2], ll.shape[-1], device=ll.device, dtype=ll.dtype)
-            if ll.shape[-2] > h.shape[-2]:
-                ll = ll[..., :-1, :]
-            if ll.shape[-1] > h.shape[-1]:
-                ll = ll[..., :-1]
-            ll = SFB2D.apply(ll, h, self.g0_col, self.g1_col, self.g0_row, self.g1_row, mode)
+            if h is not None:
+                if ll.shape[-2] > h.shape[-2]:
+                    ll = ll[..., :-1, :]
+                if ll.shape[-1] > h.shape[-1]:
+                    ll = ll[..., :-1]
+            if general:                             # a missing level goes to the kernel as a null pointer: no zero tensor
+                ll = ops.sfb2d(ll, h, self.g0_col, self.g1_col, self.g0_row, self.g1_row, mode)
+            else:
+                ll = SFB2D.apply(ll, h, self.g0_col, self.g1_col, self.g0_row, self.g1_row, mode)
         return ll

@@ -283,6 +283,24 @@ int faoctasr_tv_loss_fwd(const float* x, float* out, float* workspace, int B, in
 int faoctasr_tv_loss_bwd(const float* x, const float* g, float* dx, int B, int C, int H, int W, float weight,
                          faoctasr_stream_t stream);
 
+/* ---- general filter-bank 2-D DWT / IDWT, one level per call (csrc/dwt.hip) ----------------------
+ * pytorch_wavelets dwt/lowlevel.py:91-172 (afb1d), 226-271 (sfb1d), 312-365 (AFB2D), 647-694 (SFB2D).  The taps are HOST
+ * pointers, read during the call and passed to the kernel by value (nothing is allocated or copied: the launch is capturable):
+ * a lowpass / highpass pair of L_h taps filtering along H and one of L_w taps along W, each L even and 2 <= L <= 16.  Analysis
+ * taps are given as the correlation kernels the reference registers (the decomposition taps reversed), synthesis taps as
+ * given.  mode: 0 zero, 1 symmetric, 2 periodization, 4 reflect, 6 periodic (lowlevel.py:274-290).  FAOCTASR_EINVAL for an odd
+ * or out-of-range L, an unknown mode, a side below the minimum, or a crop outside the result.
+ * Analysis: x[NC,H,W] -> ll[NC,OH,OW], hi[NC,3,OH,OW] (band order LH, HL, HH), O = (N + 1) / 2 for periodization and
+ * (N + L - 1) / 2 otherwise; H >= L_h / 2 + 1 and W >= L_w / 2 + 1.  Also SFB2D.backward (with the synthesis taps). */
+int faoctasr_dwt2d_analysis(const float* x, float* ll, float* hi, long NC, int H, int W, const float* lo_h, const float* hi_h,
+                            int L_h, const float* lo_w, const float* hi_w, int L_w, int mode, faoctasr_stream_t stream);
+/* Synthesis: ll[NC,nh,nw], hi[NC,3,nh,nw] (either may be NULL = zeros) -> y[NC,out_h,out_w], the top-left crop of the
+ * (2 n - L + 2)-sided (periodization: 2 n) result; n >= L / 2 (periodization: 2 n >= L / 2).  Also AFB2D.backward (with the
+ * analysis taps and the crop to the input's size). */
+int faoctasr_dwt2d_synthesis(const float* ll, const float* hi, float* y, long NC, int nh, int nw, int out_h, int out_w,
+                             const float* lo_h, const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w,
+                             int mode, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
