@@ -15,6 +15,6 @@ from .ssim import ssim as ssim_fn  # the function ssim.py:65-73; not exported un
 from .data import GpuTransformA, GpuTransformB, crop_resize_normalize, random_crop_offsets
 from .train import GraphedTrainStep, ParamArena, TrainStep, live_parameters
 from .utils import (DeviceReplayBuffer, LambdaLR, ReplayBuffer, frequency_split, high_pass, low_pass, psnr, set_requires_grad, weights_init_normal)
-from .wavelets import AFB2D, SFB2D, DWTForward, DWTInverse, daubechies
+from .wavelets import AFB2D, SFB2D, DWTForward, DWTInverse, SWTForward, SWTInverse, daubechies
 
 __all__ = [n for n in dir() if not n.startswith("_")]

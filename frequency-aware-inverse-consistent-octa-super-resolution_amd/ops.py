@@ -1012,6 +1012,133 @@ def sfb2d(ll, hi, lo_w, hi_w, lo_h, hi_h, mode):
     return _SFB2D.apply(ll, hi, dwt_bank(lo_w, hi_w, lo_h, hi_h), int(mode))
 
 
+# ----------------------------------------------------------------------------------------
+# stationary (a-trous) wavelet transform (csrc/swt.hip): any even tap count up to 16, four extensions, dilations 1..8
+# ----------------------------------------------------------------------------------------
+SWT_MODES = (0, 1, 4, 6)                # zero, symmetric, reflect, periodic (wavelets.swt_mode_to_int)
+SWT_MAX_LEVELS = 4                      # dilation 2^(J-1) <= 8
+
+
+def swt_bank(lo_h, hi_h, lo_w, hi_w):
+    """Validate a stationary transform's bank -- the H-axis pair first, every filter in WAVELET order (dec_* / rec_* as given,
+    not the reversed buffers) -- and return it as host tuples."""
+    return dwt_bank(lo_h, hi_h, lo_w, hi_w)
+
+
+def _swt_geometry(H, W, bank, J, mode):
+    Lh, Lw = len(bank[0]), len(bank[2])
+    if mode not in SWT_MODES:
+        raise NotImplementedError("extension %d is not built for the stationary transform (zero, symmetric, reflect, periodic are)" % mode)
+    if not 1 <= J <= SWT_MAX_LEVELS:
+        raise ValueError("the stationary transform runs J = 1..%d levels (dilation up to %d), got %d" % (SWT_MAX_LEVELS, 1 << (SWT_MAX_LEVELS - 1), J))
+    d = 1 << (J - 1)
+    if H < Lh * d // 2 + 1 or W < Lw * d // 2 + 1:
+        raise ValueError("a %d x %d image is below the minimum side L 2^(J-1) / 2 + 1 of a %d (H) x %d (W) tap bank at J = %d: %d x %d"
+                         % (H, W, Lh, Lw, J, Lh * d // 2 + 1, Lw * d // 2 + 1))
+
+
+def _plane_strided(t):
+    """(tensor, plane stride) for an (N, C, H, W) operand whose planes are dense and evenly spaced -- band 0 of a level's
+    (N, C, 4, H, W) output -- else a contiguous copy."""
+    N, C, H, W = t.shape
+    s = t.stride()
+    if t.is_cuda and t.dtype == torch.float32 and s[3] == 1 and s[2] == W and s[1] >= H * W and (N == 1 or s[0] == C * s[1]):
+        return t, s[1]
+    return _c(t), H * W
+
+
+def _swt_level(x, bank, d, mode, scale):
+    """One analysis launch: planes of x (possibly band 0 of a previous level, read in place) -> (N, C, 4, H, W)."""
+    N, C, H, W = x.shape
+    x, ps = _plane_strided(x)
+    y = torch.empty((N, C, 4, H, W), dtype=torch.float32, device=x.device)
+    call("swt2d_analysis", ptr(x) if x.is_contiguous() else x.data_ptr(), ps, ptr(y), N * C, H, W, _tap_array(bank[0]), _tap_array(bank[1]), len(bank[0]),
+         _tap_array(bank[2]), _tap_array(bank[3]), len(bank[2]), d, mode, scale, stream_ptr())
+    return y
+
+
+def _swt_level_adjoint(c, bank, d, mode, scale, band0=None, replace=False):
+    """One adjoint launch: (N, C, 4, H, W) -> (N, C, H, W).  ``band0``, an (N, C, H, W) tensor, is added to band 0 of ``c`` as the
+    kernel reads it, or read in its place (``replace``): the levels chain without a copy of ``c``."""
+    N, C, _, H, W = c.shape
+    c = _c(c)
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=c.device)
+    call("swt2d_adjoint", ptr(c), ptr(out), H * W, ptr(_c(band0)) if band0 is not None else None, H * W, int(replace), N * C, H, W,
+         _tap_array(bank[0]), _tap_array(bank[1]), len(bank[0]), _tap_array(bank[2]), _tap_array(bank[3]), len(bank[2]), d, mode, scale,
+         stream_ptr())
+    return out
+
+
+class _SWTAnalysis(Function):
+    """J levels of the stationary transform: ``apply(x, bank, mode, J) -> J tensors (N, C, 4, H, W)``, level j at dilation 2^j on
+    band 0 of level j - 1 (read in place).  ``bank`` = (lo_h, hi_h, lo_w, hi_w) host tuples in wavelet order.  The backward is
+    the exact adjoint in every mode, coarse to fine: the gradient of a level joins band 0 of the next finer level's cotangent
+    inside that level's launch (autograd hands a zero tensor for a level nothing depends on)."""
+
+    @staticmethod
+    def forward(ctx, x, bank, mode, J):
+        _swt_geometry(x.shape[-2], x.shape[-1], bank, J, mode)
+        ctx.cfg = (bank, mode, J)
+        out, ll = [], x
+        for j in range(J):
+            y = _swt_level(ll, bank, 1 << j, mode, 1.0)
+            out.append(y)
+            ll = y[:, :, 0]
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        bank, mode, J = ctx.cfg
+        g = None
+        for j in reversed(range(J)):
+            g = _swt_level_adjoint(dys[j], bank, 1 << j, mode, 1.0, band0=g)
+        return g, None, None, None
+
+
+class _SWTSynthesis(Function):
+    """The periodic inverse: ``apply(bank, *coeffs) -> x`` for the list ``SWTForward`` returns, ``bank`` = (g0_h, g1_h, g0_w, g1_w)
+    rec taps in wavelet order.  Coarse to fine; the coarsest level's band 0 and bands 1..3 of every level are used, the finer
+    levels' band 0 is ignored: the kernel reads the coarser level's result in its place.  A level is the adjoint kernel on the
+    reversed taps with scale 1/4 (1/2 per axis), its backward the analysis kernel on the same taps and scale."""
+
+    @staticmethod
+    def forward(ctx, bank, *coeffs):
+        J = len(coeffs)
+        N, C, four, H, W = coeffs[-1].shape
+        if four != 4 or any(tuple(c.shape) != (N, C, 4, H, W) for c in coeffs):
+            raise ValueError("the coefficients of a stationary transform are (N, C, 4, H, W) tensors of one shape, got %s" % [tuple(c.shape) for c in coeffs])
+        _swt_geometry(H, W, bank, J, 6)
+        rev = tuple(t[::-1] for t in bank)
+        ctx.cfg = (rev, J)
+        ll = None
+        for j in reversed(range(J)):
+            ll = _swt_level_adjoint(coeffs[j], rev, 1 << j, 6, 0.25, band0=ll, replace=True)
+        return ll
+
+    @staticmethod
+    def backward(ctx, dy):
+        rev, J = ctx.cfg
+        grads, g = [], dy
+        for j in range(J):
+            G = _swt_level(g, rev, 1 << j, 6, 0.25)
+            grads.append(G)
+            g = G[:, :, 0]
+        for G in grads[:-1]:                    # the finer levels' band 0 does not reach the result (read above, then cleared)
+            G[:, :, 0].zero_()
+        return (None,) + tuple(grads)
+
+
+def swt_analysis(x, lo_h, hi_h, lo_w, hi_w, mode, J=1):
+    """The J levels of the stationary transform of x, a tuple of (N, C, 4, H, W) tensors; the filters are tensors or sequences
+    in wavelet order (dec_lo, dec_hi), the H-axis pair first; ``mode`` one of ``SWT_MODES``."""
+    return _SWTAnalysis.apply(x, swt_bank(lo_h, hi_h, lo_w, hi_w), int(mode), int(J))
+
+
+def swt_synthesis(coeffs, lo_h, hi_h, lo_w, hi_w):
+    """The periodic inverse of ``swt_analysis``'s list; the filters are the rec taps in wavelet order, the H-axis pair first."""
+    return _SWTSynthesis.apply(swt_bank(lo_h, hi_h, lo_w, hi_w), *coeffs)
+
+
 class _HaarDFront(Function):
     @staticmethod
     def forward(ctx, x, mode):

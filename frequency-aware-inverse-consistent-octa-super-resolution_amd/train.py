@@ -20,7 +20,7 @@ from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
-from .wavelets import DWTForward
+from .wavelets import DWTForward, SWTForward
 
 # parameters that exist in the reference's state_dict but never receive a gradient
 # (model.py:241,254-257: unet/unet_up of NetworkA2B; model.py:281-284: skip of NetworkB2A);
@@ -261,7 +261,8 @@ class TrainStep:
     def __init__(self, netG_A2B=None, netG_B2A=None, netD_A=None, netD_B=None, device="cuda", lr=1.3e-4, betas=(0.9, 0.999),
                  beta1=0.25, beta2=10.0, beta3=2.0, beta4=0.5, beta5=0.5, ssim_weight=0.0, whf_weight=0.0, dwt_levels=1,
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
-                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect"):
+                 reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
+                 dwt_stationary=False):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -274,7 +275,11 @@ class TrainStep:
 
         ``dwt_wave`` / ``dwt_mode``: the filter bank and padding of the opt-in wavelet-HF term (``whf_weight``), handed to
         ``DWTForward`` -- 'haar', a tap tuple, a wavelet object or ``daubechies(N)`` (wavelets.py).  The defaults are the Haar bank
-        the term has always used."""
+        the term has always used.
+
+        ``dwt_stationary`` (default off): the wavelet-HF term runs on ``SWTForward(J=dwt_levels, wave=dwt_wave, mode=dwt_mode)``
+        instead -- the undecimated transform, whose bands 1..3 of every level enter the L1.  The decimated transform penalises a
+        one-pixel misregistration differently depending on its parity; the stationary one has no such phase."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -297,7 +302,9 @@ class TrainStep:
         self.phase_weight, self.phase_radius = phase_weight, phase_radius
         #: opt-in smoothness term on the generators' outputs: tv_weight * (TVLoss(fake_B) + TVLoss(fake_A)) (model.py:17-33; 0 = off)
         self.tv_weight = tv_weight
-        self.dwt_loss = DWTForward(J=dwt_levels, wave=dwt_wave, mode=dwt_mode).to(dev) if whf_weight else None
+        self.dwt_stationary = bool(dwt_stationary)
+        self.dwt_loss = ((SWTForward if self.dwt_stationary else DWTForward)(J=dwt_levels, wave=dwt_wave, mode=dwt_mode).to(dev)
+                         if whf_weight else None)
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -579,6 +586,13 @@ class TrainStep:
                                {k: (extra_A[k].detach(), v) for k, v in extra_B.items()})
         return o, L, root
 
+    def _whf_bands(self, img):
+        """The high-frequency bands the wavelet-HF term compares, one tensor per level: ``DWTForward``'s yh, or bands 1..3 of every
+        level of the stationary transform."""
+        if self.dwt_stationary:
+            return [y[:, :, 1:] for y in self.dwt_loss(img)]
+        return self.dwt_loss(img)[1]
+
     def _extension_terms(self, rec, real):
         """One image pair's share of the opt-in terms of ``generator_loss`` (SSIM: train.py:234; wavelet-HF L1; spectral phase)."""
         t = {}
@@ -586,8 +600,7 @@ class TrainStep:
             t["loss_ssim"] = self.ssim_weight * (1 - ops.ssim(rec, real))
         if self.whf_weight:
             acc = 0
-            _, yh_r = self.dwt_loss(rec)
-            _, yh_t = self.dwt_loss(real)
+            yh_r, yh_t = self._whf_bands(rec), self._whf_bands(real)
             for a, b in zip(yh_r, yh_t):
                 acc = acc + ops.l1_loss(a, b, self.whf_weight)
             t["loss_whf"] = acc
@@ -621,8 +634,7 @@ class TrainStep:
         if self.whf_weight:
             t = 0
             for rec, real in ((o["recovered_A"], real_A), (o["recovered_B"], real_B)):
-                _, yh_r = self.dwt_loss(rec)
-                _, yh_t = self.dwt_loss(real)
+                yh_r, yh_t = self._whf_bands(rec), self._whf_bands(real)
                 for a, b in zip(yh_r, yh_t):
                     t = t + ops.l1_loss(a, b, self.whf_weight)
             L["loss_whf"] = t

@@ -88,31 +88,44 @@ def daubechies(N):
     return _Bank(list(d[0]), list(d[1]), list(d[2]), list(d[3]), "db%d" % N)
 
 
-def _resolve(wave, analysis):
-    """``wave`` -> (is_haar, (lo_col, hi_col, lo_row, hi_row)) as float64 arrays in the order given (transform2d.py:22-33,91-102)."""
-    if isinstance(wave, str):
-        if wave not in ("haar", "db1"):
-            raise NotImplementedError("wavelet names are resolved for 'haar' / 'db1' only (the reference looks them up in PyWavelets, "
-                                      "whose tables are not part of this package); got %r.  Pass the taps instead: a (lo, hi) or "
-                                      "(lo_col, hi_col, lo_row, hi_row) tuple, an object with dec_lo/dec_hi/rec_lo/rec_hi such as a "
-                                      "pywt.Wavelet, or faoctasr.daubechies(N)" % (wave,))
-        return True, None
+def _tap_arrays(wave, analysis):
+    """A wavelet object or a tuple of 2 or 4 tap sequences -> [lo_col, hi_col, lo_row, hi_row] as float64 arrays in the order given."""
     if all(hasattr(wave, a) for a in ("dec_lo", "dec_hi", "rec_lo", "rec_hi")):
         wave = (wave.dec_lo, wave.dec_hi) if analysis else (wave.rec_lo, wave.rec_hi)
     if len(wave) not in (2, 4):
         raise ValueError("wave must be a name, a wavelet object, or a tuple of 2 or 4 tap sequences; got %d sequences" % len(wave))
     taps = [np.asarray(torch.as_tensor(w).detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float64).ravel() for w in wave]
-    if len(taps) == 2:
-        taps = taps + taps
-    if all(len(t) == 2 and abs(abs(t[0]) - _S) <= 1e-6 and abs(abs(t[1]) - _S) <= 1e-6 for t in taps):
-        return True, None
+    return taps + taps if len(taps) == 2 else taps
+
+
+def _named(wave):
+    if wave not in ("haar", "db1"):
+        raise NotImplementedError("wavelet names are resolved for 'haar' / 'db1' only (the reference looks them up in PyWavelets, "
+                                  "whose tables are not part of this package); got %r.  Pass the taps instead: a (lo, hi) or "
+                                  "(lo_col, hi_col, lo_row, hi_row) tuple, an object with dec_lo/dec_hi/rec_lo/rec_hi such as a "
+                                  "pywt.Wavelet, or faoctasr.daubechies(N)" % (wave,))
+    return daubechies(1)
+
+
+def _check_taps(taps):
     for lo, hi in (taps[:2], taps[2:]):
         if len(lo) != len(hi):
             raise ValueError("lowpass and highpass filters must have the same length, got %d and %d" % (len(lo), len(hi)))
         if len(lo) % 2 or not 2 <= len(lo) <= ops.DWT_MAX_TAPS:
             raise ValueError("filter length %d: the filter banks take an even number of taps, 2 to %d (pad an odd-length filter with a "
                              "zero tap, as PyWavelets does for biorthogonal pairs)" % (len(lo), ops.DWT_MAX_TAPS))
-    return False, taps
+    return taps
+
+
+def _resolve(wave, analysis):
+    """``wave`` -> (is_haar, (lo_col, hi_col, lo_row, hi_row)) as float64 arrays in the order given (transform2d.py:22-33,91-102)."""
+    if isinstance(wave, str):
+        _named(wave)
+        return True, None
+    taps = _tap_arrays(wave, analysis)
+    if all(len(t) == 2 and abs(abs(t[0]) - _S) <= 1e-6 and abs(abs(t[1]) - _S) <= 1e-6 for t in taps):
+        return True, None
+    return False, _check_taps(taps)
 
 
 def _check_geometry(x, mode):
@@ -276,3 +289,70 @@ class DWTInverse(_TapModule):
             else:
                 ll = SFB2D.apply(ll, h, self.g0_col, self.g1_col, self.g0_row, self.g1_row, mode)
         return ll
+
+
+# ----------------------------------------------------------------------------------------
+# the stationary (undecimated, a-trous) transform: transform2d.py:151-212, lowlevel.py:175-223, 475-521 -> csrc/swt.hip
+# ----------------------------------------------------------------------------------------
+_SWT_MODES = {"zero": 0, "symmetric": 1, "reflect": 4, "periodic": 6, "periodization": 6, "per": 6}
+
+
+def swt_mode_to_int(mode):
+    """The extensions of the stationary transform.  'periodization' / 'per' stand for 'periodic': it is ``SWTForward``'s default
+    in the reference, whose own pad refuses it, and PyWavelets' ``swt2`` is periodic."""
+    if mode not in _SWT_MODES:
+        raise ValueError("Unkown pad type: {}".format(mode))
+    return _SWT_MODES[mode]
+
+
+def _swt_taps(wave, analysis):
+    """``wave`` -> (lo_col, hi_col, lo_row, hi_row) float64 arrays in wavelet order; Haar is an ordinary 2-tap bank here."""
+    return _check_taps(_tap_arrays(_named(wave) if isinstance(wave, str) else wave, analysis))
+
+
+class SWTForward(_TapModule):
+    """transform2d.py:151-212 as documented there: forward(x) -> a list of J contiguous (N, C, 4, H, W) tensors, bands (ll, lh, hl, hh)
+    = (W lo, H lo), (W lo, H hi), (W hi, H lo), (W hi, H hi), level j computed at dilation 2^j from band 0 of level j - 1.  Buffers
+    h0_col, h1_col, h0_row, h1_row in the ``prep_filt_afb2d`` form (the decomposition taps reversed, shapes (1,1,L,1) and
+    (1,1,1,L)); as ``afb2d_atrous`` uses them the *_col pair filters along H and the *_row pair along W, so a 4-tuple ``wave`` is
+    (col lo, col hi, row lo, row hi).  Modes 'zero', 'symmetric', 'reflect', 'periodic' (= 'periodization', 'per'); J <= 4; every
+    side at least L 2^(J-1) / 2 + 1, else ``ValueError``.  The backward is the exact adjoint in every mode (the reference
+    differentiates through its pad)."""
+
+    _tap_names = ("h0_col", "h1_col", "h0_row", "h1_row")
+
+    def __init__(self, J=1, wave="db1", mode="periodization"):
+        super().__init__()
+        swt_mode_to_int(mode)
+        if not 1 <= int(J) <= ops.SWT_MAX_LEVELS:
+            raise ValueError("SWTForward runs J = 1..%d levels, got %r" % (ops.SWT_MAX_LEVELS, J))
+        _register(self, self._tap_names, _swt_taps(wave, analysis=True), reverse=True)
+        self.J = int(J)
+        self.mode = mode
+
+    def forward(self, x):
+        _prime(self, self._tap_names)
+        h = [ops.host_taps(getattr(self, n))[::-1] for n in self._tap_names]           # back to wavelet order
+        return list(ops.swt_analysis(x, h[0], h[1], h[2], h[3], swt_mode_to_int(self.mode), self.J))
+
+
+class SWTInverse(_TapModule):
+    """The periodic inverse of ``SWTForward`` (PyWavelets' ``iswt2``; the reference's ``SWTInverse`` calls the decimated bank and
+    does not run): forward(coeffs) -> x for the list of (N, C, 4, H, W) tensors, coarse to fine, per level and axis
+    y[m] = 1/2 sum_k g0[k] lo[(m - k d + (L/2 - 1) d) mod N] + g1[k] hi[same], d = 2^level, H first, then W.  The coarsest level's
+    band 0 and bands 1..3 of every level are used; the finer levels' band 0 is ignored.  Buffers g0_col, g1_col, g0_row, g1_row
+    hold the synthesis taps as given (``DWTInverse``'s form).  Any mode but the periodic ones raises ``ValueError``."""
+
+    _tap_names = ("g0_col", "g1_col", "g0_row", "g1_row")
+
+    def __init__(self, wave="db1", mode="periodization"):
+        super().__init__()
+        if swt_mode_to_int(mode) != 6:
+            raise ValueError("SWTInverse is built for the periodic extension only ('periodic', 'periodization', 'per'), got %r" % (mode,))
+        _register(self, self._tap_names, _swt_taps(wave, analysis=False), reverse=False)
+        self.mode = mode
+
+    def forward(self, coeffs):
+        _prime(self, self._tap_names)
+        g = [ops.host_taps(getattr(self, n)) for n in self._tap_names]
+        return ops.swt_synthesis(list(coeffs), g[0], g[1], g[2], g[3])

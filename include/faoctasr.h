@@ -301,6 +301,30 @@ int faoctasr_dwt2d_synthesis(const float* ll, const float* hi, float* y, long NC
                              const float* lo_h, const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w,
                              int mode, faoctasr_stream_t stream);
 
+/* ---- stationary (undecimated, a-trous) 2-D wavelet transform, one level per call (csrc/swt.hip) --
+ * pytorch_wavelets dwt/lowlevel.py:175-223 (afb1d_atrous), 475-521 (afb2d_atrous); transform2d.py:151-212 (SWTForward).  The taps
+ * are HOST pointers, read during the call and passed to the kernel by value (the launch is capturable), in WAVELET order
+ * (dec_lo / dec_hi, not the reversed buffers the modules register): a pair of L_h taps filtering along H and one of L_w taps
+ * along W, each L even and 2 <= L <= 16.  dilation = 2^level: 1, 2, 4 or 8.  mode: 0 zero, 1 symmetric, 4 reflect, 6 periodic.
+ * H >= L_h dilation / 2 + 1 and W >= L_w dilation / 2 + 1 (the extension then folds at most once a side).  FAOCTASR_EINVAL for a
+ * tap count, mode, dilation, plane stride or side outside these.
+ * Analysis: NC planes of x (H x W, x_plane_stride elements apart: level j + 1 reads band 0 of level j's output in place) ->
+ * y[NC,4,H,W], per axis out[i] = sum_k h[k] xe[i - k dilation + L dilation / 2], W first, then H, the result times `scale`;
+ * bands (W lo, H lo), (W lo, H hi), (W hi, H lo), (W hi, H hi).  Also the periodic inverse's backward (reversed rec taps, 1/4). */
+int faoctasr_swt2d_analysis(const float* x, long x_plane_stride, float* y, long NC, int H, int W, const float* lo_h,
+                            const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w, int dilation, int mode,
+                            float scale, faoctasr_stream_t stream);
+/* Adjoint: c[NC,4,H,W] -> NC planes of dx (dx_plane_stride elements apart), `scale` times the exact transpose of the analysis
+ * in every mode, as a fixed-order gather (no atomics).  With the reversed rec taps, mode 6 and scale 1/4 it is one level of the
+ * periodic inverse: y[m] = 1/2 sum_k g0[k] lo[(m - k d + (L/2 - 1) d) mod N] + g1[k] hi[same] per axis, H first.
+ * band0 (NULL: none): NC planes, band0_plane_stride elements apart, that are added to band 0 of c as it is read
+ * (band0_replaces = 0: the backward chains the coarser level's gradient into a level's cotangent) or read instead of it
+ * (band0_replaces = 1: the inverse chains the coarser level's result into a level's coefficients) -- neither copies c. */
+int faoctasr_swt2d_adjoint(const float* c, float* dx, long dx_plane_stride, const float* band0, long band0_plane_stride,
+                           int band0_replaces, long NC, int H, int W, const float* lo_h,
+                           const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w, int dilation, int mode,
+                           float scale, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
