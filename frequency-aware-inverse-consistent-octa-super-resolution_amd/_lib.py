@@ -66,6 +66,9 @@ _SIG = {
     "tv_loss_bwd": (_I, "ppp iiii f p"),
     "dwt2d_analysis": (_I, "ppp l ii ppi ppi i p"),
     "dwt2d_synthesis": (_I, "ppp l iiii ppi ppi i p"),
+    "dwt1d_fused_max": (_L, ""),
+    "dwt1d_analysis": (_I, "p lll pp l i p i pp i i i p"),
+    "dwt1d_synthesis": (_I, "p lll pp l p i i pp i i i p"),
     "swt2d_analysis": (_I, "p l p l ii ppi ppi i i f p"),
     "swt2d_adjoint": (_I, "pp l p l i l ii ppi ppi i i f p"),
     "loss_workspace_floats": (_L, ""),

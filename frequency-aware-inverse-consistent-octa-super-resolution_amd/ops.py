@@ -1013,6 +1013,215 @@ def sfb2d(ll, hi, lo_w, hi_w, lo_h, hi_h, mode):
 
 
 # ----------------------------------------------------------------------------------------
+# 1-D filter-bank DWT over rows (csrc/dwt1d.hip): all J levels of a row in one launch, rows up to DWT1D_FUSED_MAX samples in LDS
+# ----------------------------------------------------------------------------------------
+DWT1D_FUSED_MAX = 8192                  # csrc/dwt1d.hip DWT1D_FUSED_MAX (faoctasr_dwt1d_fused_max)
+DWT1D_MAX_LEVELS = 8
+
+
+def dwt1d_bank(lo, hi):
+    """Validate one 1-D filter pair and return it as host tuples."""
+    return dwt_bank(lo, hi, lo, hi)[:2]
+
+
+def dwt1d_lengths(n, L, mode, J):
+    """[n_0 .. n_J]: the input length of every analysis level and the coarsest output, n_(j+1) = dwt_out_size(n_j)."""
+    out = [int(n)]
+    for _ in range(J):
+        out.append(dwt_out_size(out[-1], L, mode))
+    return out
+
+
+def dwt1d_inverse_lengths(lo_len, hi_lens, L, mode):
+    """The inverse's length bookkeeping, coarsest level first as ``DWT1DInverse`` walks them.  ``hi_lens[j]`` is the length of
+    level j's highpass (0 = finest), None for a missing level.  -> (counts, fulls): per level j the coefficient count the level
+    runs on -- the running lowpass after a surplus last sample was dropped -- and the length of its result, ``2 c - L + 2``
+    (periodization: ``2 c``).  A lowpass that still differs from its level's highpass raises ``ValueError``."""
+    J = len(hi_lens)
+    counts, fulls = [0] * J, [0] * J
+    m = int(lo_len)
+    for j in reversed(range(J)):
+        c = hi_lens[j]
+        if c is not None:
+            if m == c + 1:
+                m = c
+            elif m != c:
+                raise ValueError("level %d: a lowpass of %d samples does not belong to a highpass of %d (one surplus sample is dropped, no more)" % (j, m, c))
+        if m < ((L + 3) // 4 if mode == 2 else L // 2):
+            raise ValueError("level %d: %d coefficients are below the minimum of a %d tap bank" % (j, m, L))
+        counts[j] = m
+        m = fulls[j] = 2 * m if mode == 2 else 2 * m - L + 2
+    return counts, fulls
+
+
+def _rows(t):
+    """(tensor, (inner, outer stride, row stride)) of an (N, C, n) operand whose samples are contiguous, else of its contiguous copy."""
+    N, C, n = t.shape
+    s = t.stride()
+    if t.is_cuda and t.dtype == torch.float32 and (s[2] == 1 or n == 1) and s[1] >= n and s[0] >= 0:
+        return t, (C, s[0], s[1])
+    t = _c(t)
+    return t, (C, C * n, n)
+
+
+def _dwt1d_check(bank, mode, J):
+    if mode not in DWT_MODES:
+        raise NotImplementedError("padding mode %d is not built (zero, symmetric, reflect, periodic, periodization are)" % mode)
+    if not 1 <= J <= DWT1D_MAX_LEVELS:
+        raise ValueError("the 1-D transform runs J = 1..%d levels, got %d" % (DWT1D_MAX_LEVELS, J))
+
+
+def _dwt1d_fused(n, fused):
+    if fused is None:
+        return n <= DWT1D_FUSED_MAX
+    if fused and n > DWT1D_FUSED_MAX:
+        raise ValueError("a row of %d samples is beyond the fused launch's limit DWT1D_FUSED_MAX = %d" % (n, DWT1D_FUSED_MAX))
+    return bool(fused)
+
+
+def _dwt1d_analysis(x, bank, mode, in_lens, fused):
+    """The analysis launch(es): x (N, C, n) -> (lo, [hi_0 .. hi_(J-1)]); ``in_lens[j]`` the length level j reads (what its source
+    holds or one zero more).  One call fused, one per level tiled (the lowpass then travels through device memory)."""
+    N, C, n = x.shape
+    J, L = len(in_lens), len(bank[0])
+    outs = [dwt_out_size(m, L, mode) for m in in_lens]
+    his = [torch.empty((N, C, o), dtype=torch.float32, device=x.device) for o in outs]
+    x, (inner, so, sr) = _rows(x)
+    h0, h1 = _tap_array(bank[0]), _tap_array(bank[1])
+    if fused:
+        lo = torch.empty((N, C, outs[-1]), dtype=torch.float32, device=x.device)
+        hp = (ctypes.c_void_p * J)(*[ptr(h) for h in his])
+        ln = (ctypes.c_int * J)(*in_lens)
+        call("dwt1d_analysis", x.data_ptr(), inner, so, sr, ptr(lo), ctypes.cast(hp, ctypes.c_void_p), N * C, n,
+             ctypes.cast(ln, ctypes.c_void_p), J, h0, h1, L, mode, 1, stream_ptr())
+        return lo, his
+    lo = x
+    for j in range(J):
+        src, (inner, so, sr) = _rows(lo)
+        lo = torch.empty((N, C, outs[j]), dtype=torch.float32, device=x.device)
+        hp = (ctypes.c_void_p * 1)(ptr(his[j]))
+        ln = (ctypes.c_int * 1)(in_lens[j])
+        call("dwt1d_analysis", src.data_ptr(), inner, so, sr, ptr(lo), ctypes.cast(hp, ctypes.c_void_p), N * C, src.shape[-1],
+             ctypes.cast(ln, ctypes.c_void_p), 1, h0, h1, L, mode, 0, stream_ptr())
+    return lo, his
+
+
+def _dwt1d_synthesis(lo, his, bank, mode, counts, crops, fused):
+    """The synthesis launch(es): lo (N, C, >= counts[-1]), his[j] (N, C, counts[j]) or None -> y (N, C, crops[0]); level j's result
+    is cropped to ``crops[j]`` (``crops[j] == counts[j - 1]`` for j > 0)."""
+    N, C = lo.shape[0], lo.shape[1]
+    J, L = len(counts), len(bank[0])
+    his = [_c(h) if h is not None else None for h in his]
+    g0, g1 = _tap_array(bank[0]), _tap_array(bank[1])
+    lo, (inner, so, sr) = _rows(lo)
+    if fused:
+        y = torch.empty((N, C, crops[0]), dtype=torch.float32, device=lo.device)
+        hp = (ctypes.c_void_p * J)(*[ptr(h) for h in his])
+        cn = (ctypes.c_int * J)(*counts)
+        call("dwt1d_synthesis", lo.data_ptr(), inner, so, sr, ctypes.cast(hp, ctypes.c_void_p), ptr(y), N * C, ctypes.cast(cn, ctypes.c_void_p), J,
+             crops[0], g0, g1, L, mode, 1, stream_ptr())
+        return y
+    for j in reversed(range(J)):
+        y = torch.empty((N, C, crops[j]), dtype=torch.float32, device=lo.device)
+        hp = (ctypes.c_void_p * 1)(ptr(his[j]))
+        cn = (ctypes.c_int * 1)(counts[j])
+        call("dwt1d_synthesis", lo.data_ptr(), inner, so, sr, ctypes.cast(hp, ctypes.c_void_p), ptr(y), N * C, ctypes.cast(cn, ctypes.c_void_p), 1,
+             crops[j], g0, g1, L, mode, 0, stream_ptr())
+        lo, (inner, so, sr) = _rows(y)
+    return y
+
+
+def _dev_rows(t, what):
+    if t.dim() != 3:
+        raise ValueError("%s: the 1-D transform takes (N, C, L) tensors, got %d dimensions" % (what, t.dim()))
+    if not (t.is_cuda and t.dtype == torch.float32):
+        raise _lib.KernelError("kernel operand must be an fp32 device tensor, got %s %s on %s" % (tuple(t.shape), t.dtype, t.device))
+
+
+class _DWT1DAnalysis(Function):
+    """J analysis levels of (N, C, n) rows: ``apply(x, bank, mode, J, fused) -> (lo, hi_0, .., hi_(J-1))``, ``bank`` = (h0, h1) host
+    tuples, correlation kernels.  The backward is the reference's own (lowlevel.py:401-424 per level): the synthesis bank on the
+    ANALYSIS taps, every level cropped to the length its forward read -- one launch where the forward was one."""
+
+    @staticmethod
+    def forward(ctx, x, bank, mode, J, fused):
+        _dwt1d_check(bank, mode, J)
+        if x.dim() != 3:
+            raise ValueError("the 1-D transform takes (N, C, L) tensors, got %d dimensions" % x.dim())
+        L = len(bank[0])
+        lens = dwt1d_lengths(x.shape[-1], L, mode, J)
+        for j in range(J):
+            if lens[j] < L // 2 + 1:
+                raise ValueError("level %d would read %d samples, below the minimum length L/2 + 1 = %d of a %d tap bank" % (j, lens[j], L // 2 + 1, L))
+        fused = _dwt1d_fused(lens[0], fused)
+        _dev_rows(x, "dwt1d_analysis")
+        ctx.cfg = (bank, mode, lens, fused)
+        lo, his = _dwt1d_analysis(x, bank, mode, lens[:J], fused)
+        return (lo,) + tuple(his)
+
+    @staticmethod
+    def backward(ctx, dlo, *dhis):
+        bank, mode, lens, fused = ctx.cfg
+        return _dwt1d_synthesis(dlo, list(dhis), bank, mode, lens[1:], lens[:-1], fused), None, None, None, None
+
+
+class _DWT1DSynthesis(Function):
+    """The inverse over all levels: ``apply(lo, bank, mode, fused, hi_0, .., hi_(J-1)) -> y``, a ``None`` level standing for zeros;
+    a surplus last sample of the running lowpass is dropped between levels, as ``DWT1DInverse`` does.  The backward is the
+    reference's (lowlevel.py:730-743 per level): the analysis bank on the SYNTHESIS taps with the mode's padding, a zero
+    appended wherever the forward dropped a sample -- one launch where the forward was one."""
+
+    @staticmethod
+    def forward(ctx, lo, bank, mode, fused, *his):
+        J = len(his)
+        _dwt1d_check(bank, mode, J)
+        for t in (lo,) + his:
+            if t is not None and t.dim() != 3:
+                raise ValueError("the 1-D transform takes (N, C, L) tensors, got %d dimensions" % t.dim())
+        for j, h in enumerate(his):
+            if h is not None and tuple(h.shape[:2]) != tuple(lo.shape[:2]):
+                raise ValueError("level %d: highpass %s and lowpass %s do not belong together" % (j, tuple(h.shape), tuple(lo.shape)))
+        counts, fulls = dwt1d_inverse_lengths(lo.shape[-1], [None if h is None else h.shape[-1] for h in his], len(bank[0]), mode)
+        fused = _dwt1d_fused(fulls[0], fused)
+        for t in (lo,) + his:
+            if t is not None:
+                _dev_rows(t, "dwt1d_synthesis")
+        ctx.cfg = (bank, mode, counts, fulls, lo.shape[-1], tuple(h is not None for h in his), fused)
+        return _dwt1d_synthesis(lo, list(his), bank, mode, counts, [fulls[0]] + counts[:-1], fused)
+
+    @staticmethod
+    def backward(ctx, dy):
+        bank, mode, counts, fulls, lo_len, has, fused = ctx.cfg
+        dlo, dhis = _dwt1d_analysis(dy, bank, mode, fulls, fused)
+        if lo_len > counts[-1]:                 # the coarsest lowpass lost its last sample on the way in
+            dlo = torch.nn.functional.pad(dlo, (0, lo_len - counts[-1]))
+        return (dlo, None, None, None) + tuple(d if h else None for d, h in zip(dhis, has))
+
+
+def dwt1d_analysis(x, h0, h1, mode, J=1, fused=None):
+    """(lo, [hi_0 .. hi_(J-1)]) of J analysis levels of (N, C, n) rows in one launch; the filters are tensors or sequences in
+    correlation order (the decomposition taps reversed).  ``fused``: None picks the fused launch up to ``DWT1D_FUSED_MAX``
+    samples a row and the tiled one (a launch per level) beyond, True / False force one (True beyond the limit raises)."""
+    out = _DWT1DAnalysis.apply(x, dwt1d_bank(h0, h1), int(mode), int(J), fused)
+    return out[0], list(out[1:])
+
+
+def dwt1d_synthesis(lo, highs, g0, g1, mode, fused=None):
+    """The inverse of ``dwt1d_analysis``'s coefficients in one launch; a ``None`` entry of ``highs`` stands for zeros."""
+    return _DWT1DSynthesis.apply(lo, dwt1d_bank(g0, g1), int(mode), fused, *highs)
+
+
+def afb1d(x, h0, h1, mode):
+    """(lo, hi) of one analysis level of (N, C, n) rows."""
+    return _DWT1DAnalysis.apply(x, dwt1d_bank(h0, h1), int(mode), 1, None)
+
+
+def sfb1d(lo, hi, g0, g1, mode):
+    """One synthesis level of (N, C, n) coefficients; ``hi`` may be None for zeros."""
+    return _DWT1DSynthesis.apply(lo, dwt1d_bank(g0, g1), int(mode), None, hi)
+
+
+# ----------------------------------------------------------------------------------------
 # stationary (a-trous) wavelet transform (csrc/swt.hip): any even tap count up to 16, four extensions, dilations 1..8
 # ----------------------------------------------------------------------------------------
 SWT_MODES = (0, 1, 4, 6)                # zero, symmetric, reflect, periodic (wavelets.swt_mode_to_int)

@@ -1,4 +1,4 @@
-"""2-D DWT / IDWT modules on fused HIP kernels, behind the interface of the reference's vendored pytorch_wavelets
+"""2-D and 1-D DWT / IDWT modules on fused HIP kernels, behind the interface of the reference's vendored pytorch_wavelets
 (pytorch_wavelets/pytorch_wavelets/dwt/transform2d.py:7-148, lowlevel.py:91-172,226-271,312-365,647-694).
 
 Two paths.  The Haar modules (``wave='haar'`` / ``'db1'``, or 2-tap Haar arrays) run the 2x2 block kernels the OCTA networks use
@@ -289,6 +289,97 @@ class DWTInverse(_TapModule):
             else:
                 ll = SFB2D.apply(ll, h, self.g0_col, self.g1_col, self.g0_row, self.g1_row, mode)
         return ll
+
+
+# ----------------------------------------------------------------------------------------
+# the 1-D transform over rows: transform1d.py:7-115, lowlevel.py:368-424, 697-743 -> csrc/dwt1d.hip
+# ----------------------------------------------------------------------------------------
+class AFB1D(Function):
+    """lowlevel.py:368-424: one 1-D analysis level; ``apply(x, h0, h1, mode_int) -> (x0, x1)`` for x of shape (N, C, L) and the
+    filters as ``DWT1DForward`` registers them.  The backward is the reference's: the synthesis bank on the analysis taps,
+    cropped to the input's length."""
+
+    @staticmethod
+    def forward(ctx, x, h0, h1, mode):
+        return ops._DWT1DAnalysis.forward(ctx, x, ops.dwt1d_bank(h0, h1), int(mode), 1, None)
+
+    @staticmethod
+    def backward(ctx, dx0, dx1):
+        return ops._DWT1DAnalysis.backward(ctx, dx0, dx1)[0], None, None, None
+
+
+class SFB1D(Function):
+    """lowlevel.py:697-743: one 1-D synthesis level; ``apply(low, high, g0, g1, mode_int) -> y``.  The backward is the analysis
+    bank on the synthesis taps with the mode's padding."""
+
+    @staticmethod
+    def forward(ctx, low, high, g0, g1, mode):
+        return ops._DWT1DSynthesis.forward(ctx, low, ops.dwt1d_bank(g0, g1), int(mode), None, high)
+
+    @staticmethod
+    def backward(ctx, dy):
+        g = ops._DWT1DSynthesis.backward(ctx, dy)
+        return g[0], g[4], None, None, None
+
+
+def _taps_1d(wave, analysis):
+    """``wave`` -> (lo, hi) float64 arrays in the order given; Haar is an ordinary 2-tap bank here."""
+    if isinstance(wave, str):
+        wave = _named(wave)
+    elif not all(hasattr(wave, a) for a in ("dec_lo", "dec_hi", "rec_lo", "rec_hi")) and len(wave) != 2:
+        raise ValueError("wave must be a name, a wavelet object, or a (lo, hi) pair of tap sequences; got %d sequences" % len(wave))
+    return _check_taps(_tap_arrays(wave, analysis))[:2]
+
+
+def _register_1d(module, taps, reverse):
+    for name, t in zip(module._tap_names, taps):
+        t = torch.tensor(np.ascontiguousarray(t[::-1] if reverse else t), dtype=torch.get_default_dtype())
+        module.register_buffer(name, t.reshape(1, 1, -1))
+    _record(module, module._tap_names)
+
+
+class DWT1DForward(_TapModule):
+    """transform1d.py:7-60.  forward(x) -> (yl, [yh_0 .. yh_{J-1}]) for x of shape (N, C, L): yh_j of shape (N, C, L_j) with
+    L_j = (L_{j-1} + taps - 1) // 2 (``(L_{j-1} + 1) // 2`` for periodization), contiguous.  Buffers h0, h1 of shape (1, 1, taps) as
+    ``prep_filt_afb1d`` registers them (the decomposition taps reversed).  ``wave``: a (lo, hi) pair, an object with
+    ``dec_lo .. rec_hi``, ``daubechies(N)``, or 'haar' / 'db1'.  All J levels of a row run in ONE launch (rows up to
+    ``DWT1D_FUSED_MAX`` samples; a launch per level beyond), J <= 8; every level's input needs L/2 + 1 samples."""
+
+    _tap_names = ("h0", "h1")
+
+    def __init__(self, J=1, wave="db1", mode="zero"):
+        super().__init__()
+        _register_1d(self, _taps_1d(wave, analysis=True), reverse=True)
+        self.J = J
+        self.mode = mode
+
+    def forward(self, x):
+        if x.dim() != 3:
+            raise ValueError("Can only handle 3d inputs (N, C, L), got %d dimensions" % x.dim())
+        _prime(self, self._tap_names)
+        return ops.dwt1d_analysis(x, self.h0, self.h1, mode_to_int(self.mode), self.J)
+
+
+class DWT1DInverse(_TapModule):
+    """transform1d.py:63-115.  forward((yl, yh)) -> x; a ``None`` entry in yh stands for a zero band.  A level returns
+    ``2 n - taps + 2`` samples (``2 n`` for periodization), so an odd-length input comes back one sample longer; a surplus last
+    sample of the running lowpass is dropped between levels, as in the reference, and a lowpass whose length still differs from
+    its level's highpass raises ``ValueError``.  Buffers g0, g1 of shape (1, 1, taps) hold the synthesis taps as given.  One
+    launch for all levels (results up to ``DWT1D_FUSED_MAX`` samples a row)."""
+
+    _tap_names = ("g0", "g1")
+
+    def __init__(self, wave="db1", mode="zero"):
+        super().__init__()
+        _register_1d(self, _taps_1d(wave, analysis=False), reverse=False)
+        self.mode = mode
+
+    def forward(self, coeffs):
+        yl, yh = coeffs
+        if yl.dim() != 3:
+            raise ValueError("Can only handle 3d inputs (N, C, L), got %d dimensions" % yl.dim())
+        _prime(self, self._tap_names)
+        return ops.dwt1d_synthesis(yl, list(yh), self.g0, self.g1, mode_to_int(self.mode))
 
 
 # ----------------------------------------------------------------------------------------

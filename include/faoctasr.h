@@ -301,6 +301,33 @@ int faoctasr_dwt2d_synthesis(const float* ll, const float* hi, float* y, long NC
                              const float* lo_h, const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w,
                              int mode, faoctasr_stream_t stream);
 
+/* ---- 1-D filter-bank DWT / IDWT over rows, all levels of a row in one launch (csrc/dwt1d.hip) ----
+ * pytorch_wavelets dwt/transform1d.py:7-115 (DWT1DForward / DWT1DInverse), dwt/lowlevel.py:368-424 (AFB1D), 697-743 (SFB1D).  One
+ * lowpass / highpass pair of L taps, L even and 2 <= L <= 16, as HOST pointers read during the call and passed to the kernel by
+ * value, like the host arrays of per-level pointers and lengths (nothing is allocated or copied: the launch is capturable);
+ * analysis taps as the correlation kernels the reference registers (the decomposition taps reversed), synthesis taps as given;
+ * modes as for the 2-D bank; 1 <= J <= 8 levels.  The rows of the strided operand: row r starts (r / inner) * outer_stride +
+ * (r % inner) * row_stride elements in, samples contiguous (an (N, C, n) tensor: inner = C).  fused = 1: one launch runs all J
+ * levels of a row in LDS, rows of at most faoctasr_dwt1d_fused_max() samples; fused = 0: the tiled launch, any length, J = 1
+ * only (one call per level).  Both give the same bits.  FAOCTASR_EINVAL for anything outside these. */
+long faoctasr_dwt1d_fused_max(void);
+/* Analysis: NC rows of n samples -> lo[NC, n_J], hi[j][NC, n_(j+1)] for j = 0 .. J-1 (hi: a host array of J device pointers),
+ * per level out[i] = sum_k h[k] xe[2 i + k - base], n_(j+1) = (m + 1) / 2 for periodization and (m + L - 1) / 2 otherwise, m the
+ * level's input length.  in_lens (NULL: every level reads what the one before produced; level 0 reads n): J host ints, the
+ * length level j is to read -- what its source holds, or ONE more: the extra sample is a zero appended before the extension.
+ * Every level's input has at least 2 samples.  Also SFB1D.backward (with the synthesis taps). */
+int faoctasr_dwt1d_analysis(const float* x, long x_inner, long x_outer_stride, long x_row_stride, float* lo, float* const* hi,
+                            long NC, int n, const int* in_lens, int J, const float* h0, const float* h1, int L, int mode,
+                            int fused, faoctasr_stream_t stream);
+/* Synthesis: lo (NC strided rows, the first counts[J-1] samples of each are read), hi[j][NC, counts[j]] (a host array of J
+ * device pointers, a NULL entry = zeros), counts: J host ints, the coefficient count of level j (0 = finest) -> y[NC, out_len].
+ * From the coarsest level to the finest; level j's result (2 c - L + 2 samples, periodization 2 c) is cropped to counts[j-1],
+ * the finest level's to out_len; a crop longer than the result is an error, as is a count below L / 2 (periodization: below
+ * (L + 3) / 4).  Also AFB1D.backward (with the analysis taps, the crops being the levels' input lengths). */
+int faoctasr_dwt1d_synthesis(const float* lo, long lo_inner, long lo_outer_stride, long lo_row_stride, const float* const* hi,
+                             float* y, long NC, const int* counts, int J, int out_len, const float* g0, const float* g1, int L,
+                             int mode, int fused, faoctasr_stream_t stream);
+
 /* ---- stationary (undecimated, a-trous) 2-D wavelet transform, one level per call (csrc/swt.hip) --
  * pytorch_wavelets dwt/lowlevel.py:175-223 (afb1d_atrous), 475-521 (afb2d_atrous); transform2d.py:151-212 (SWTForward).  The taps
  * are HOST pointers, read during the call and passed to the kernel by value (the launch is capturable), in WAVELET order
