@@ -71,6 +71,10 @@ _SIG = {
     "dwt1d_synthesis": (_I, "p lll pp l p i i pp i i i p"),
     "swt2d_analysis": (_I, "p l p l ii ppi ppi i i f p"),
     "swt2d_adjoint": (_I, "pp l p l i l ii ppi ppi i i f p"),
+    "dtcwt_fwd_j1": (_I, "p lll pp llllll i l iii pi pi i p"),
+    "dtcwt_fwd_j2": (_I, "p lll pp llllll i l iii pppp i p"),
+    "dtcwt_inv_j1": (_I, "p lll p llllll p l iii pi pi i p"),
+    "dtcwt_inv_j2": (_I, "p lll p llllll p l iii pppp i p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -1,0 +1,507 @@
+// Dual-tree complex wavelet transform, one level per launch, fp32 (pytorch_wavelets dtcwt/transform_funcs.py fwd_j1, fwd_j2plus,
+// inv_j1, inv_j2plus; dtcwt/lowlevel.py colfilter .. rowifilt, q2c, c2q).  Four kernels serve the forward, the inverse and all four
+// backward passes (each backward is another of the four on swapped taps, transform_funcs.py:343-488).
+//
+// Notation.  fold(j, N) is the half-sample symmetric extension of period 2N (MODE_SYMMETRIC of dwt.hip), applied any number of
+// times; xs is x read through it, or -- level 1 in any mode but 'symmetric' -- x with zeros outside [0, N).  Filters arrive as the
+// modules register them (taps reversed), so every sum below is a plain correlation with the buffer `buf`.
+//
+// Level 1, per axis (W first, then H), L odd:           out[i] = sum_t buf[t] xs[i + t - L/2]            ("same" size)
+//   ll = lo.lo, lh = (W lo, H hi), hl = (W hi, H lo), hh = hi.hi at full resolution; the lowpass filter h0 and the highpass h1
+//   may differ in length.
+// Level >= 2, per axis of length r (r % 4 == 0), m even taps, always symmetric:
+//   lowpass call   out[2i] = sum_t h0b[t] xs[4i + 2t + 2 - m],   out[2i+1] = sum_t h0a[t] xs[4i + 2t + 3 - m]
+//   highpass call  out[2i] = sum_t h1a[t] xs[4i + 2t + 3 - m],   out[2i+1] = sum_t h1b[t] xs[4i + 2t + 2 - m]
+// q2c on every 2x2 quad a=(2i,2j) b=(2i,2j+1) c=(2i+1,2j) d=(2i+1,2j+1), scaled by 1/sqrt 2 first:
+//   z1 = (a - d) + i (b + c),  z2 = (a + d) + i (b - c);   orientations 15,45,75,105,135,165 = lh.z1, hh.z1, hl.z1, hl.z2, hh.z2, lh.z2.
+// c2q is its inverse map: (2i,2j) = w1r + w2r, (2i,2j+1) = w1i + w2i, (2i+1,2j) = w1i - w2i, (2i+1,2j+1) = w2r - w1r, times 1/sqrt 2.
+// Inverse level 1:   y = row(col(hh, g1) + col(hl, g0), g1) + row(col(lh, g1) + col(ll, g0), g0)     (H first, then W).
+// Inverse level >= 2: the same sums with the 2x interpolation     out[4i + q] = sum_{t < m/2} half_q[t] xs[2 (i + t) + d_q - m/2],
+//   q = 0..3, where half_q is the even or odd polyphase half of one of the two trees' filters and d_q an offset in 0..3; both
+//   depend on the parity of m/2 and on whether the call is a lowpass or a highpass one (lowlevel.py:154-239; the host builds
+//   the table, dtcwt_ifilt_taps below).
+//
+// Every kernel: a block owns a tile of one (n, c) plane, stages its input patch (tile + halo) in LDS through the index map --
+// the inverses apply c2q while staging --, runs the first pass into LDS and the second into registers, applies q2c there and
+// stores.  The input is read once (plus the halo), every output written once, nothing intermediate leaves the CU; the taps
+// travel by value in the kernel arguments (no device allocation, no state, capturable).  Every output is a fixed-order sum
+// (t = 0 .. L-1 per pass, no atomics), whatever the tile it falls in: bit-reproducible.
+//
+// The bandpass tensor is addressed through element strides of its (n, c, orientation, row, column, re/im) axes, so any
+// o_dim / ri_dim layout and any view runs without a copy; where re/im are adjacent and 8-byte aligned the pair moves as one
+// float2.  The lowpass input takes (n, c, row) strides, columns unit-stride.  Outputs the kernels own (ll, y) are contiguous.
+#include <cstdint>
+#include "common.h"
+
+namespace faoctasr {
+
+constexpr int DT_MAXL = 20;                       // level 1: odd 3..19; q-shift: even 4..20
+constexpr float DT_S = 0.70710678118654752440f;
+
+struct DtStr { long n, c, o, r, w, i; };         // bandpass element strides
+struct DtLow { long n, c, r; };                  // lowpass input element strides
+
+struct DtTaps1 { float f0[DT_MAXL], f1[DT_MAXL]; };                      // level 1: lowpass, highpass
+struct DtTaps2 { float lo0[DT_MAXL], lo1[DT_MAXL], hi0[DT_MAXL], hi1[DT_MAXL]; };   // level >= 2 analysis, by output phase
+struct DtTapsI { float lo[4][DT_MAXL / 2], hi[4][DT_MAXL / 2]; int dlo[4], dhi[4]; };   // level >= 2 synthesis, by output phase q
+
+// level-1 tiles (forward: of ll; inverse: of y) and the level >= 2 ones (forward: of ll = 4 x 32 quads; inverse: of y)
+constexpr int J1_TH = 16, J1_TW = 64, J1_PR = J1_TH + DT_MAXL - 2, J1_PC = J1_TW + DT_MAXL - 2;          // halo 2 * 9
+constexpr int F2_TH = 8, F2_TW = 64, F2_PR = 2 * F2_TH + 2 * DT_MAXL - 4, F2_PC = 2 * F2_TW + 2 * DT_MAXL - 4;
+constexpr int I2_TH = 32, I2_TW = 64, I2_PR = I2_TH / 2 + DT_MAXL, I2_PC = I2_TW / 2 + DT_MAXL;
+
+// index of the sample that position j of the extension reads; -1 for a zero
+__device__ __forceinline__ int dt_map(int j, int N, int sym) {
+    if (sym) {
+        int m = j % (2 * N);
+        if (m < 0) m += 2 * N;
+        return m < N ? m : 2 * N - 1 - m;
+    }
+    return (j >= 0 && j < N) ? j : -1;
+}
+
+__device__ __forceinline__ void dt_put(float* p, long si, bool vec, float re, float im) {
+    if (vec) *reinterpret_cast<float2*>(p) = make_float2(re, im);
+    else { p[0] = re; p[si] = im; }
+}
+
+// q2c of one quad (top = a, b; bot = c, d) into orientations o1 (z1) and o2 (z2)
+__device__ __forceinline__ void dt_q2c(float* q, const DtStr& s, bool vec, int o1, int o2, float2 top, float2 bot) {
+    const float a = top.x * DT_S, b = top.y * DT_S, c = bot.x * DT_S, d = bot.y * DT_S;
+    dt_put(q + o1 * s.o, s.i, vec, a - d, b + c);
+    dt_put(q + o2 * s.o, s.i, vec, a + d, b - c);
+}
+
+// c2q: the value at row parity pr, column parity pc of the quad whose complex pair (w1, w2) starts at p1, p2
+__device__ __forceinline__ float dt_c2q(const float* p1, const float* p2, long si, int pr, int pc) {
+    const long comp = (pr ^ pc) ? si : 0;                   // (0,1) and (1,0) read the imaginary parts
+    const float w1 = p1[comp], w2 = p2[comp];
+    return (pr ? (pc ? w2 - w1 : w1 - w2) : w1 + w2) * DT_S;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// level 1 forward
+// ---------------------------------------------------------------------------------------------------------------------------
+template <bool HIGHS>
+__global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x, DtLow xs, float* __restrict__ ll, float* __restrict__ hi,
+                                                    DtStr hs, int vec, int C, int H, int W, int tiles_h, int tiles_w, int L0, int L1,
+                                                    int sym, DtTaps1 taps) {
+    __shared__ float patch[J1_PR][J1_PC];
+    __shared__ __attribute__((aligned(16))) float mid_lo[J1_PR][J1_TW];
+    __shared__ __attribute__((aligned(16))) float mid_hi[HIGHS ? J1_PR : 1][J1_TW];
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    const int tw = b % tiles_w; b /= tiles_w;
+    const int th = b % tiles_h;
+    const long plane = b / tiles_h;
+    const long n = plane / C, c = plane % C;
+    const int oi0 = th * J1_TH, oj0 = tw * J1_TW;
+    const int hm = (L0 > L1 ? L0 : L1) >> 1, a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
+    const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;               // <= J1_PR, J1_PC
+    const float* xp = x + n * xs.n + c * xs.c;
+
+    for (int r = tid >> 6; r < rows; r += 4) {
+        const int sr = dt_map(oi0 - hm + r, H, sym);
+        for (int cc = tid & 63; cc < cols; cc += 64) {
+            const int sc = dt_map(oj0 - hm + cc, W, sym);
+            patch[r][cc] = (sr >= 0 && sc >= 0) ? xp[sr * xs.r + sc] : 0.f;
+        }
+    }
+    __syncthreads();
+
+    {   // W pass: thread (r, cc) filters patch row r at tile column cc
+        const int cc = tid & 63;
+        for (int r = tid >> 6; r < rows; r += 4) {
+            float lo = 0.f;
+            for (int t = 0; t < L0; ++t) lo = fmaf(taps.f0[t], patch[r][cc + t + a0], lo);
+            mid_lo[r][cc] = lo;
+            if (HIGHS) {
+                float hv = 0.f;
+                for (int t = 0; t < L1; ++t) hv = fmaf(taps.f1[t], patch[r][cc + t + a1], hv);
+                mid_hi[r][cc] = hv;
+            }
+        }
+    }
+    __syncthreads();
+
+    // H pass: a thread owns one 2x2 quad of the tile (8 x 32 quads), reads the column pair as float2
+    const int qi = tid >> 5, qj = tid & 31;
+    const int oi = oi0 + 2 * qi, oj = oj0 + 2 * qj;
+    if (oi >= H || oj >= W) return;                                       // H, W even: a quad is inside or outside as a whole
+    float2 vll[2], vlh[2], vhl[2], vhh[2];
+    for (int d = 0; d < 2; ++d) {
+        float2 s = make_float2(0.f, 0.f);
+        for (int t = 0; t < L0; ++t) {
+            const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a0][2 * qj]);
+            s.x = fmaf(taps.f0[t], v.x, s.x); s.y = fmaf(taps.f0[t], v.y, s.y);
+        }
+        vll[d] = s;
+        if (HIGHS) {
+            float2 u = make_float2(0.f, 0.f), p = u, q = u;
+            for (int t = 0; t < L1; ++t) {
+                const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a1][2 * qj]);
+                const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a1][2 * qj]);
+                u.x = fmaf(taps.f1[t], v.x, u.x); u.y = fmaf(taps.f1[t], v.y, u.y);
+                q.x = fmaf(taps.f1[t], w.x, q.x); q.y = fmaf(taps.f1[t], w.y, q.y);
+            }
+            for (int t = 0; t < L0; ++t) {
+                const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a0][2 * qj]);
+                p.x = fmaf(taps.f0[t], w.x, p.x); p.y = fmaf(taps.f0[t], w.y, p.y);
+            }
+            vlh[d] = u; vhl[d] = p; vhh[d] = q;
+        }
+    }
+    if (ll) {
+        float* lp = ll + plane * H * (long)W + (long)oi * W + oj;
+        *reinterpret_cast<float2*>(lp) = vll[0];
+        *reinterpret_cast<float2*>(lp + W) = vll[1];
+    }
+    if (HIGHS) {
+        float* q = hi + n * hs.n + c * hs.c + (long)(oi >> 1) * hs.r + (long)(oj >> 1) * hs.w;
+        dt_q2c(q, hs, vec, 0, 5, vlh[0], vlh[1]);
+        dt_q2c(q, hs, vec, 1, 4, vhh[0], vhh[1]);
+        dt_q2c(q, hs, vec, 2, 3, vhl[0], vhl[1]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// level >= 2 forward: x [H, W] (multiples of 4) -> ll [H/2, W/2], six complex bands [H/4, W/4]
+// ---------------------------------------------------------------------------------------------------------------------------
+template <bool HIGHS>
+__global__ __launch_bounds__(256) void dtcwt_fwd_j2(const float* __restrict__ x, DtLow xs, float* __restrict__ ll, float* __restrict__ hi,
+                                                    DtStr hs, int vec, int C, int H, int W, int tiles_h, int tiles_w, int m, DtTaps2 taps) {
+    __shared__ __attribute__((aligned(16))) float patch[F2_PR][F2_PC];
+    __shared__ __attribute__((aligned(16))) float mid_lo[F2_PR][F2_TW];
+    __shared__ __attribute__((aligned(16))) float mid_hi[HIGHS ? F2_PR : 1][F2_TW];
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    const int tw = b % tiles_w; b /= tiles_w;
+    const int th = b % tiles_h;
+    const long plane = b / tiles_h;
+    const long n = plane / C, c = plane % C;
+    const int OH = H >> 1, OW = W >> 1;
+    const int i0 = th * (F2_TH / 2), j0 = tw * (F2_TW / 2);               // first quad row / column = first index of the trees
+    const int rows = 2 * F2_TH + 2 * m - 4, cols = 2 * F2_TW + 2 * m - 4;  // <= F2_PR, F2_PC; patch (r, cc) is x position 4 i0 + 2 - m + r
+    const float* xp = x + n * xs.n + c * xs.c;
+
+    for (int r = tid >> 6; r < rows; r += 4) {
+        const int sr = dt_map(4 * i0 + 2 - m + r, H, 1);
+        for (int cc = tid & 63; cc < cols; cc += 64)
+            patch[r][cc] = xp[sr * xs.r + dt_map(4 * j0 + 2 - m + cc, W, 1)];
+    }
+    __syncthreads();
+
+    {   // W pass: tile column cc = 2 i + p; the float2 at patch column 4 i + 2 t holds the samples at offsets 2 - m and 3 - m
+        const int cc = tid & 63, i = cc >> 1, p = cc & 1;
+        for (int r = tid >> 6; r < rows; r += 4) {
+            float lo = 0.f, hv = 0.f;
+            for (int t = 0; t < m; ++t) {
+                const float2 v = *reinterpret_cast<const float2*>(&patch[r][4 * i + 2 * t]);
+                lo = fmaf(p ? taps.lo1[t] : taps.lo0[t], p ? v.y : v.x, lo);
+                if (HIGHS) hv = fmaf(p ? taps.hi1[t] : taps.hi0[t], p ? v.x : v.y, hv);
+            }
+            mid_lo[r][cc] = lo;
+            if (HIGHS) mid_hi[r][cc] = hv;
+        }
+    }
+    __syncthreads();
+
+    // H pass: 4 x 32 quads; threads 0..127 take the W-lowpass plane (ll, lh), threads 128..255 the W-highpass plane (hl, hh)
+    const int path = tid >> 7, qi = (tid & 127) >> 5, qj = tid & 31;
+    if (!HIGHS && path) return;
+    const int oi = 2 * (i0 + qi), oj = 2 * (j0 + qj);                      // top-left of the quad in ll
+    if (oi >= OH || oj >= OW) return;
+    float2 l0 = make_float2(0.f, 0.f), l1 = l0, h0 = l0, h1 = l0;         // lowpass call rows 2qi, 2qi+1; highpass call likewise
+    for (int t = 0; t < m; ++t) {
+        const float* mp = path ? &mid_hi[HIGHS ? 4 * qi + 2 * t : 0][2 * qj] : &mid_lo[4 * qi + 2 * t][2 * qj];
+        const float2 r0 = *reinterpret_cast<const float2*>(mp), r1 = *reinterpret_cast<const float2*>(mp + F2_TW);
+        l0.x = fmaf(taps.lo0[t], r0.x, l0.x); l0.y = fmaf(taps.lo0[t], r0.y, l0.y);
+        l1.x = fmaf(taps.lo1[t], r1.x, l1.x); l1.y = fmaf(taps.lo1[t], r1.y, l1.y);
+        if (HIGHS) {
+            h0.x = fmaf(taps.hi0[t], r1.x, h0.x); h0.y = fmaf(taps.hi0[t], r1.y, h0.y);
+            h1.x = fmaf(taps.hi1[t], r0.x, h1.x); h1.y = fmaf(taps.hi1[t], r0.y, h1.y);
+        }
+    }
+    if (!path && ll) {
+        float* lp = ll + plane * OH * (long)OW + (long)oi * OW + oj;
+        *reinterpret_cast<float2*>(lp) = l0;
+        *reinterpret_cast<float2*>(lp + OW) = l1;
+    }
+    if (HIGHS) {
+        float* q = hi + n * hs.n + c * hs.c + (long)(i0 + qi) * hs.r + (long)(j0 + qj) * hs.w;
+        if (path) {
+            dt_q2c(q, hs, vec, 2, 3, l0, l1);                             // hl
+            dt_q2c(q, hs, vec, 1, 4, h0, h1);                             // hh
+        } else {
+            dt_q2c(q, hs, vec, 0, 5, h0, h1);                             // lh
+        }
+    }
+}
+
+// stage one coefficient position (sr, sc) of the four full-resolution planes ll, lh, hl, hh (c2q applied on the way)
+__device__ __forceinline__ void dt_stage(const float* lp, DtLow ls, const float* hp, const DtStr& hs, int sr, int sc, float* o0, float* o1,
+                                         float* o2, float* o3) {
+    *o0 = lp ? lp[sr * ls.r + sc] : 0.f;
+    if (hp) {
+        const float* q = hp + (long)(sr >> 1) * hs.r + (long)(sc >> 1) * hs.w;
+        const int pr = sr & 1, pc = sc & 1;
+        *o1 = dt_c2q(q, q + 5 * hs.o, hs.i, pr, pc);                      // lh: 15, 165
+        *o2 = dt_c2q(q + 2 * hs.o, q + 3 * hs.o, hs.i, pr, pc);           // hl: 75, 105
+        *o3 = dt_c2q(q + hs.o, q + 4 * hs.o, hs.i, pr, pc);               // hh: 45, 135
+    } else {
+        *o1 = *o2 = *o3 = 0.f;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// level 1 inverse: ll [H, W], six complex bands [H/2, W/2] (either may be null = zeros, its path is skipped) -> y [H, W]
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dtcwt_inv_j1(const float* __restrict__ ll, DtLow ls, const float* __restrict__ hi, DtStr hs,
+                                                    float* __restrict__ y, int C, int H, int W, int tiles_h, int tiles_w, int L0, int L1,
+                                                    int sym, DtTaps1 taps) {
+    __shared__ float cf[4][J1_PR][J1_PC];
+    __shared__ float mid_lo[J1_TH][J1_PC], mid_hi[J1_TH][J1_PC];
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    const int tw = b % tiles_w; b /= tiles_w;
+    const int th = b % tiles_h;
+    const long plane = b / tiles_h;
+    const long n = plane / C, c = plane % C;
+    const int t0 = th * J1_TH, s0 = tw * J1_TW;
+    const int hm = (L0 > L1 ? L0 : L1) >> 1, a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
+    const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;
+    const float* lp = ll ? ll + n * ls.n + c * ls.c : nullptr;
+    const float* hp = hi ? hi + n * hs.n + c * hs.c : nullptr;
+
+    for (int r = tid >> 6; r < rows; r += 4) {
+        const int sr = dt_map(t0 - hm + r, H, sym);
+        for (int cc = tid & 63; cc < cols; cc += 64) {
+            const int sc = dt_map(s0 - hm + cc, W, sym);
+            if (sr >= 0 && sc >= 0) dt_stage(lp, ls, hp, hs, sr, sc, &cf[0][r][cc], &cf[1][r][cc], &cf[2][r][cc], &cf[3][r][cc]);
+            else cf[0][r][cc] = cf[1][r][cc] = cf[2][r][cc] = cf[3][r][cc] = 0.f;
+        }
+    }
+    __syncthreads();
+
+    // H pass: lo = col(lh, g1) + col(ll, g0), hi = col(hh, g1) + col(hl, g0), for every tile row and patch column
+    for (int tt = tid >> 6; tt < J1_TH; tt += 4) {
+        for (int cc = tid & 63; cc < cols; cc += 64) {
+            float l1 = 0.f, l0 = 0.f, h1 = 0.f, h0 = 0.f;
+            if (hp) {
+                for (int t = 0; t < L1; ++t) {
+                    l1 = fmaf(taps.f1[t], cf[1][tt + t + a1][cc], l1);
+                    h1 = fmaf(taps.f1[t], cf[3][tt + t + a1][cc], h1);
+                }
+                for (int t = 0; t < L0; ++t) h0 = fmaf(taps.f0[t], cf[2][tt + t + a0][cc], h0);
+            }
+            if (lp)
+                for (int t = 0; t < L0; ++t) l0 = fmaf(taps.f0[t], cf[0][tt + t + a0][cc], l0);
+            mid_lo[tt][cc] = l1 + l0;
+            mid_hi[tt][cc] = h1 + h0;
+        }
+    }
+    __syncthreads();
+
+    float* yp = y + plane * H * (long)W;
+    const int ss = tid & 63, s = s0 + ss;
+    for (int tt = tid >> 6; tt < J1_TH; tt += 4) {
+        const int t = t0 + tt;
+        if (t >= H || s >= W) continue;
+        float vh = 0.f, vl = 0.f;
+        if (hp)
+            for (int k = 0; k < L1; ++k) vh = fmaf(taps.f1[k], mid_hi[tt][ss + k + a1], vh);
+        for (int k = 0; k < L0; ++k) vl = fmaf(taps.f0[k], mid_lo[tt][ss + k + a0], vl);
+        yp[(long)t * W + s] = vh + vl;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// level >= 2 inverse: ll [R, Q], six complex bands [R/2, Q/2] (either may be null) -> y [2R, 2Q]; always symmetric
+// ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll, DtLow ls, const float* __restrict__ hi, DtStr hs,
+                                                    float* __restrict__ y, int C, int R, int Q, int tiles_h, int tiles_w, int m2, DtTapsI taps) {
+    __shared__ float cf[4][I2_PR][I2_PC];
+    __shared__ float mid_lo[I2_TH][I2_PC], mid_hi[I2_TH][I2_PC];
+    __shared__ float tl[2][4][DT_MAXL / 2];
+    __shared__ int td[2][4];
+    const int tid = threadIdx.x;
+    int b = blockIdx.x;
+    const int tw = b % tiles_w; b /= tiles_w;
+    const int th = b % tiles_h;
+    const long plane = b / tiles_h;
+    const long n = plane / C, c = plane % C;
+    const int t0 = th * I2_TH, s0 = tw * I2_TW, OH = 2 * R, OW = 2 * Q;
+    const int i0 = t0 >> 2, j0 = s0 >> 2;
+    const int rows = I2_TH / 2 + 2 * m2, cols = I2_TW / 2 + 2 * m2;      // patch (r, cc) is coefficient position 2 i0 - m2 + r
+    const float* lp = ll ? ll + n * ls.n + c * ls.c : nullptr;
+    const float* hp = hi ? hi + n * hs.n + c * hs.c : nullptr;
+
+    if (tid < 4 * (DT_MAXL / 2)) {                                        // the per-phase taps, for the lane-varying phase of the W pass
+        tl[0][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.lo[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
+        tl[1][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.hi[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
+    }
+    if (tid < 4) { td[0][tid] = taps.dlo[tid]; td[1][tid] = taps.dhi[tid]; }
+    for (int r = tid >> 6; r < rows; r += 4) {
+        const int sr = dt_map(2 * i0 - m2 + r, R, 1);
+        for (int cc = tid & 63; cc < cols; cc += 64)
+            dt_stage(lp, ls, hp, hs, sr, dt_map(2 * j0 - m2 + cc, Q, 1), &cf[0][r][cc], &cf[1][r][cc], &cf[2][r][cc], &cf[3][r][cc]);
+    }
+    __syncthreads();
+
+    // H pass: a wave takes a tile row (its phase q is uniform), lanes the patch columns
+    for (int tt = tid >> 6; tt < I2_TH; tt += 4) {
+        const int q = tt & 3, ii = tt >> 2;                               // t0 is a multiple of 4
+        const int rl = 2 * ii + td[0][q], rh = 2 * ii + td[1][q];
+        for (int cc = tid & 63; cc < cols; cc += 64) {
+            float l1 = 0.f, l0 = 0.f, h1 = 0.f, h0 = 0.f;
+            if (hp)
+                for (int t = 0; t < m2; ++t) {
+                    l1 = fmaf(tl[1][q][t], cf[1][rh + 2 * t][cc], l1);
+                    h1 = fmaf(tl[1][q][t], cf[3][rh + 2 * t][cc], h1);
+                    h0 = fmaf(tl[0][q][t], cf[2][rl + 2 * t][cc], h0);
+                }
+            if (lp)
+                for (int t = 0; t < m2; ++t) l0 = fmaf(tl[0][q][t], cf[0][rl + 2 * t][cc], l0);
+            mid_lo[tt][cc] = l1 + l0;
+            mid_hi[tt][cc] = h1 + h0;
+        }
+    }
+    __syncthreads();
+
+    float* yp = y + plane * OH * (long)OW;
+    const int ss = tid & 63, s = s0 + ss, q = ss & 3, jj = ss >> 2;
+    const int cl = 2 * jj + td[0][q], ch = 2 * jj + td[1][q];
+    for (int tt = tid >> 6; tt < I2_TH; tt += 4) {
+        const int t = t0 + tt;
+        if (t >= OH || s >= OW) continue;
+        float vh = 0.f, vl = 0.f;
+        if (hp)
+            for (int k = 0; k < m2; ++k) vh = fmaf(tl[1][q][k], mid_hi[tt][ch + 2 * k], vh);
+        for (int k = 0; k < m2; ++k) vl = fmaf(tl[0][q][k], mid_lo[tt][cl + 2 * k], vl);
+        yp[(long)t * OW + s] = vh + vl;
+    }
+}
+
+static int dt_blocks(const char* what, long N, int C, int tiles_h, int tiles_w, long* blocks) {
+    if (N < 1 || C < 1) return fail(FAOCTASR_EINVAL, "%s: N %ld C %d", what, N, C);
+    *blocks = N * C * tiles_h * (long)tiles_w;
+    if (*blocks > 0x7fffffffL) return fail(FAOCTASR_EUNSUPPORTED, "%s: N %ld C %d needs more than 2^31 - 1 blocks", what, N, C);
+    return FAOCTASR_OK;
+}
+
+static int dt_taps1(const char* what, const float* f0, int L0, const float* f1, int L1, DtTaps1* t) {
+    if (!f0 || !f1) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
+    if (L0 < 3 || L0 >= DT_MAXL || !(L0 & 1) || L1 < 3 || L1 >= DT_MAXL || !(L1 & 1))
+        return fail(FAOCTASR_EINVAL, "%s: level-1 tap counts %d and %d must be odd and within 3..%d", what, L0, L1, DT_MAXL - 1);
+    *t = DtTaps1{};
+    for (int k = 0; k < L0; ++k) t->f0[k] = f0[k];
+    for (int k = 0; k < L1; ++k) t->f1[k] = f1[k];
+    return FAOCTASR_OK;
+}
+
+static int dt_taps2_check(const char* what, const float* a, const float* b, const float* c, const float* d, int m) {
+    if (!a || !b || !c || !d) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
+    if (m < 4 || m > DT_MAXL || (m & 1)) return fail(FAOCTASR_EINVAL, "%s: q-shift tap count %d must be even and within 4..%d", what, m, DT_MAXL);
+    return FAOCTASR_OK;
+}
+
+// the table of lowlevel.py:154-239: per output phase q the polyphase half and offset of colifilt(X, fa, fb, highpass)
+static void dtcwt_ifilt_taps(const float* fa, const float* fb, int m, int highpass, float out[4][DT_MAXL / 2], int d[4]) {
+    const int m2 = m / 2;
+    // which filter (0 = fa, 1 = fb), which half (0 = even taps, 1 = odd taps), offset
+    static const int even_lo[4][3] = {{0, 0, 0}, {1, 0, 1}, {0, 1, 2}, {1, 1, 3}}, even_hi[4][3] = {{0, 0, 1}, {1, 0, 0}, {0, 1, 3}, {1, 1, 2}};
+    static const int odd_lo[4][3] = {{0, 1, 1}, {1, 1, 2}, {0, 0, 1}, {1, 0, 2}}, odd_hi[4][3] = {{0, 1, 2}, {1, 1, 1}, {0, 0, 2}, {1, 0, 1}};
+    const int (*tab)[3] = (m2 & 1) ? (highpass ? odd_hi : odd_lo) : (highpass ? even_hi : even_lo);
+    for (int q = 0; q < 4; ++q) {
+        const float* f = tab[q][0] ? fb : fa;
+        for (int t = 0; t < DT_MAXL / 2; ++t) out[q][t] = t < m2 ? f[2 * t + tab[q][1]] : 0.f;
+        d[q] = tab[q][2];
+    }
+}
+
+}  // namespace faoctasr
+
+using namespace faoctasr;
+
+extern "C" int faoctasr_dtcwt_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                                     long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
+                                     const float* h0, int L0, const float* h1, int L1, int mode, faoctasr_stream_t stream) {
+    DtTaps1 t;
+    int rc = dt_taps1("dtcwt_fwd_j1", h0, L0, h1, L1, &t);
+    if (rc) return rc;
+    if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j1: null pointer");
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j1: H %d W %d must be even and at least 2", H, W);
+    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j1: unknown padding mode %d", mode);
+    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
+    long blocks;
+    if ((rc = dt_blocks("dtcwt_fwd_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
+    const DtLow xs{x_sn, x_sc, x_sr};
+    const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
+    if (hi)
+        hipLaunchKernelGGL(dtcwt_fwd_j1<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C, H, W,
+                           tiles_h, tiles_w, L0, L1, mode == 1, t);
+    else
+        hipLaunchKernelGGL(dtcwt_fwd_j1<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, 0, C, H, W,
+                           tiles_h, tiles_w, L0, L1, mode == 1, t);
+    return check_launch("dtcwt_fwd_j1");
+}
+
+extern "C" int faoctasr_dtcwt_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                                     long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
+                                     const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
+                                     faoctasr_stream_t stream) {
+    int rc = dt_taps2_check("dtcwt_fwd_j2", h0a, h0b, h1a, h1b, m);
+    if (rc) return rc;
+    if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j2: null pointer");
+    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j2: H %d W %d must be multiples of 4", H, W);
+    const int tiles_h = (H / 2 + F2_TH - 1) / F2_TH, tiles_w = (W / 2 + F2_TW - 1) / F2_TW;
+    long blocks;
+    if ((rc = dt_blocks("dtcwt_fwd_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
+    DtTaps2 t = {};
+    for (int k = 0; k < m; ++k) { t.lo0[k] = h0b[k]; t.lo1[k] = h0a[k]; t.hi0[k] = h1a[k]; t.hi1[k] = h1b[k]; }
+    const DtLow xs{x_sn, x_sc, x_sr};
+    const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
+    if (hi)
+        hipLaunchKernelGGL(dtcwt_fwd_j2<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C, H, W,
+                           tiles_h, tiles_w, m, t);
+    else
+        hipLaunchKernelGGL(dtcwt_fwd_j2<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, 0, C, H, W,
+                           tiles_h, tiles_w, m, t);
+    return check_launch("dtcwt_fwd_j2");
+}
+
+extern "C" int faoctasr_dtcwt_inv_j1(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                                     long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
+                                     const float* g0, int L0, const float* g1, int L1, int mode, faoctasr_stream_t stream) {
+    DtTaps1 t;
+    int rc = dt_taps1("dtcwt_inv_j1", g0, L0, g1, L1, &t);
+    if (rc) return rc;
+    if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j1: null pointer");
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j1: H %d W %d must be even and at least 2", H, W);
+    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j1: unknown padding mode %d", mode);
+    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
+    long blocks;
+    if ((rc = dt_blocks("dtcwt_inv_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
+    hipLaunchKernelGGL(dtcwt_inv_j1, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
+                       DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
+    return check_launch("dtcwt_inv_j1");
+}
+
+extern "C" int faoctasr_dtcwt_inv_j2(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                                     long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
+                                     const float* g0a, const float* g0b, const float* g1a, const float* g1b, int m,
+                                     faoctasr_stream_t stream) {
+    int rc = dt_taps2_check("dtcwt_inv_j2", g0a, g0b, g1a, g1b, m);
+    if (rc) return rc;
+    if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j2: null pointer");
+    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j2: the result's H %d W %d must be multiples of 4", H, W);
+    const int tiles_h = (H + I2_TH - 1) / I2_TH, tiles_w = (W + I2_TW - 1) / I2_TW;
+    long blocks;
+    if ((rc = dt_blocks("dtcwt_inv_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
+    DtTapsI t = {};
+    dtcwt_ifilt_taps(g0b, g0a, m, 0, t.lo, t.dlo);                        // colifilt(X, g0b, g0a, False)
+    dtcwt_ifilt_taps(g1b, g1a, m, 1, t.hi, t.dhi);                        // colifilt(X, g1b, g1a, True)
+    hipLaunchKernelGGL(dtcwt_inv_j2, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
+                       DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H / 2, W / 2, tiles_h, tiles_w, m / 2, t);
+    return check_launch("dtcwt_inv_j2");
+}

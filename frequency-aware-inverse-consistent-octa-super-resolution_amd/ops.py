@@ -1348,6 +1348,245 @@ def swt_synthesis(coeffs, lo_h, hi_h, lo_w, hi_w):
     return _SWTSynthesis.apply(swt_bank(lo_h, hi_h, lo_w, hi_w), *coeffs)
 
 
+# ----------------------------------------------------------------------------------------
+# dual-tree complex wavelet transform (csrc/dtcwt.hip): one fused launch per level and direction
+# ----------------------------------------------------------------------------------------
+DTCWT_MAX_TAPS = 20                     # q-shift filters: even, 4..20; level-1 filters: odd, 3..19
+
+
+def dtcwt_layout(o_dim, ri_dim):
+    """The axis names ('n', 'c', 'h', 'w', 'o', 'r') of a bandpass tensor in the order ``o_dim`` / ``ri_dim`` put them, by the
+    reference's own rule (transform_funcs.py:10-29): both taken modulo 6, the orientations stacked into the (N, C, H, W) band at
+    ``o_dim`` (less one if ``ri_dim`` lies before it), then real and imaginary parts stacked at ``ri_dim``."""
+    if o_dim == ri_dim:
+        raise ValueError("Orientations and real/imaginary parts must be in different dimensions.")
+    o, r = int(o_dim) % 6, int(ri_dim) % 6
+    if r < o:
+        o -= 1
+    if o > 4:
+        raise ValueError("o_dim %d with ri_dim %d puts the orientations past the last axis of the 5-d band" % (o_dim, ri_dim))
+    names = ["n", "c", "h", "w"]
+    names.insert(o, "o")
+    names.insert(r, "r")
+    return tuple(names)
+
+
+def dtcwt_sizes(H, W, J):
+    """Per level j = 0 .. J-1: ((input rows, cols) after the module's padding, (lowpass rows, cols), (bandpass rows, cols))."""
+    out = []
+    h, w = H + H % 2, W + W % 2
+    out.append(((h, w), (h, w), (h // 2, w // 2)))
+    for _ in range(1, J):
+        h, w = (h if h % 4 == 0 else h + 2), (w if w % 4 == 0 else w + 2)
+        out.append(((h, w), (h // 2, w // 2), (h // 4, w // 4)))
+        h, w = h // 2, w // 2
+    return out
+
+
+def _dtcwt_taps1(f0, f1):
+    f0, f1 = host_taps(f0), host_taps(f1)
+    for f in (f0, f1):
+        if len(f) % 2 == 0 or not 3 <= len(f) < DTCWT_MAX_TAPS:
+            raise ValueError("filter length %d: the level-1 filters take an odd number of taps, 3 to %d" % (len(f), DTCWT_MAX_TAPS - 1))
+    return f0, f1
+
+
+def _dtcwt_taps2(fa0, fb0, fa1, fb1):
+    f = tuple(host_taps(t) for t in (fa0, fb0, fa1, fb1))
+    if len(set(len(t) for t in f)) != 1:
+        raise ValueError("the four q-shift filters must have the same length, got %s" % [len(t) for t in f])
+    if len(f[0]) % 2 or not 4 <= len(f[0]) <= DTCWT_MAX_TAPS:
+        raise ValueError("filter length %d: the q-shift filters take an even number of taps, 4 to %d" % (len(f[0]), DTCWT_MAX_TAPS))
+    return f
+
+
+def _dtcwt_dev(t, what):
+    if t.dtype != torch.float32:
+        raise ValueError("%s must be float32, got %s" % (what, t.dtype))
+    if not t.is_cuda:
+        raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+
+
+def _dtcwt_low(t):
+    """(tensor, n stride, c stride, row stride) of an (N, C, H, W) lowpass input with unit-stride columns, else of a copy."""
+    if t.stride(3) != 1 and t.shape[3] > 1:
+        t = t.contiguous()
+    s = t.stride()
+    return t, s[0], s[1], s[2]
+
+
+def _dtcwt_high_strides(h, names):
+    s = dict(zip(names, h.stride()))
+    st = tuple(s[k] for k in "ncohwr")
+    vec = int(st[5] == 1 and all(v % 2 == 0 for v in st[:5]) and h.data_ptr() % 8 == 0)
+    return st, vec
+
+
+def _dtcwt_check_high(h, names, rows, cols, N, C):
+    if h.dim() != 6:
+        raise ValueError("Bandpass inputs must have 6 dimensions, got %d" % h.dim())
+    size = dict(zip(names, h.shape))
+    if size["o"] != 6:
+        raise ValueError("Inverse transform must have input with 6 orientations, got %d" % size["o"])
+    if size["r"] != 2:
+        raise ValueError("Inputs must be complex with real and imaginary parts in the ri dimension, got size %d" % size["r"])
+    if rows is not None and (2 * size["h"], 2 * size["w"], size["n"], size["c"]) != (rows, cols, N, C):
+        raise ValueError("the lowpass (%d, %d, %d, %d) must be twice the bandpass (%d, %d, %d, %d) in rows and columns"
+                         % (N, C, rows, cols, size["n"], size["c"], size["h"], size["w"]))
+    return size
+
+
+def _dtcwt_forward(x, taps, level1, mode, names, want_ll=True, want_hi=True):
+    """One analysis launch.  ``level1``: taps = (f0, f1), 'same' filters, x even-sided; else taps = (h0a, h0b, h1a, h1b) and x a
+    multiple of 4 a side.  Returns (ll or None, highs or None)."""
+    if x.dim() != 4:
+        raise ValueError("the transform takes inputs of 4 dimensions (N, C, H, W), got %d" % x.dim())
+    N, C, H, W = x.shape
+    q = 2 if level1 else 4
+    if H % q or W % q or H < q or W < q:
+        raise ValueError("a level-%s input must have rows and columns that are a multiple of %d, got %d x %d" % ("1" if level1 else ">=2", q, H, W))
+    _dtcwt_dev(x, "the input")
+    x, sn, sc, sr = _dtcwt_low(x)
+    lh, lw = (H, W) if level1 else (H // 2, W // 2)
+    ll = torch.empty((N, C, lh, lw), dtype=torch.float32, device=x.device) if want_ll else None
+    hi, st, vec = None, (0,) * 6, 0
+    if want_hi:
+        size = {"n": N, "c": C, "o": 6, "h": lh // 2, "w": lw // 2, "r": 2}
+        hi = torch.empty(tuple(size[k] for k in names), dtype=torch.float32, device=x.device)
+        st, vec = _dtcwt_high_strides(hi, names)
+    if level1:
+        call("dtcwt_fwd_j1", x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, _tap_array(taps[0]), len(taps[0]),
+             _tap_array(taps[1]), len(taps[1]), mode, stream_ptr())
+    else:
+        call("dtcwt_fwd_j2", x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]),
+             stream_ptr())
+    return ll, hi
+
+
+def _dtcwt_inverse(ll, hi, taps, level1, mode, names):
+    """One synthesis launch; ``ll`` or ``hi`` may be None (zeros, not computed)."""
+    if ll is None and hi is None:
+        raise ValueError("the lowpass and the bandpass cannot both be missing")
+    if ll is not None:
+        if ll.dim() != 4:
+            raise ValueError("the lowpass takes 4 dimensions (N, C, H, W), got %d" % ll.dim())
+        N, C, R, Q = ll.shape
+        if R % 2 or Q % 2 or R < 2 or Q < 2:
+            raise ValueError("a lowpass must have rows and columns that are a multiple of 2, got %d x %d" % (R, Q))
+        if hi is not None:
+            _dtcwt_check_high(hi, names, R, Q, N, C)
+    else:
+        size = _dtcwt_check_high(hi, names, None, None, None, None)
+        N, C, R, Q = size["n"], size["c"], 2 * size["h"], 2 * size["w"]
+    for t, what in ((ll, "the lowpass"), (hi, "the bandpass")):
+        if t is not None:
+            _dtcwt_dev(t, what)
+    dev = (ll if ll is not None else hi).device
+    sn = sc = sr = 0
+    if ll is not None:
+        ll, sn, sc, sr = _dtcwt_low(ll)
+    st = _dtcwt_high_strides(hi, names)[0] if hi is not None else (0,) * 6
+    H, W = (R, Q) if level1 else (2 * R, 2 * Q)
+    y = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
+    lp, hp = (ll.data_ptr() if ll is not None else None), (hi.data_ptr() if hi is not None else None)
+    if level1:
+        call("dtcwt_inv_j1", lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, _tap_array(taps[0]), len(taps[0]), _tap_array(taps[1]),
+             len(taps[1]), mode, stream_ptr())
+    else:
+        call("dtcwt_inv_j2", lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+    return y
+
+
+def _swap_ab(t):
+    return (t[1], t[0], t[3], t[2])
+
+
+class _DTCWTFwd(Function):
+    """One analysis level: ``apply(x, taps, level1, skip_hps, names, mode) -> (ll, highs)``; a skipped bandpass is a 0-d zero, as in
+    the reference.  The backward is the reference's: the matching inverse on the same (analysis) taps, a and b swapped at levels
+    >= 2 -- the exact adjoint.  A cotangent nothing depends on goes to the kernel as a null pointer."""
+
+    @staticmethod
+    def forward(ctx, x, taps, level1, skip_hps, names, mode):
+        ctx.cfg = (taps if level1 else _swap_ab(taps), level1, mode, names)
+        ctx.set_materialize_grads(False)
+        ll, hi = _dtcwt_forward(x, taps, level1, mode, names, want_hi=not skip_hps)
+        if skip_hps:
+            hi = ll.new_zeros([])
+            ctx.mark_non_differentiable(hi)
+        return ll, hi
+
+    @staticmethod
+    def backward(ctx, dl, dh):
+        taps, level1, mode, names = ctx.cfg
+        if dh is not None and dh.dim() == 0:
+            dh = None
+        if dl is None and dh is None:
+            return (None,) * 6
+        return (_dtcwt_inverse(dl, dh, taps, level1, mode, names),) + (None,) * 5
+
+
+class _DTCWTFwdJ1(_DTCWTFwd):
+    """transform_funcs.py:343-374 FWD_J1 on csrc/dtcwt.hip (``level1`` = True)."""
+
+
+class _DTCWTFwdJ2(_DTCWTFwd):
+    """transform_funcs.py:377-413 FWD_J2PLUS (``level1`` = False; always the symmetric extension)."""
+
+
+class _DTCWTInv(Function):
+    """One synthesis level: ``apply(ll, highs, taps, level1, names, mode) -> y``; ``ll`` or ``highs`` may be None.  The backward is
+    the matching forward on the same (synthesis) taps, a and b swapped at levels >= 2, and computes only the gradients asked for."""
+
+    @staticmethod
+    def forward(ctx, ll, hi, taps, level1, names, mode):
+        ctx.cfg = (taps if level1 else _swap_ab(taps), level1, mode, names)
+        return _dtcwt_inverse(ll, hi, taps, level1, mode, names)
+
+    @staticmethod
+    def backward(ctx, dy):
+        taps, level1, mode, names = ctx.cfg
+        want_ll, want_hi = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_ll or want_hi):
+            return (None,) * 6
+        dl, dh = _dtcwt_forward(dy, taps, level1, mode, names, want_ll=want_ll, want_hi=want_hi)
+        return (dl, dh) + (None,) * 4
+
+
+class _DTCWTInvJ1(_DTCWTInv):
+    """transform_funcs.py:416-449 INV_J1."""
+
+
+class _DTCWTInvJ2(_DTCWTInv):
+    """transform_funcs.py:452-488 INV_J2PLUS."""
+
+
+def dtcwt_fwd_j1(x, h0o, h1o, skip_hps=False, o_dim=2, ri_dim=-1, mode=1):
+    """Level 1 of the forward transform: x (N, C, H, W), H and W even -> (ll (N, C, H, W), highs in the ``o_dim`` / ``ri_dim`` layout,
+    default (N, C, 6, H/2, W/2, 2)).  The filters are tensors or sequences as the modules register them (taps reversed).
+    ``mode`` 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code pads with zeros, as the reference does."""
+    names = dtcwt_layout(o_dim, ri_dim)
+    return _DTCWTFwdJ1.apply(x, _dtcwt_taps1(h0o, h1o), True, bool(skip_hps), names, int(mode))
+
+
+def dtcwt_fwd_j2(x, h0a, h0b, h1a, h1b, skip_hps=False, o_dim=2, ri_dim=-1):
+    """A level >= 2 of the forward transform: x (N, C, H, W), multiples of 4 -> (ll (N, C, H/2, W/2), highs (.., H/4, W/4, ..))."""
+    names = dtcwt_layout(o_dim, ri_dim)
+    return _DTCWTFwdJ2.apply(x, _dtcwt_taps2(h0a, h0b, h1a, h1b), False, bool(skip_hps), names, 1)
+
+
+def dtcwt_inv_j1(ll, highs, g0o, g1o, o_dim=2, ri_dim=-1, mode=1):
+    """Level 1 of the inverse: ll (N, C, H, W) and highs (.., H/2, W/2, ..) -> y (N, C, H, W); either may be None for zeros."""
+    names = dtcwt_layout(o_dim, ri_dim)
+    return _DTCWTInvJ1.apply(ll, highs, _dtcwt_taps1(g0o, g1o), True, names, int(mode))
+
+
+def dtcwt_inv_j2(ll, highs, g0a, g0b, g1a, g1b, o_dim=2, ri_dim=-1):
+    """A level >= 2 of the inverse: ll (N, C, R, Q) and highs (.., R/2, Q/2, ..) -> y (N, C, 2R, 2Q); either may be None."""
+    names = dtcwt_layout(o_dim, ri_dim)
+    return _DTCWTInvJ2.apply(ll, highs, _dtcwt_taps2(g0a, g0b, g1a, g1b), False, names, 1)
+
+
 class _HaarDFront(Function):
     @staticmethod
     def forward(ctx, x, mode):

@@ -447,3 +447,171 @@ class SWTInverse(_TapModule):
         _prime(self, self._tap_names)
         g = [ops.host_taps(getattr(self, n)) for n in self._tap_names]
         return ops.swt_synthesis(list(coeffs), g[0], g[1], g[2], g[3])
+
+
+# ----------------------------------------------------------------------------------------
+# the dual-tree complex wavelet transform: dtcwt/transform2d.py:20-254, transform_funcs.py -> csrc/dtcwt.hip
+# ----------------------------------------------------------------------------------------
+_DTCWT_PROVIDERS = ("pytorch_wavelets.dtcwt.coeffs", "dtcwt.coeffs")
+#: the two level-1 banks with closed rational forms (Kingsbury's LeGall 5,3 and near-symmetric 5,7 pairs): (h0o, g0o, h1o, g1o)
+_BIORT_CLOSED = {
+    "legall": (([-1, 2, 6, 2, -1], 8), ([1, 2, 1], 4), ([-1, 2, -1], 4), ([-1, -2, 6, -2, -1], 8)),
+    "near_sym_a": (([-1, 5, 12, 5, -1], 20), ([-3, -15, 73, 170, 73, -15, -3], 280), ([3, -15, -73, 170, -73, -15, 3], 280),
+                   ([-1, -5, 12, -5, -1], 20)),
+}
+
+
+def _dtcwt_provider(kind, name):
+    import importlib
+    for mod in _DTCWT_PROVIDERS:
+        try:
+            fn = getattr(importlib.import_module(mod), kind)
+        except (ImportError, AttributeError):
+            continue
+        return tuple(np.asarray(v, dtype=np.float64).ravel() for v in fn(name))
+    form = "a 2-tuple (h0o, h1o) -- (g0o, g1o) for the inverse" if kind == "biort" else \
+        "a 4-tuple (h0a, h0b, h1a, h1b) -- (g0a, g0b, g1a, g1b) for the inverse"
+    raise NotImplementedError("the %s name %r is not resolved: the tap tables are data of the dtcwt / pytorch_wavelets packages and not "
+                              "part of this one (only 'legall' and 'near_sym_a' are built here, from their closed forms), and neither "
+                              "%s is importable.  Pass the taps instead: %s of tap sequences"
+                              % (kind, name, " nor ".join(_DTCWT_PROVIDERS), form))
+
+
+def dtcwt_biort(name):
+    """(h0o, g0o, h1o, g1o) of a level-1 bank, the reference's ``coeffs.biort`` order, as float64 arrays."""
+    if name in _BIORT_CLOSED:
+        return tuple(np.asarray(num, dtype=np.float64) / den for num, den in _BIORT_CLOSED[name])
+    return _dtcwt_provider("biort", name)[:4]
+
+
+def dtcwt_qshift(name):
+    """(h0a, h0b, g0a, g0b, h1a, h1b, g1a, g1b) of a q-shift bank, the reference's ``coeffs.qshift`` order; provider only."""
+    return _dtcwt_provider("qshift", name)[:8]
+
+
+def _dtcwt_taps(biort, qshift, analysis):
+    if isinstance(biort, str):
+        b = dtcwt_biort(biort)
+        biort = (b[0], b[2]) if analysis else (b[1], b[3])
+    elif len(biort) != 2:
+        raise ValueError("biort must be a name or a 2-tuple of tap sequences (lowpass, highpass); got %d sequences" % len(biort))
+    if isinstance(qshift, str):
+        q = dtcwt_qshift(qshift)
+        qshift = (q[0], q[1], q[4], q[5]) if analysis else (q[2], q[3], q[6], q[7])
+    elif len(qshift) != 4:
+        raise ValueError("qshift must be a name or a 4-tuple of tap sequences (tree a low, tree b low, tree a high, tree b high); got %d "
+                         "sequences" % len(qshift))
+    taps = [np.asarray(torch.as_tensor(t).detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64).ravel()
+            for t in tuple(biort) + tuple(qshift)]
+    ops._dtcwt_taps1(taps[0], taps[1])
+    ops._dtcwt_taps2(*taps[2:])
+    return taps
+
+
+def _register_dtcwt(module, taps):
+    """prep_filt (dtcwt/lowlevel.py:58-67): shape (1, 1, L, 1), the taps reversed."""
+    for name, t in zip(module._tap_names, taps):
+        module.register_buffer(name, torch.tensor(np.ascontiguousarray(t[::-1]), dtype=torch.get_default_dtype()).reshape(1, 1, -1, 1))
+    _record(module, module._tap_names)
+
+
+def _per_level(value, J, what):
+    if isinstance(value, (list, tuple, np.ndarray)):
+        if len(value) != J:
+            raise ValueError("%s lists one entry per level: %d entries for J = %d" % (what, len(value), J))
+        return [bool(v) for v in value]
+    return [bool(value)] * J
+
+
+def _missing(t):
+    return t is None or t.dim() == 0 or t.numel() == 0
+
+
+class DTCWTForward(_TapModule):
+    """dtcwt/transform2d.py:20-147.  forward(x) -> (yl, yh) for x of shape (N, C, H, W): yh[j] the six complex bandpass orientations
+    (15, 45, 75, 105, 135, 165 degrees) of level j, shape (N, C, 6, H_j, W_j, 2) or as ``o_dim`` / ``ri_dim`` place the orientation
+    and real/imaginary axes; yl the last lowpass (twice the last bandpass a side), or with ``include_scale`` the list of every
+    level's lowpass (a 0-d zero where not asked for).  A level in ``skip_hps`` computes its lowpass only and returns a 0-d zero.
+    ``biort``: 'legall' or 'near_sym_a' (built from their closed forms), another name if ``pytorch_wavelets.dtcwt.coeffs`` or
+    ``dtcwt.coeffs`` is importable, or a 2-tuple (h0o, h1o) of odd length 3..19; ``qshift``: a provider's name or a 4-tuple
+    (h0a, h0b, h1a, h1b) of one even length 4..``ops.DTCWT_MAX_TAPS``.  ``mode`` acts on level 1 only: 'symmetric', or zero padding
+    for any other name; the later levels always extend symmetrically.  An odd side has its last row / column repeated; a lowpass
+    side that is no multiple of 4 has its first and last row / column repeated before the next level (torch ops outside the
+    kernels -- the sizes 192, 256, 512 never take them up to J = 3).  Otherwise a forward is J launches of csrc/dtcwt.hip."""
+
+    _tap_names = ("h0o", "h1o", "h0a", "h0b", "h1a", "h1b")
+
+    def __init__(self, biort="near_sym_a", qshift="qshift_a", J=3, skip_hps=False, include_scale=False, o_dim=2, ri_dim=-1,
+                 mode="symmetric"):
+        super().__init__()
+        if o_dim == ri_dim:
+            raise ValueError("Orientations and real/imaginary parts must be in different dimensions.")
+        ops.dtcwt_layout(o_dim, ri_dim)
+        self.biort, self.qshift, self.J, self.o_dim, self.ri_dim, self.mode = biort, qshift, J, o_dim, ri_dim, mode
+        _register_dtcwt(self, _dtcwt_taps(biort, qshift, analysis=True))
+        self.skip_hps = _per_level(skip_hps, J, "skip_hps")
+        self.include_scale = _per_level(include_scale, J, "include_scale")
+
+    def forward(self, x):
+        if self.J == 0:
+            return x, None
+        if x.dim() != 4:
+            raise ValueError("the transform takes inputs of 4 dimensions (N, C, H, W), got %d" % x.dim())
+        mode = mode_to_int(self.mode)
+        _prime(self, self._tap_names)
+        if x.shape[2] % 2:
+            x = torch.cat((x, x[:, :, -1:]), dim=2)
+        if x.shape[3] % 2:
+            x = torch.cat((x, x[:, :, :, -1:]), dim=3)
+        low, h = ops.dtcwt_fwd_j1(x, self.h0o, self.h1o, self.skip_hps[0], self.o_dim, self.ri_dim, mode)
+        highs, scales = [h], [low if self.include_scale[0] else None]
+        for j in range(1, self.J):
+            if low.shape[2] % 4:
+                low = torch.cat((low[:, :, 0:1], low, low[:, :, -1:]), dim=2)
+            if low.shape[3] % 4:
+                low = torch.cat((low[:, :, :, 0:1], low, low[:, :, :, -1:]), dim=3)
+            low, h = ops.dtcwt_fwd_j2(low, self.h0a, self.h0b, self.h1a, self.h1b, self.skip_hps[j], self.o_dim, self.ri_dim)
+            highs.append(h)
+            scales.append(low if self.include_scale[j] else None)
+        if True in self.include_scale:
+            return [s if s is not None else x.new_zeros([]) for s in scales], highs
+        return low, highs
+
+
+class DTCWTInverse(_TapModule):
+    """dtcwt/transform2d.py:150-254.  forward((yl, yh)) -> x.  ``None``, a 0-d or an empty tensor for a bandpass level -- or for the
+    lowpass, where the coarsest bandpass is given -- stands for zeros and costs nothing: its path is not computed.  A lowpass that
+    is not twice its level's bandpass loses its first and last row / column (the forward's pad).  The bandpass tensors are read
+    in place through their strides, whatever ``o_dim`` / ``ri_dim`` and whatever view.  Unlike the reference, a missing level-1
+    bandpass keeps ``mode`` (the reference then extends symmetrically even for 'zero')."""
+
+    _tap_names = ("g0o", "g1o", "g0a", "g0b", "g1a", "g1b")
+
+    def __init__(self, biort="near_sym_a", qshift="qshift_a", o_dim=2, ri_dim=-1, mode="symmetric"):
+        super().__init__()
+        if o_dim == ri_dim:
+            raise ValueError("Orientations and real/imaginary parts must be in different dimensions.")
+        self._names = ops.dtcwt_layout(o_dim, ri_dim)
+        self.biort, self.qshift, self.o_dim, self.ri_dim, self.mode = biort, qshift, o_dim, ri_dim, mode
+        _register_dtcwt(self, _dtcwt_taps(biort, qshift, analysis=False))
+
+    def _fit(self, low, h):
+        if _missing(low) or _missing(h) or h.dim() != 6:
+            return low
+        size = dict(zip(self._names, h.shape))
+        if low.shape[2] != 2 * size["h"]:
+            low = low[:, :, 1:-1]
+        if low.shape[3] != 2 * size["w"]:
+            low = low[:, :, :, 1:-1]
+        return low
+
+    def forward(self, coeffs):
+        low, highs = coeffs
+        mode = mode_to_int(self.mode)
+        _prime(self, self._tap_names)
+        low = None if _missing(low) else low
+        for h in list(highs)[:0:-1]:
+            h = None if _missing(h) else h
+            low = ops.dtcwt_inv_j2(self._fit(low, h), h, self.g0a, self.g0b, self.g1a, self.g1b, self.o_dim, self.ri_dim)
+        h = None if _missing(highs[0]) else highs[0]
+        return ops.dtcwt_inv_j1(self._fit(low, h), h, self.g0o, self.g1o, self.o_dim, self.ri_dim, mode)

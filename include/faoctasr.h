@@ -352,6 +352,40 @@ int faoctasr_swt2d_adjoint(const float* c, float* dx, long dx_plane_stride, cons
                            const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w, int dilation, int mode,
                            float scale, faoctasr_stream_t stream);
 
+/* ---- dual-tree complex wavelet transform, one level per call (csrc/dtcwt.hip) --------------------
+ * pytorch_wavelets dtcwt/transform_funcs.py (fwd_j1, fwd_j2plus, inv_j1, inv_j2plus), dtcwt/lowlevel.py.  The taps are HOST
+ * pointers, read during the call and passed to the kernel by value (the launch is capturable), in the order the modules register
+ * them (prep_filt: the taps reversed).  Level 1: a lowpass of L0 and a highpass of L1 taps, each odd and 3..19; mode 1 is the
+ * symmetric extension, every other mode pads with zeros.  Levels >= 2: the four q-shift filters of one even length m, 4..20,
+ * always symmetric.  Operands of N x C planes.  The lowpass INPUT of a call is strided: plane (n, c) starts n * sn + c * sc
+ * elements in, rows are sr elements apart, columns contiguous.  The bandpass tensor -- six complex orientations (15, 45, 75,
+ * 105, 135, 165 degrees) of half the lowpass resolution -- is addressed through the element strides of its n, c, orientation,
+ * row, column and re/im axes, so any layout or view is read and written in place; hi_vec2 = 1 (only where hi_si == 1, every
+ * other stride is even and the base is 8-byte aligned) stores each (re, im) pair as one 8-byte word.  Outputs ll and y are
+ * contiguous.  FAOCTASR_EINVAL for a tap count, size or null pointer outside these.
+ * fwd_j1: x [H, W], H and W even -> ll [H, W] and hi [H/2, W/2]; either output may be NULL (not computed / not stored).  Also the
+ *   backward of inv_j1 (on the synthesis taps).
+ * fwd_j2: x [H, W], multiples of 4 -> ll [H/2, W/2], hi [H/4, W/4]; either may be NULL.  Also the backward of inv_j2 (on the
+ *   synthesis taps with a and b swapped).
+ * inv_j1: ll [H, W], hi [H/2, W/2] -> y [H, W]; ll or hi may be NULL (zeros; its path is not computed).  Also the backward of
+ *   fwd_j1 (on the analysis taps).
+ * inv_j2: ll [H/2, W/2], hi [H/4, W/4] -> y [H, W], multiples of 4; ll or hi may be NULL.  Also the backward of fwd_j2 (on the
+ *   analysis taps with a and b swapped). */
+int faoctasr_dtcwt_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                          long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
+                          const float* h0, int L0, const float* h1, int L1, int mode, faoctasr_stream_t stream);
+int faoctasr_dtcwt_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                          long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
+                          const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
+                          faoctasr_stream_t stream);
+int faoctasr_dtcwt_inv_j1(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                          long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
+                          const float* g0, int L0, const float* g1, int L1, int mode, faoctasr_stream_t stream);
+int faoctasr_dtcwt_inv_j2(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                          long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
+                          const float* g0a, const float* g0b, const float* g1a, const float* g1b, int m,
+                          faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
