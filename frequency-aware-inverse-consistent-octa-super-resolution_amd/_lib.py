@@ -75,6 +75,10 @@ _SIG = {
     "dtcwt_fwd_j2": (_I, "p lll pp llllll i l iii pppp i p"),
     "dtcwt_inv_j1": (_I, "p lll p llllll p l iii pi pi i p"),
     "dtcwt_inv_j2": (_I, "p lll p llllll p l iii pppp i p"),
+    "scat_fwd_j1": (_I, "p lll p ll i p lll p i ff l iii pi pi i p"),
+    "scat_fwd_j2": (_I, "p lll p ll p lll p i ff l iii pppp i p"),
+    "scat_bwd_j1": (_I, "p ll i p lll p p l iii pi pi i p"),
+    "scat_bwd_j2": (_I, "p ll p lll p p l iii pppp i p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -1587,6 +1587,188 @@ def dtcwt_inv_j2(ll, highs, g0a, g0b, g1a, g1b, o_dim=2, ri_dim=-1):
     return _DTCWTInvJ2.apply(ll, highs, _dtcwt_taps2(g0a, g0b, g1a, g1b), False, names, 1)
 
 
+# ----------------------------------------------------------------------------------------
+# DTCWT scattering layers (csrc/scat.hip): a dual-tree level, smoothed magnitudes and the pooled lowpass in one launch
+# ----------------------------------------------------------------------------------------
+def scat_sizes(H, W, order):
+    """((padded input rows, cols), (output rows, cols)) of ``ScatLayer`` (order 1: even sides, a half) and ``ScatLayerj2`` (order 2:
+    multiples of 8, a quarter)."""
+    q = 2 if order == 1 else 8
+    h, w = H + (-H) % q, W + (-W) % q
+    return (h, w), ((h // 2, w // 2) if order == 1 else (h // 4, w // 4))
+
+
+def _scat_check(x, taps2, mode, combine_colour):
+    """Every refusal of a scattering layer, the device check last; returns (N, C, H, W)."""
+    if x.dim() != 4:
+        raise ValueError("a scattering layer takes inputs of 4 dimensions (N, C, H, W), got %d" % x.dim())
+    N, C, H, W = x.shape
+    if N < 1 or C < 1:
+        raise ValueError("a scattering layer takes at least one image and one channel, got N %d C %d" % (N, C))
+    if combine_colour and C != 3:
+        raise ValueError("combine_colour takes 3 channels, got %d" % C)
+    q = 2 if taps2 is None else 8
+    if H % q or W % q or H < q or W < q:
+        raise ValueError("the input of a %s-order scattering layer must have rows and columns that are a multiple of %d, got %d x %d"
+                         % ("first" if taps2 is None else "second", q, H, W))
+    if not 0 <= mode <= 6:
+        raise ValueError("Unkown pad type: {}".format(mode))
+    if taps2 is not None and mode != 1:
+        raise NotImplementedError("the q-shift level of ScatLayerj2 extends symmetrically only (mode 1), got mode %d" % mode)
+    _dtcwt_dev(x, "the input")
+    return N, C, H, W
+
+
+def _scat_low(t):
+    """(pointer, n stride, c stride) of an (N, C, h, w) view with contiguous rows."""
+    if t.shape[3] > 1 and t.stride(3) != 1 or t.shape[2] > 1 and t.stride(2) != t.shape[3]:
+        raise _lib.KernelError("a scattering lowpass operand must have contiguous rows, got strides %s" % (t.stride(),))
+    return t.data_ptr(), t.stride(0), t.stride(1)
+
+
+def _scat_mag(t, colour):
+    """(pointer, n, orientation and c strides) of an (N, 6, C, h, w) view with contiguous rows; the colour form has no c axis."""
+    if t.shape[4] > 1 and t.stride(4) != 1 or t.shape[3] > 1 and t.stride(3) != t.shape[4] or t.shape[1] != 6:
+        raise _lib.KernelError("a scattering magnitude operand must have 6 orientations and contiguous rows, got %s strides %s"
+                               % (tuple(t.shape), t.stride()))
+    return t.data_ptr(), t.stride(0), t.stride(1), (0 if colour else t.stride(2))
+
+
+def _scat_fwd(x, taps, level1, mode, bias, low, pool, mag, phase, colour):
+    """One forward launch: x (N, C, H, W) -> the views ``low`` (N, C, ., .), ``mag`` (N, 6, C or 1, ., .) and ``phase`` (or None)."""
+    N, C, H, W = x.shape
+    x, sn, sc, sr = _dtcwt_low(x)
+    b = float(bias)
+    if level1:
+        call("scat_fwd_j1", x.data_ptr(), sn, sc, sr, *_scat_low(low), int(pool), *_scat_mag(mag, colour), ptr(phase), int(colour), b, b * b,
+             N, C, H, W, _tap_array(taps[0]), len(taps[0]), _tap_array(taps[1]), len(taps[1]), mode, stream_ptr())
+    else:
+        call("scat_fwd_j2", x.data_ptr(), sn, sc, sr, *_scat_low(low), *_scat_mag(mag, colour), ptr(phase), int(colour), b, b * b,
+             N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+
+
+def _scat_bwd(dlow, pool, dmag, phase, taps, level1, mode, colour, shape):
+    """One backward launch on the forward's taps: the cotangent views and the phasors -> dx of ``shape`` (N, C, H, W)."""
+    N, C, H, W = shape
+    dx = torch.empty(shape, dtype=torch.float32, device=phase.device)
+    if level1:
+        call("scat_bwd_j1", *_scat_low(dlow), int(pool), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W, _tap_array(taps[0]),
+             len(taps[0]), _tap_array(taps[1]), len(taps[1]), mode, stream_ptr())
+    else:
+        call("scat_bwd_j2", *_scat_low(dlow), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W, *(_tap_array(t) for t in taps),
+             len(taps[0]), stream_ptr())
+    return dx
+
+
+def _scat_phase(x, C, h, w, save):
+    return torch.empty((x.shape[0], 6, C, h, w, 2), dtype=torch.float32, device=x.device) if save else None
+
+
+class _ScatJ1(Function):
+    """scatternet/lowlevel.py:71-137 ScatLayerj1_f on csrc/scat.hip: ``apply(x, taps, mode, bias, colour, save) -> Z`` of shape
+    (N, 7, C, H/2, W/2), or (N, 9, H/2, W/2) with ``colour``; one launch, and one for the backward.  ``save`` False stores no
+    phasors (the reference's ``x.requires_grad == False`` branch)."""
+
+    @staticmethod
+    def forward(ctx, x, taps, mode, bias, colour, save):
+        N, C, H, W = x.shape
+        h, w = H // 2, W // 2
+        phase = _scat_phase(x, C, h, w, save)
+        if colour:
+            Z = torch.empty((N, 9, h, w), dtype=torch.float32, device=x.device)
+            low, mag = Z[:, :3], Z[:, 3:].unsqueeze(2)
+        else:
+            Z = torch.empty((N, 7, C, h, w), dtype=torch.float32, device=x.device)
+            low, mag = Z[:, 0], Z[:, 1:]
+        _scat_fwd(x, taps, True, mode, bias, low, True, mag, phase, colour)
+        ctx.cfg = (taps, mode, colour, tuple(x.shape))
+        if save:
+            ctx.save_for_backward(phase)
+        return Z
+
+    @staticmethod
+    def backward(ctx, dZ):
+        taps, mode, colour, shape = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        if not ctx.saved_tensors:
+            raise _lib.KernelError("the scattering layer's forward ran without gradients enabled: no phasors were saved")
+        phase, = ctx.saved_tensors
+        dZ = dZ.contiguous()
+        dlow, dmag = (dZ[:, :3], dZ[:, 3:].unsqueeze(2)) if colour else (dZ[:, 0], dZ[:, 1:])
+        return (_scat_bwd(dlow, True, dmag, phase, taps, True, mode, colour, shape),) + (None,) * 5
+
+
+class _ScatJ2(Function):
+    """scatternet/lowlevel.py:206-398 ScatLayerj2_f: ``apply(x, taps1, taps2, mode, bias, colour, save) -> Z`` of shape
+    (N, 49, C, H/4, W/4), or (N, 51, H/4, W/4) with ``colour``.  Three launches write Z in place -- level 1 on x (unpooled lowpass
+    s0 and first-order magnitudes, two temporaries), level 2 on s0, level 1 on the 6C (colour: 6) magnitude channels -- and the
+    backward is the three adjoints in reverse."""
+
+    @staticmethod
+    def forward(ctx, x, taps1, taps2, mode, bias, colour, save):
+        N, C, H, W = x.shape
+        h2, w2, h4, w4 = H // 2, W // 2, H // 4, W // 4
+        dev = x.device
+        C1 = 1 if colour else C                                        # channels of a first-order magnitude
+        s0 = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
+        m1 = torch.empty((N, 6, C1, h2, w2), dtype=torch.float32, device=dev)
+        ph1, ph2, ph21 = _scat_phase(x, C, h2, w2, save), _scat_phase(x, C, h4, w4, save), _scat_phase(x, 6 * C1, h4, w4, save)
+        if colour:
+            Z = torch.empty((N, 51, h4, w4), dtype=torch.float32, device=dev)
+            z_s0, z_s1j1, z_s1j2, z_s2 = Z[:, :3], Z[:, 3:9], Z[:, 9:15].unsqueeze(2), Z[:, 15:].view(N, 6, 6, h4, w4)
+        else:
+            Z = torch.empty((N, 49, C, h4, w4), dtype=torch.float32, device=dev)
+            z_s0, z_s1j1, z_s1j2, z_s2 = Z[:, 0], Z[:, 1:7].view(N, 6 * C, h4, w4), Z[:, 7:13], Z[:, 13:].view(N, 6, 6 * C, h4, w4)
+        _scat_fwd(x, taps1, True, mode, bias, s0, False, m1, ph1, colour)
+        _scat_fwd(s0, taps2, False, 1, bias, z_s0, True, z_s1j2, ph2, colour)
+        _scat_fwd(m1.view(N, 6 * C1, h2, w2), taps1, True, mode, bias, z_s1j1, True, z_s2, ph21, False)
+        ctx.cfg = (taps1, taps2, mode, colour, tuple(x.shape))
+        if save:
+            ctx.save_for_backward(ph1, ph2, ph21)
+        return Z
+
+    @staticmethod
+    def backward(ctx, dZ):
+        taps1, taps2, mode, colour, shape = ctx.cfg
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        if not ctx.saved_tensors:
+            raise _lib.KernelError("the scattering layer's forward ran without gradients enabled: no phasors were saved")
+        ph1, ph2, ph21 = ctx.saved_tensors
+        N, C, H, W = shape
+        h2, w2, h4, w4 = H // 2, W // 2, H // 4, W // 4
+        C1 = 1 if colour else C
+        dZ = dZ.contiguous()
+        if colour:
+            d_s0, d_s1j1, d_s1j2, d_s2 = dZ[:, :3], dZ[:, 3:9], dZ[:, 9:15].unsqueeze(2), dZ[:, 15:].view(N, 6, 6, h4, w4)
+        else:
+            d_s0, d_s1j1, d_s1j2, d_s2 = dZ[:, 0], dZ[:, 1:7].view(N, 6 * C, h4, w4), dZ[:, 7:13], dZ[:, 13:].view(N, 6, 6 * C, h4, w4)
+        dm1 = _scat_bwd(d_s1j1, True, d_s2, ph21, taps1, True, mode, False, (N, 6 * C1, h2, w2))
+        ds0 = _scat_bwd(d_s0, True, d_s1j2, ph2, taps2, False, 1, colour, (N, C, H, W))
+        dx = _scat_bwd(ds0, False, dm1.view(N, 6, C1, h2, w2), ph1, taps1, True, mode, colour, (N, C, H, W))
+        return (dx,) + (None,) * 6
+
+
+def scat_layer_j1(x, h0o, h1o, mode=1, magbias=1e-2, combine_colour=False):
+    """One order of scattering at one scale: x (N, C, H, W), H and W even -> Z (N, 7, C, H/2, W/2): the 2x2 mean of the level-1
+    lowpass, then ``sqrt(re^2 + im^2 + magbias^2) - magbias`` of the six orientations; with ``combine_colour`` (C == 3) the
+    magnitude runs over the three channels too and Z is (N, 9, H/2, W/2).  Filters as the modules register them (taps reversed);
+    ``mode`` 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code pads with zeros."""
+    taps = _dtcwt_taps1(h0o, h1o)
+    _scat_check(x, None, int(mode), combine_colour)
+    return _ScatJ1.apply(x, taps, int(mode), float(magbias), bool(combine_colour), torch.is_grad_enabled() and x.requires_grad)
+
+
+def scat_layer_j2(x, h0o, h1o, h0a, h0b, h1a, h1b, mode=1, magbias=1e-2, combine_colour=False):
+    """Second-order scattering over two scales: x (N, C, H, W), multiples of 8 -> Z (N, 49, C, H/4, W/4): the lowpass, the six
+    first-order magnitudes of level 1 (pooled) and of level 2, and the 36 second-order ones (index 6 o2 + o1); with
+    ``combine_colour`` (N, 51, H/4, W/4) = 3 + 6 + 6 + 36.  Only ``mode`` 1 (symmetric), as in the reference."""
+    taps1, taps2 = _dtcwt_taps1(h0o, h1o), _dtcwt_taps2(h0a, h0b, h1a, h1b)
+    _scat_check(x, taps2, int(mode), combine_colour)
+    return _ScatJ2.apply(x, taps1, taps2, int(mode), float(magbias), bool(combine_colour), torch.is_grad_enabled() and x.requires_grad)
+
+
 class _HaarDFront(Function):
     @staticmethod
     def forward(ctx, x, mode):

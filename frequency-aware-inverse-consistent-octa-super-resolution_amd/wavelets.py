@@ -495,7 +495,9 @@ def _dtcwt_taps(biort, qshift, analysis):
         biort = (b[0], b[2]) if analysis else (b[1], b[3])
     elif len(biort) != 2:
         raise ValueError("biort must be a name or a 2-tuple of tap sequences (lowpass, highpass); got %d sequences" % len(biort))
-    if isinstance(qshift, str):
+    if qshift is None:                      # a level-1 bank alone (ScatLayer)
+        qshift = ()
+    elif isinstance(qshift, str):
         q = dtcwt_qshift(qshift)
         qshift = (q[0], q[1], q[4], q[5]) if analysis else (q[2], q[3], q[6], q[7])
     elif len(qshift) != 4:
@@ -504,7 +506,8 @@ def _dtcwt_taps(biort, qshift, analysis):
     taps = [np.asarray(torch.as_tensor(t).detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64).ravel()
             for t in tuple(biort) + tuple(qshift)]
     ops._dtcwt_taps1(taps[0], taps[1])
-    ops._dtcwt_taps2(*taps[2:])
+    if qshift:
+        ops._dtcwt_taps2(*taps[2:])
     return taps
 
 
@@ -615,3 +618,93 @@ class DTCWTInverse(_TapModule):
             low = ops.dtcwt_inv_j2(self._fit(low, h), h, self.g0a, self.g0b, self.g1a, self.g1b, self.o_dim, self.ri_dim)
         h = None if _missing(highs[0]) else highs[0]
         return ops.dtcwt_inv_j1(self._fit(low, h), h, self.g0o, self.g1o, self.o_dim, self.ri_dim, mode)
+
+
+# ----------------------------------------------------------------------------------------
+# DTCWT scattering layers: scatternet/layers.py -> csrc/scat.hip
+# ----------------------------------------------------------------------------------------
+def _register_scat(module, taps):
+    """prep_filt as ``_register_dtcwt``, but as the reference's scattering layers hold their taps: frozen parameters."""
+    for name, t in zip(module._tap_names, taps):
+        t = torch.tensor(np.ascontiguousarray(t[::-1]), dtype=torch.get_default_dtype()).reshape(1, 1, -1, 1)
+        setattr(module, name, nn.Parameter(t, requires_grad=False))
+    _record(module, module._tap_names)
+
+
+def _scat_taps(biort, qshift):
+    for name in (biort, qshift):
+        if isinstance(name, str) and name.endswith("_bp"):
+            raise NotImplementedError("%r: the rotationally symmetric three-filter variants (near_sym_b_bp / qshift_b_bp) need a third "
+                                      "filter path in every kernel of csrc/scat.hip and are not built" % name)
+    return _dtcwt_taps(biort, qshift, analysis=True)
+
+
+class ScatLayer(_TapModule):
+    """scatternet/layers.py:11-79.  One order of scattering at one scale: forward(x) for x of shape (N, C, H, W) returns
+    (N, 7C, H/2, W/2) -- the C lowpass channels (the level-1 lowpass averaged 2x2), then for each of the six orientations the C
+    magnitudes ``sqrt(re^2 + im^2 + magbias^2) - magbias``.  ``combine_colour`` (C == 3): the magnitude runs over the three channels
+    as well, (N, 9, H/2, W/2).  ``biort`` as ``DTCWTForward`` takes it; ``mode`` 'symmetric', or zero padding for any other name.  An
+    odd side has its last row / column repeated (a torch op).  The forward is one launch of csrc/scat.hip and so is the backward;
+    under ``torch.no_grad()`` (or for an input that needs no gradient) no phasors are stored."""
+
+    _tap_names = ("h0o", "h1o")
+
+    def __init__(self, biort="near_sym_a", mode="symmetric", magbias=1e-2, combine_colour=False):
+        super().__init__()
+        self.biort, self.mode_str, self.mode, self.magbias, self.combine_colour = biort, mode, mode_to_int(mode), magbias, combine_colour
+        self.bandpass_diag = False
+        _register_scat(self, _scat_taps(biort, None))
+
+    def forward(self, x):
+        if x.dim() != 4:
+            raise ValueError("a scattering layer takes inputs of 4 dimensions (N, C, H, W), got %d" % x.dim())
+        if self.combine_colour and x.shape[1] != 3:
+            raise ValueError("combine_colour takes 3 channels, got %d" % x.shape[1])
+        _prime(self, self._tap_names)
+        if x.shape[2] % 2:
+            x = torch.cat((x, x[:, :, -1:]), dim=2)
+        if x.shape[3] % 2:
+            x = torch.cat((x, x[:, :, :, -1:]), dim=3)
+        Z = ops.scat_layer_j1(x, self.h0o, self.h1o, self.mode, self.magbias, self.combine_colour)
+        return Z if self.combine_colour else Z.view(Z.shape[0], 7 * Z.shape[2], Z.shape[3], Z.shape[4])
+
+    def extra_repr(self):
+        return "biort='{}', mode='{}', magbias={}".format(self.biort, self.mode_str, self.magbias)
+
+
+class ScatLayerj2(_TapModule):
+    """scatternet/layers.py:82-172.  Second-order scattering over two scales with the level-1 and the q-shift filters: forward(x)
+    returns (N, 49C, H/4, W/4) -- per channel group the lowpass, the six level-1 and the six level-2 first-order magnitudes and the
+    36 second-order ones (index 6 o2 + o1) --, or (N, 51, H/4, W/4) = 3 + 6 + 6 + 36 with ``combine_colour``.  A side that is no
+    multiple of 8 is extended by its own leading and trailing rows / columns (torch ops, as the reference pads).  Only
+    ``mode='symmetric'`` runs: any other raises ``NotImplementedError`` in ``forward``, as the reference's q-shift filters do.  The
+    forward is three launches of csrc/scat.hip that write the result in place, the backward three."""
+
+    _tap_names = ("h0o", "h1o", "h0a", "h0b", "h1a", "h1b")
+
+    def __init__(self, biort="near_sym_a", qshift="qshift_a", mode="symmetric", magbias=1e-2, combine_colour=False):
+        super().__init__()
+        self.biort, self.qshift, self.mode_str, self.mode = biort, qshift, mode, mode_to_int(mode)
+        self.magbias, self.combine_colour, self.bandpass_diag = magbias, combine_colour, False
+        _register_scat(self, _scat_taps(biort, qshift))
+
+    def forward(self, x):
+        if self.mode != 1:
+            raise NotImplementedError("ScatLayerj2 runs with mode='symmetric' only (the q-shift level has no other extension), got %r"
+                                      % self.mode_str)
+        if x.dim() != 4:
+            raise ValueError("a scattering layer takes inputs of 4 dimensions (N, C, H, W), got %d" % x.dim())
+        if self.combine_colour and x.shape[1] != 3:
+            raise ValueError("combine_colour takes 3 channels, got %d" % x.shape[1])
+        _prime(self, self._tap_names)
+        for dim in (2, 3):
+            rem = x.shape[dim] % 8
+            if rem:
+                before, after = (8 - rem) // 2, (9 - rem) // 2
+                n = x.shape[dim]
+                x = torch.cat((x.narrow(dim, 0, before), x, x.narrow(dim, n - after, after)), dim=dim)
+        Z = ops.scat_layer_j2(x, self.h0o, self.h1o, self.h0a, self.h0b, self.h1a, self.h1b, self.mode, self.magbias, self.combine_colour)
+        return Z if self.combine_colour else Z.view(Z.shape[0], 49 * Z.shape[2], Z.shape[3], Z.shape[4])
+
+    def extra_repr(self):
+        return "biort='{}', mode='{}', magbias={}".format(self.biort, self.mode_str, self.magbias)

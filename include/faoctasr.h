@@ -386,6 +386,34 @@ int faoctasr_dtcwt_inv_j2(const float* ll, long ll_sn, long ll_sc, long ll_sr, c
                           const float* g0a, const float* g0b, const float* g1a, const float* g1b, int m,
                           faoctasr_stream_t stream);
 
+/* ---- DTCWT scattering layers (csrc/scat.hip) ------------------------------------------------------
+ * pytorch_wavelets scatternet/lowlevel.py (ScatLayerj1_f, ScatLayerj2_f): one dual-tree level, the smoothed magnitude
+ * sqrt(re^2 + im^2 + bias^2) - bias of its six orientations and the 2x2 mean of its lowpass, in one launch each way.  Taps, modes
+ * and size rules are those of the dtcwt calls above; bias2 is bias * bias, computed by the caller in double and rounded.
+ * Addresses are in elements and rows are contiguous: x takes (n, c, row) strides; low / dlow (n, c) strides; mag / dmag
+ * (n, orientation, c) strides, so a call writes into (reads from) slices of a layer's output (cotangent); phase is a contiguous
+ * (N, 6, C, H', W', 2) tensor of unit phasors (re / r, im / r); dx is contiguous (N, C, H, W).
+ * fwd_j1: x [H, W] -> low [H/2, W/2] (pool = 1: the mean) or [H, W] (pool = 0: the lowpass itself), mag and phase [H/2, W/2].
+ * fwd_j2: x [H, W], multiples of 4 -> low, mag, phase [H/4, W/4].
+ * phase == NULL: no phasors are stored (a forward without a backward).  colour = 1 (C must be 3): one magnitude per orientation
+ *   over the three channels, sqrt(sum_c (re_c^2 + im_c^2) + bias^2) - bias (mag_sc is not used), phasors per channel.
+ * bwd_j1, bwd_j2: the adjoints, on the SAME analysis taps as the forward call (bwd_j2 swaps trees a and b itself): dlow of the
+ *   forward's low shape, dmag and phase of its mag and phase shapes -> dx [H, W].  The colour form is dmag_sc = 0. */
+int faoctasr_scat_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, int pool,
+                         float* mag, long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2,
+                         long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, int mode,
+                         faoctasr_stream_t stream);
+int faoctasr_scat_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, float* mag,
+                         long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2, long N, int C,
+                         int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
+                         faoctasr_stream_t stream);
+int faoctasr_scat_bwd_j1(const float* dlow, long dlow_sn, long dlow_sc, int pool, const float* dmag, long dmag_sn, long dmag_so,
+                         long dmag_sc, const float* phase, float* dx, long N, int C, int H, int W, const float* h0, int L0,
+                         const float* h1, int L1, int mode, faoctasr_stream_t stream);
+int faoctasr_scat_bwd_j2(const float* dlow, long dlow_sn, long dlow_sc, const float* dmag, long dmag_sn, long dmag_so, long dmag_sc,
+                         const float* phase, float* dx, long N, int C, int H, int W, const float* h0a, const float* h0b,
+                         const float* h1a, const float* h1b, int m, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
