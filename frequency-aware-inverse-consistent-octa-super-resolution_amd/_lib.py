@@ -79,6 +79,10 @@ _SIG = {
     "scat_fwd_j2": (_I, "p lll p ll p lll p i ff l iii pppp i p"),
     "scat_bwd_j1": (_I, "p ll i p lll p p l iii pi pi i p"),
     "scat_bwd_j2": (_I, "p ll p lll p p l iii pppp i p"),
+    "dtcwt_loss_workspace_floats": (_L, "l iii i"),
+    "dtcwt_loss_fwd_j1": (_I, "p lll p lll pp pp p ff l iii pi pi i p"),
+    "dtcwt_loss_fwd_j2": (_I, "p lll p lll pp pp p ff l iii pppp i p"),
+    "dtcwt_loss_final": (_I, "p pp i p p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -1588,6 +1588,174 @@ def dtcwt_inv_j2(ll, highs, g0a, g0b, g1a, g1b, o_dim=2, ri_dim=-1):
 
 
 # ----------------------------------------------------------------------------------------
+# DTCWT magnitude loss (csrc/dtcwt_loss.hip): both images' level in one launch, no band stored
+# ----------------------------------------------------------------------------------------
+DTCWT_LOSS_MAX_LEVELS = 16
+_DTCWT_NAMES = ("n", "c", "o", "h", "w", "r")
+
+
+def dtcwt_mag_loss_fused(H, W, J):
+    """Whether an H x W image runs ``dtcwt_mag_loss`` on the fused kernels: both sides multiples of 2^J (no level pads)."""
+    return 1 <= J <= DTCWT_LOSS_MAX_LEVELS and H >= (1 << J) and W >= (1 << J) and H % (1 << J) == 0 and W % (1 << J) == 0
+
+
+def _dtcwt_mag_loss_check(x, y, taps2, J, mode, magbias, level_weights):
+    """Every refusal of the magnitude loss, the device check last; returns the level weights as floats."""
+    if int(J) != J or J < 1:
+        raise ValueError("the magnitude loss takes J >= 1 levels, got %r" % (J,))
+    if J >= 2 and taps2 is None:
+        raise ValueError("J = %d needs the four q-shift filters (levels >= 2), got None" % J)
+    if not magbias > 0:
+        raise ValueError("magbias must be positive (the magnitude's gradient is z / r), got %r" % (magbias,))
+    w = [1.0] * J if level_weights is None else [float(v) for v in level_weights]
+    if len(w) != J:
+        raise ValueError("level_weights lists one weight per level: %d entries for J = %d" % (len(w), J))
+    if x.dim() != 4 or y.dim() != 4:
+        raise ValueError("the magnitude loss takes inputs of 4 dimensions (N, C, H, W), got %d and %d" % (x.dim(), y.dim()))
+    if x.shape != y.shape:
+        raise ValueError("x and y must have the same shape, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if x.shape[0] < 1 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError("the magnitude loss takes non-empty inputs, got %s" % (tuple(x.shape),))
+    if not 0 <= mode <= 6:
+        raise ValueError("Unkown pad type: {}".format(mode))
+    for t, what in ((x, "x"), (y, "y")):
+        if t.dtype != torch.float32:
+            raise ValueError("%s must be float32, got %s" % (what, t.dtype))
+    _dtcwt_dev(x, "x")
+    _dtcwt_dev(y, "y")
+    if x.device != y.device:
+        raise ValueError("x and y must be on one device, got %s and %s" % (x.device, y.device))
+    return w
+
+
+class _DTCWTMagLoss(Function):
+    """``apply(x, y, taps1, taps2, J, mode, bias, weights, want_x, want_y) -> L`` on sizes ``dtcwt_mag_loss_fused`` accepts: J
+    analysis launches that take both images and one that adds the partial sums.  The cotangent bands of an input that needs a
+    gradient are written by the same launches (already scaled by w_j / count_j) and are all that is saved; the backward runs them
+    through the transform's adjoint, coarsest level first -- J launches per input -- and scales by the upstream gradient on the
+    device."""
+
+    @staticmethod
+    def forward(ctx, x, y, taps1, taps2, J, mode, bias, weights, want_x, want_y):
+        N, C, H, W = x.shape
+        dev = x.device
+        lib = _lib.load()
+        dims, floats = [], []
+        h, w = H, W
+        for j in range(J):
+            n = lib.faoctasr_dtcwt_loss_workspace_floats(N, C, h, w, int(j == 0))
+            if n < 0:
+                raise _lib.KernelError("faoctasr_dtcwt_loss_workspace_floats failed: %s" % lib.faoctasr_last_error().decode())
+            dims.append((h, w))
+            floats.append(n)
+            if j:
+                h, w = h // 2, w // 2
+        ws = _lib.workspace(dev, sum(floats), "dtcwt_loss")   # per stream: consumed by the same call's last launch
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        scales, gxs, gys = [], [], []
+        b2 = float(bias) * float(bias)
+        off = 0
+        for j in range(J):
+            h, w = dims[j]
+            bh, bw = (h // 2, w // 2) if j == 0 else (h // 4, w // 4)
+            scales.append(weights[j] / float(N * C * 6 * bh * bw))
+            last = j == J - 1
+            lh, lw = (h, w) if j == 0 else (h // 2, w // 2)
+            llx = None if last else torch.empty((N, C, lh, lw), dtype=torch.float32, device=dev)
+            lly = None if last else torch.empty((N, C, lh, lw), dtype=torch.float32, device=dev)
+            gx = torch.empty((N, C, 6, bh, bw, 2), dtype=torch.float32, device=dev) if want_x else None
+            gy = torch.empty((N, C, 6, bh, bw, 2), dtype=torch.float32, device=dev) if want_y else None
+            x, xn, xc, xr = _dtcwt_low(x)
+            y, yn, yc, yr = _dtcwt_low(y)
+            head = (x.data_ptr(), xn, xc, xr, y.data_ptr(), yn, yc, yr, ptr(llx), ptr(lly), ptr(gx), ptr(gy),
+                    ws.data_ptr() + 4 * off, scales[j], b2, N, C, h, w)
+            if j == 0:
+                call("dtcwt_loss_fwd_j1", *head, _tap_array(taps1[0]), len(taps1[0]), _tap_array(taps1[1]), len(taps1[1]), mode, stream_ptr())
+            else:
+                call("dtcwt_loss_fwd_j2", *head, *(_tap_array(t) for t in taps2), len(taps2[0]), stream_ptr())
+            off += floats[j]
+            gxs.append(gx)
+            gys.append(gy)
+            x, y = llx, lly
+        call("dtcwt_loss_final", ws.data_ptr(), ctypes.cast((ctypes.c_long * J)(*floats), ctypes.c_void_p),
+             ctypes.cast((ctypes.c_double * J)(*scales), ctypes.c_void_p), J, ptr(out), stream_ptr())
+        ctx.cfg = (taps1, _swap_ab(taps2) if taps2 is not None else None, mode, want_x, want_y)
+        if want_x or want_y:
+            ctx.save_for_backward(*[g for g in gxs + gys if g is not None])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        taps1, taps2, mode, want_x, want_y = ctx.cfg
+        saved = list(ctx.saved_tensors)
+        J = len(saved) // (int(want_x) + int(want_y)) if saved else 0
+        grads = []
+        for k, (want, need) in enumerate(((want_x, ctx.needs_input_grad[0]), (want_y, ctx.needs_input_grad[1]))):
+            if not need:
+                grads.append(None)
+                continue
+            if not want:
+                raise _lib.KernelError("the magnitude loss's forward ran without gradients enabled for this input: no cotangent bands were saved")
+            bands = saved[:J] if (k == 0 or not want_x) else saved[J:]
+            low = None
+            for h in bands[:0:-1]:
+                low = _dtcwt_inverse(low, h, taps2, False, 1, _DTCWT_NAMES)
+            grads.append(_dtcwt_inverse(low, bands[0], taps1, True, mode, _DTCWT_NAMES) * g)
+        return tuple(grads) + (None,) * 8
+
+
+def _dtcwt_mag_loss_composed(x, y, taps1, taps2, J, mode, bias, weights):
+    """The same definition from the per-level ops, the modules' padding and torch ops: for sizes the fused kernels do not take."""
+    b2 = float(bias) * float(bias)
+    lows = []
+    for t in (x, y):
+        if t.shape[2] % 2:
+            t = torch.cat((t, t[:, :, -1:]), dim=2)
+        if t.shape[3] % 2:
+            t = torch.cat((t, t[:, :, :, -1:]), dim=3)
+        lows.append(t)
+    total = None
+    for j in range(J):
+        mags = []
+        for k in (0, 1):
+            low = lows[k]
+            if j == 0:
+                low, h = _DTCWTFwdJ1.apply(low, taps1, True, False, _DTCWT_NAMES, mode)
+            else:
+                if low.shape[2] % 4:
+                    low = torch.cat((low[:, :, 0:1], low, low[:, :, -1:]), dim=2)
+                if low.shape[3] % 4:
+                    low = torch.cat((low[:, :, :, 0:1], low, low[:, :, :, -1:]), dim=3)
+                low, h = _DTCWTFwdJ2.apply(low, taps2, False, False, _DTCWT_NAMES, 1)
+            lows[k] = low
+            mags.append(torch.sqrt(h[..., 0] * h[..., 0] + h[..., 1] * h[..., 1] + b2))
+        term = weights[j] * (mags[0] - mags[1]).abs().mean()
+        total = term if total is None else total + term
+    return total
+
+
+def dtcwt_mag_loss(x, y, h0o, h1o, qshift=None, J=1, mode=1, magbias=1e-2, level_weights=None):
+    """``sum_j w_j * mean |r_j(x) - r_j(y)|`` with ``r = sqrt(re^2 + im^2 + magbias^2)`` over the six complex orientations of every
+    level j = 1..J of the dual-tree transform of x and y (N, C, H, W), as a 0-d fp32 tensor with gradients to both; the mean of a
+    level runs over its N * C * 6 * h_j * w_j coefficients, there is no lowpass term.  Filters as the modules register them (taps
+    reversed): ``h0o``, ``h1o`` and, for J >= 2, ``qshift`` = (h0a, h0b, h1a, h1b).  ``mode`` acts on level 1: 1 is the symmetric
+    extension, any other ``wavelets.mode_to_int`` code pads with zeros.  ``magbias`` > 0.
+
+    With H and W multiples of 2^J the op is J + 1 launches of csrc/dtcwt_loss.hip -- a block runs its tile of x and then of y, and
+    no band is stored -- and J launches of the transform's adjoint per input that needs a gradient; under ``no_grad`` nothing is
+    saved.  Bit-reproducible.  Any other size takes the composition of the per-level ops with the modules' padding and torch ops
+    for the magnitude and the mean: the same definition, autograd-correct, slower."""
+    taps1 = _dtcwt_taps1(h0o, h1o)
+    taps2 = _dtcwt_taps2(*qshift) if qshift is not None else None
+    w = _dtcwt_mag_loss_check(x, y, taps2, J, int(mode), magbias, level_weights)
+    J = int(J)
+    if not dtcwt_mag_loss_fused(x.shape[2], x.shape[3], J):
+        return _dtcwt_mag_loss_composed(x, y, taps1, taps2, J, int(mode), float(magbias), w)
+    grad = torch.is_grad_enabled()
+    return _DTCWTMagLoss.apply(x, y, taps1, taps2, J, int(mode), float(magbias), tuple(w), grad and x.requires_grad, grad and y.requires_grad)
+
+
+# ----------------------------------------------------------------------------------------
 # DTCWT scattering layers (csrc/scat.hip): a dual-tree level, smoothed magnitudes and the pooled lowpass in one launch
 # ----------------------------------------------------------------------------------------
 def scat_sizes(H, W, order):

@@ -20,7 +20,7 @@ from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
-from .wavelets import DWTForward, SWTForward
+from .wavelets import DTCWTMagnitudeLoss, DWTForward, SWTForward
 
 # parameters that exist in the reference's state_dict but never receive a gradient
 # (model.py:241,254-257: unet/unet_up of NetworkA2B; model.py:281-284: skip of NetworkB2A);
@@ -262,7 +262,7 @@ class TrainStep:
                  beta1=0.25, beta2=10.0, beta3=2.0, beta4=0.5, beta5=0.5, ssim_weight=0.0, whf_weight=0.0, dwt_levels=1,
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
                  reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
-                 dwt_stationary=False):
+                 dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric"):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -279,7 +279,12 @@ class TrainStep:
 
         ``dwt_stationary`` (default off): the wavelet-HF term runs on ``SWTForward(J=dwt_levels, wave=dwt_wave, mode=dwt_mode)``
         instead -- the undecimated transform, whose bands 1..3 of every level enter the L1.  The decimated transform penalises a
-        one-pixel misregistration differently depending on its parity; the stationary one has no such phase."""
+        one-pixel misregistration differently depending on its parity; the stationary one has no such phase.
+
+        ``cwt_weight`` (default 0: nothing is constructed or launched): adds ``loss_cwt = cwt_weight * (L(recovered_A, real_A) +
+        L(recovered_B, real_B))`` to ``loss_G``, L the dual-tree magnitude loss ``DTCWTMagnitudeLoss(cwt_biort, cwt_qshift,
+        J=cwt_levels, mode=cwt_mode)``: six orientations, nearly shift-invariant magnitudes.  ``cwt_qshift`` is resolved only for
+        ``cwt_levels`` >= 2 (a name needs a tap provider; a 4-tuple of tap sequences does not)."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -305,6 +310,10 @@ class TrainStep:
         self.dwt_stationary = bool(dwt_stationary)
         self.dwt_loss = ((SWTForward if self.dwt_stationary else DWTForward)(J=dwt_levels, wave=dwt_wave, mode=dwt_mode).to(dev)
                          if whf_weight else None)
+        #: opt-in dual-tree magnitude term on the cycle reconstructions (wavelets.DTCWTMagnitudeLoss; 0 = off, no module is built)
+        self.cwt_weight = cwt_weight
+        self.cwt_loss = (DTCWTMagnitudeLoss(biort=cwt_biort, qshift=cwt_qshift, J=cwt_levels, mode=cwt_mode).to(dev)
+                         if cwt_weight else None)
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -606,6 +615,8 @@ class TrainStep:
             t["loss_whf"] = acc
         if self.phase_weight:
             t["loss_phase"] = self.phase_weight * (1 + ops.phase_loss(rec, real, self.phase_radius))
+        if self.cwt_weight:
+            t["loss_cwt"] = self.cwt_weight * self.cwt_loss(rec, real)
         return t
 
     def generator_loss(self, o, real_A, real_B):
@@ -643,6 +654,9 @@ class TrainStep:
             L["loss_phase"] = self.phase_weight * ((1 + ops.phase_loss(o["recovered_A"], real_A, self.phase_radius)) +
                                                    (1 + ops.phase_loss(o["recovered_B"], real_B, self.phase_radius)))
             total = total + L["loss_phase"]
+        if self.cwt_weight:
+            L["loss_cwt"] = self.cwt_weight * (self.cwt_loss(o["recovered_A"], real_A) + self.cwt_loss(o["recovered_B"], real_B))
+            total = total + L["loss_cwt"]
         if self.tv_weight:
             L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
             total = total + L["loss_tv"]

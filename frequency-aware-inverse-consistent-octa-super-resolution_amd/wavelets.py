@@ -631,11 +631,15 @@ def _register_scat(module, taps):
     _record(module, module._tap_names)
 
 
-def _scat_taps(biort, qshift):
+def _refuse_bp(biort, qshift):
     for name in (biort, qshift):
         if isinstance(name, str) and name.endswith("_bp"):
             raise NotImplementedError("%r: the rotationally symmetric three-filter variants (near_sym_b_bp / qshift_b_bp) need a third "
                                       "filter path in every kernel of csrc/scat.hip and are not built" % name)
+
+
+def _scat_taps(biort, qshift):
+    _refuse_bp(biort, qshift)
     return _dtcwt_taps(biort, qshift, analysis=True)
 
 
@@ -708,3 +712,43 @@ class ScatLayerj2(_TapModule):
 
     def extra_repr(self):
         return "biort='{}', mode='{}', magbias={}".format(self.biort, self.mode_str, self.magbias)
+
+
+# ----------------------------------------------------------------------------------------
+# DTCWT magnitude loss -> csrc/dtcwt_loss.hip
+# ----------------------------------------------------------------------------------------
+class DTCWTMagnitudeLoss(_TapModule):
+    """forward(x, y) -> ``sum_j w_j * mean |r_j(x) - r_j(y)|`` over the six complex orientations of the levels j = 1..J of
+    ``DTCWTForward(biort, qshift, J, mode)``, with the scattering layers' smoothed magnitude ``r = sqrt(re^2 + im^2 + magbias^2)``
+    (its bias cancels in the difference); a level's mean runs over its N * C * 6 * h_j * w_j coefficients and there is no lowpass
+    term.  A 0-d tensor with gradients to both images.  The six orientations keep +45 and -45 degrees apart and the magnitudes are
+    nearly shift-invariant, so the comparison tolerates a sub-pixel misregistration that a decimated real transform penalises.
+
+    ``biort`` / ``qshift`` / ``mode`` as ``DTCWTForward`` takes them, registered under the same buffer names; ``qshift`` is resolved
+    only when J >= 2.  ``level_weights``: one weight per level (default all 1).  The three-filter ``*_bp`` banks are refused.  With H
+    and W multiples of 2^J a forward is J + 1 launches of csrc/dtcwt_loss.hip that store no band, and the backward J launches of
+    the transform's adjoint per image that needs a gradient; any other size takes the composition of the per-level ops with
+    ``DTCWTForward``'s padding and torch ops (``ops.dtcwt_mag_loss``) -- the sizes 192, 256, 512 never do up to J = 3."""
+
+    def __init__(self, biort="near_sym_a", qshift="qshift_a", J=3, mode="symmetric", magbias=1e-2, level_weights=None):
+        super().__init__()
+        if int(J) != J or J < 1:
+            raise ValueError("the magnitude loss takes J >= 1 levels, got %r" % (J,))
+        if not magbias > 0:
+            raise ValueError("magbias must be positive (the magnitude's gradient is z / r), got %r" % (magbias,))
+        if level_weights is not None and len(level_weights) != J:
+            raise ValueError("level_weights lists one weight per level: %d entries for J = %d" % (len(level_weights), J))
+        self.biort, self.qshift, self.J, self.mode, self.magbias = biort, qshift, int(J), mode, float(magbias)
+        self.level_weights = None if level_weights is None else tuple(float(w) for w in level_weights)
+        self._tap_names = DTCWTForward._tap_names if self.J >= 2 else DTCWTForward._tap_names[:2]
+        _refuse_bp(biort, qshift)
+        _register_dtcwt(self, _dtcwt_taps(biort, qshift if self.J >= 2 else None, analysis=True))
+
+    def forward(self, x, y):
+        mode = mode_to_int(self.mode)
+        _prime(self, self._tap_names)
+        q = (self.h0a, self.h0b, self.h1a, self.h1b) if self.J >= 2 else None
+        return ops.dtcwt_mag_loss(x, y, self.h0o, self.h1o, q, self.J, mode, self.magbias, self.level_weights)
+
+    def extra_repr(self):
+        return "biort='{}', J={}, mode='{}', magbias={}".format(self.biort, self.J, self.mode, self.magbias)

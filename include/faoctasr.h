@@ -414,6 +414,31 @@ int faoctasr_scat_bwd_j2(const float* dlow, long dlow_sn, long dlow_sc, const fl
                          const float* phase, float* dx, long N, int C, int H, int W, const float* h0a, const float* h0b,
                          const float* h1a, const float* h1b, int m, faoctasr_stream_t stream);
 
+/* ---- DTCWT magnitude loss (csrc/dtcwt_loss.hip) -----------------------------------------------------
+ * L(x, y) = sum_j w_j * mean over (n, c, orientation, row, column) of | r_j(x) - r_j(y) |,  r = sqrt(re^2 + im^2 + bias^2), over the
+ * bandpass coefficients of the dtcwt calls above; no lowpass term.  Taps, modes, size rules, strides of x and y ((n, c, row), unit
+ * columns) and error codes are theirs; bias2 = bias * bias > 0.
+ * fwd_j1 / fwd_j2: one level of BOTH images in one launch (a block runs its tile of x, then of y, through the same LDS).  Writes
+ *   part[0, blocks): one partial sum of |r_x - r_y| per block, blocks = faoctasr_dtcwt_loss_workspace_floats(N, C, H, W, level1)
+ *     with the H, W of that launch (level1 = 1 for fwd_j1, 0 for fwd_j2; -1 on a bad shape);
+ *   llx, lly: each image's lowpass for the next level, contiguous [H, W] (fwd_j1) or [H/2, W/2] (fwd_j2); NULL: not stored;
+ *   gx, gy: the cotangent bands sign(r_x - r_y) * z_x / r_x * scale and -sign(r_x - r_y) * z_y / r_y * scale, sign(0) = 0, as
+ *     contiguous (N, C, 6, h, w, 2) tensors; NULL: not computed.  scale = w_j / count_j.  dtcwt_inv_j2 / dtcwt_inv_j1 on the
+ *     analysis taps (a and b swapped at levels >= 2) carry them to dL/dx and dL/dy.
+ * final: out[0] = sum_j level_scale[j] * (sum of the level_floats[j] partials of level j), the levels' partials one after the
+ *   other in `workspace`; level_floats and level_scale are HOST arrays of `levels` (<= 16) entries, read during the call.  Fixed
+ *   order, in double: bit-reproducible. */
+long faoctasr_dtcwt_loss_workspace_floats(long N, int C, int H, int W, int level1);
+int faoctasr_dtcwt_loss_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, const float* y, long y_sn, long y_sc, long y_sr,
+                               float* llx, float* lly, float* gx, float* gy, float* part, float scale, float bias2, long N, int C,
+                               int H, int W, const float* h0, int L0, const float* h1, int L1, int mode, faoctasr_stream_t stream);
+int faoctasr_dtcwt_loss_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, const float* y, long y_sn, long y_sc, long y_sr,
+                               float* llx, float* lly, float* gx, float* gy, float* part, float scale, float bias2, long N, int C,
+                               int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
+                               faoctasr_stream_t stream);
+int faoctasr_dtcwt_loss_final(const float* workspace, const long* level_floats, const double* level_scale, int levels, float* out,
+                              faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */

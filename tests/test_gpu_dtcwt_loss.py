@@ -1,0 +1,333 @@
+"""The DTCWT magnitude loss (csrc/dtcwt_loss.hip) on the MI355X: ``DTCWTMagnitudeLoss`` / ``ops.dtcwt_mag_loss`` against the
+reference's own CPU results (tests/golden/golden_cwt_loss.npz) and the float64 restatement of tests/test_dtcwt_loss_cpu.py
+(pinned to that fixture there), tile seams, exact cases, the launch structure, and the opt-in ``TrainStep(cwt_weight=...)`` term,
+eager and hipGraph-captured.
+
+Every error is measured against the float64 restatement; the bar is the project's, twice the fp32 reference's own error:
+
+    gradients (relative L2, per array):   e_hip <= 2 e_ref + 2^-23
+    loss (relative):                      e_hip <= 2 E_ref + 1 ulp of the loss
+
+e_ref is the fp32 reference's distance from the restatement (the fixture's ``f32`` arrays; off the fixture, the restatement run
+in fp32 on the CPU).  A single scalar's e_ref can be small by luck, so E_ref is the LARGEST relative fp32-reference error of the
+loss over all fixture cases of the bank (off the fixture: that, or the case's own fp32 restatement if larger).
+
+The tie condition.  sign(r_x - r_y) is discontinuous: a rounding difference at r_x ~ r_y flips a whole coefficient's gradient.
+Every test that compares gradients first asserts, on the float64 restatement, that the smallest |r_x - r_y| / max(r_x, r_y) over
+ALL coefficients is at least 2^-16 (about 16 times the fp32 error of a magnitude).  The seeds below were picked on the CPU for
+that; nothing is excluded.
+
+Each array prints a ``DTCWT_LOSS_ERR`` line (run with ``-s``; a run's lines are what profiles/dtcwt_loss_error.txt holds)."""
+import math
+import random
+
+import pytest
+import torch
+
+from test_dtcwt_cpu import rel_l2
+from test_dtcwt_loss_cpu import BANKS, CASES, MIN_GAP, bufs, case_name, fixture_cases, fixture_inputs, gold, loss_err, restate, restate_case, tuples
+
+pytestmark = pytest.mark.gpu
+
+K, FLOOR = 2.0, 2.0 ** -23
+TIGHT = ("loss_G", "loss_cycle_ABA", "loss_cycle_BAB", "loss_idt")
+GX_ARG, GY_ARG, LLX_ARG, LLY_ARG = 10, 11, 8, 9           # positions of the cotangent and lowpass pointers in the entry points' arguments
+#: seeds for which the tie condition holds, per bank (searched on the CPU with the float64 restatement)
+SEAM_SEEDS = {"a": 110, "b": 100, "c": 114}
+RAGGED_SEEDS = {"a": 221, "b": 211, "c": 212}
+
+
+@pytest.fixture(scope="module")
+def fa():
+    import faoctasr
+    faoctasr._lib.load()
+    return faoctasr
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import octa_oracle
+    return octa_oracle
+
+
+def criterion(fa, bank, J, mode="symmetric", weights=None):
+    fb, fq = tuples(bank)
+    return fa.DTCWTMagnitudeLoss(biort=fb, qshift=fq, J=J, mode=mode, level_weights=weights).cuda()
+
+
+def run_hip(mod, x, y, x_grad=True, y_grad=True):
+    """{"loss", "dx", "dy"} of the module on the GPU, back on the host; the tensors stay float32."""
+    xd = (x if x.is_cuda else x.float().cuda()).detach().requires_grad_(x_grad)
+    yd = (y if y.is_cuda else y.float().cuda()).detach().requires_grad_(y_grad)
+    loss = mod(xd, yd)
+    assert loss.shape == () and loss.dtype == torch.float32
+    if x_grad or y_grad:
+        loss.backward()
+    torch.cuda.synchronize()
+    out = {"loss": loss.detach().cpu()}
+    if x_grad:
+        out["dx"] = xd.grad.cpu()
+    if y_grad:
+        out["dy"] = yd.grad.cpu()
+    return out
+
+
+def ulp_rel(v):
+    v = abs(float(v))
+    return 2.0 ** (math.floor(math.log2(v)) - 23) / v
+
+
+_E_ref = {}
+
+
+def loss_E_ref(bank):
+    """The largest relative error of the fp32 reference's loss over the bank's fixture cases."""
+    if bank not in _E_ref:
+        g = gold()
+        _E_ref[bank] = max(loss_err(g["%s/%s/f32/loss" % (bank, c[0])], restate_case((bank,) + c)["loss"]) for c in CASES)
+    return _E_ref[bank]
+
+
+def hold_to_bar(name, bank, ref64, ref32, got):
+    """Print e_ref, e_hip and their ratio per array, then assert the bars of the module docstring on every one."""
+    bad = []
+    E_ref = max(loss_E_ref(bank), loss_err(ref32["loss"], ref64["loss"]))
+    e_hip = loss_err(got["loss"], ref64["loss"])
+    print("DTCWT_LOSS_ERR %-32s %-4s e_ref %.3e (this case %.3e) e_hip %.3e ratio %.3f" % (
+        name, "loss", E_ref, loss_err(ref32["loss"], ref64["loss"]), e_hip, e_hip / E_ref))
+    if not e_hip <= K * E_ref + ulp_rel(ref64["loss"]):
+        bad.append(("loss", e_hip, E_ref))
+    for k in ("dx", "dy"):
+        if k not in ref64:
+            assert k not in got
+            continue
+        assert tuple(got[k].shape) == tuple(ref64[k].shape)
+        e_ref, e_hip = rel_l2(ref32[k], ref64[k]), rel_l2(got[k], ref64[k])
+        print("DTCWT_LOSS_ERR %-32s %-4s e_ref %.3e e_hip %.3e ratio %.3f" % (name, k, e_ref, e_hip, e_hip / e_ref if e_ref else float("inf")))
+        if not e_hip <= K * e_ref + FLOOR:
+            bad.append((k, e_hip, e_ref))
+    assert not bad, (name, bad)
+
+
+@pytest.mark.parametrize("case", fixture_cases(), ids=case_name)
+def test_fixture_parity(fa, case):
+    """The loss, dx and dy of every fixture case."""
+    bank, cid, shape, J, mode, weights, y_grad = case
+    g = gold()
+    ref64 = restate_case(case)
+    assert ref64["gap"] >= MIN_GAP, ref64["gap"]                          # the tie condition
+    ref32 = {k: torch.from_numpy(g["%s/%s/f32/%s" % (bank, cid, k)]) for k in ref64 if k != "gap"}
+    x, y = fixture_inputs(case)
+    hold_to_bar(case_name(case), bank, ref64, ref32, run_hip(criterion(fa, bank, J, mode, weights), x, y, True, y_grad))
+
+
+def seeded_pair(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g), torch.randn(*shape, generator=g)
+
+
+@pytest.mark.parametrize("bank", BANKS)
+def test_tile_seams(fa, bank):
+    """(1, 2, 40, 264) at J = 3: level 1 tiles 16 x 64 of its 40 x 264 input (two tiles + 8 rows, four tiles + 8 columns), levels 2
+    and 3 tile 16 x 128 of their 40 x 264 and 20 x 132 inputs -- every launch crosses a tile boundary in both axes and ends in a
+    remainder tile.  Banks a and c have m/2 odd (5, 9), bank b even (8)."""
+    shape = (1, 2, 40, 264)
+    assert fa.ops.dtcwt_mag_loss_fused(40, 264, 3)
+    x, y = seeded_pair(shape, SEAM_SEEDS[bank])
+    b = bufs(bank)
+    ref64 = restate(x, y, b, "symmetric", 3)
+    assert ref64["gap"] >= MIN_GAP, ref64["gap"]                          # the tie condition
+    ref32 = restate(x, y, b, "symmetric", 3, dtype=torch.float32)
+    hold_to_bar("seams 1x2x40x264 J3 %s" % bank, bank, ref64, ref32, run_hip(criterion(fa, bank, 3), x, y))
+
+
+@pytest.mark.parametrize("bank", BANKS)
+def test_ragged_size_takes_the_composed_path(fa, monkeypatch, bank):
+    """(1, 2, 13, 19) at J = 2: odd sides and a level-1 lowpass that is no multiple of 4 -- the per-level ops with the modules'
+    padding and torch ops, held to the same bar."""
+    shape = (1, 2, 13, 19)
+    assert not fa.ops.dtcwt_mag_loss_fused(13, 19, 2)
+    x, y = seeded_pair(shape, RAGGED_SEEDS[bank])
+    b = bufs(bank)
+    ref64 = restate(x, y, b, "symmetric", 2)
+    assert ref64["gap"] >= MIN_GAP, ref64["gap"]                          # the tie condition
+    ref32 = restate(x, y, b, "symmetric", 2, dtype=torch.float32)
+    calls = spy(fa, monkeypatch)
+    got = run_hip(criterion(fa, bank, 2), x, y)
+    assert calls and not [n for n, _ in calls if n.startswith("dtcwt_loss")]
+    hold_to_bar("ragged 1x2x13x19 J2 %s" % bank, bank, ref64, ref32, got)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# exact cases
+# ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("bank,J,shape", [("a", 3, (2, 2, 40, 72)), ("b", 2, (1, 3, 16, 24)), ("c", 1, (2, 1, 18, 130))])
+def test_exact_cases(fa, bank, J, shape):
+    x, y = (t.cuda() for t in seeded_pair(shape, 5))
+    mod = criterion(fa, bank, J)
+    same = run_hip(mod, x, x.clone())
+    assert float(same["loss"]) == 0.0 and not same["dx"].any() and not same["dy"].any()         # sign(0) = 0
+    xy, yx = run_hip(mod, x, y), run_hip(mod, y, x)
+    assert torch.equal(xy["loss"], yx["loss"])                            # bit for bit
+    assert torch.equal(xy["dx"], yx["dy"]) and torch.equal(xy["dy"], yx["dx"])
+    w = [1.0, 0.75, 1.5][:J]
+    full, half = run_hip(criterion(fa, bank, J, weights=w), x, y), run_hip(criterion(fa, bank, J, weights=[0.5 * v for v in w]), x, y)
+    assert torch.equal(half["loss"], 0.5 * full["loss"])
+    assert torch.equal(half["dx"], 0.5 * full["dx"]) and torch.equal(half["dy"], 0.5 * full["dy"])
+    assert float(full["loss"]) > 0 and full["dx"].abs().max() > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# structure
+# ------------------------------------------------------------------------------------------------------------------------
+def spy(fa, monkeypatch):
+    calls = []
+    real = fa.ops.call
+    monkeypatch.setattr(fa.ops, "call", lambda name, *a: (calls.append((name, a)), real(name, *a))[1])
+    return calls
+
+
+@pytest.mark.parametrize("J", [1, 2, 3])
+def test_launch_counts(fa, monkeypatch, J):
+    """Forward J + 1 launches; backward J launches per input that needs a gradient, coarsest level first."""
+    x, y = (t.cuda() for t in seeded_pair((1, 2, 32, 64), 3))
+    mod = criterion(fa, "a", J)
+    fwd = ["dtcwt_loss_fwd_j1"] + ["dtcwt_loss_fwd_j2"] * (J - 1) + ["dtcwt_loss_final"]
+    bwd = ["dtcwt_inv_j2"] * (J - 1) + ["dtcwt_inv_j1"]
+    for x_grad, y_grad in ((True, True), (True, False), (False, True)):
+        xd, yd = x.clone().requires_grad_(x_grad), y.clone().requires_grad_(y_grad)
+        calls = spy(fa, monkeypatch)
+        loss = mod(xd, yd)
+        assert [n for n, _ in calls] == fwd
+        for k, (n, a) in enumerate(calls[:-1]):
+            assert bool(a[GX_ARG]) == x_grad and bool(a[GY_ARG]) == y_grad, (n, x_grad, y_grad)
+            assert bool(a[LLX_ARG]) == bool(a[LLY_ARG]) == (k < J - 1)    # no lowpass is written at the last level
+        del calls[:]
+        loss.backward()
+        assert [n for n, _ in calls] == bwd * (int(x_grad) + int(y_grad))
+        assert (xd.grad is not None) == x_grad and (yd.grad is not None) == y_grad
+        monkeypatch.undo()
+
+
+def test_no_grad_forward_saves_nothing_and_changes_no_bit(fa, monkeypatch):
+    x, y = (t.cuda() for t in seeded_pair((2, 3, 16, 24), 2))
+    mod = criterion(fa, "a", 3)
+    calls = spy(fa, monkeypatch)
+    Lg = mod(x.clone().requires_grad_(True), y.clone().requires_grad_(True))
+    assert all(a[GX_ARG] and a[GY_ARG] for n, a in calls[:-1])
+    del calls[:]
+    with torch.no_grad():
+        Ln = mod(x.clone().requires_grad_(True), y.clone().requires_grad_(True))
+    assert len(calls) == 4 and all(a[GX_ARG] is None and a[GY_ARG] is None for n, a in calls[:-1])      # null cotangent pointers
+    assert not Ln.requires_grad and Ln.grad_fn is None
+    del calls[:]
+    Lp = mod(x, y)                                                        # inputs that need no gradient
+    assert all(a[GX_ARG] is None and a[GY_ARG] is None for n, a in calls[:-1]) and not Lp.requires_grad
+    assert torch.equal(Ln, Lg) and torch.equal(Lp, Lg)
+
+
+def test_upstream_gradient_is_applied_on_the_device(fa):
+    x, y = (t.cuda() for t in seeded_pair((1, 1, 16, 16), 4))
+    mod = criterion(fa, "a", 2)
+    one = run_hip(mod, x, y)
+    xd = x.clone().requires_grad_(True)
+    (mod(xd, y) * 0.25).backward()
+    assert torch.equal(xd.grad.cpu(), 0.25 * one["dx"])
+
+
+def test_bit_reproducible_and_on_a_side_stream(fa):
+    x, y = (t.cuda() for t in seeded_pair((2, 1, 64, 192), 6))
+    mod = criterion(fa, "a", 3)
+    first, again = run_hip(mod, x, y), run_hip(mod, x, y)
+    assert all(torch.equal(first[k], again[k]) for k in first)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        side = run_hip(mod, x, y)
+    torch.cuda.current_stream().wait_stream(s)
+    assert all(torch.equal(first[k], side[k]) for k in first)
+
+
+def test_views_equal_their_contiguous_copies(fa):
+    big, other = (t.cuda() for t in seeded_pair((2, 2, 70, 90), 13))
+    mod = criterion(fa, "a", 3)
+    for vx, vy in ((big[:, :, 3:67, 5:69], other[:, :, 3:67, 5:69]), (big[:, :, ::2, 1:49][:, :, :32], other[:, :, :32, :48]),
+                   (big.transpose(2, 3)[:, :, :88, :64], other.transpose(2, 3)[:, :, :88, :64])):
+        assert not vx.is_contiguous()
+        got, want = run_hip(mod, vx, vy), run_hip(mod, vx.contiguous(), vy.contiguous())
+        assert all(torch.equal(got[k], want[k]) for k in want)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the train step's opt-in term
+# ------------------------------------------------------------------------------------------------------------------------
+def build_nets(fa, O, seed=0):
+    nets = {"A2B": fa.NetworkA2B(), "B2A": fa.NetworkB2A(), "D_A": fa.FS_DiscriminatorA(1), "D_B": fa.FS_DiscriminatorB(1)}
+    specs = {"A2B": O.spec_network_a2b(), "B2A": O.spec_network_b2a(), "D_A": O.spec_fs_discriminator("sum"), "D_B": O.spec_fs_discriminator("cat")}
+    for k, n in nets.items():
+        n.load_state_dict(O.make_state(specs[k], k, seed), strict=True)
+        n.cuda().train()
+    return nets
+
+
+def fresh_step(fa, O, **kw):
+    random.seed(1234)
+    n = build_nets(fa, O)
+    return fa.TrainStep(n["A2B"], n["B2A"], n["D_A"], n["D_B"], **kw)
+
+
+def cwt_args():
+    return dict(cwt_weight=0.5, cwt_levels=2, cwt_qshift=tuples("a")[1])
+
+
+@pytest.mark.parametrize("two_chains", [True, False])
+@pytest.mark.parametrize("precision", ["f32", "f16x2"])
+def test_train_step_cwt_term(fa, O, precision, two_chains):
+    """192^2, batch 2: the term is what the restatement gives on the step's own tensors, it is what loss_G gains, it moves the
+    generators' gradient, and a weight-0 step does not know it.  Both places the opt-in terms live: the two-chain schedule and
+    the single-stream ``generator_loss``."""
+    a, b = (t.cuda() for t in O.synthetic_batch(2, 192))
+    saved = fa.TrainStep.overlap_min_pixels
+    fa.TrainStep.overlap_min_pixels = 0 if two_chains else 1 << 40
+    try:
+        ts = fresh_step(fa, O, precision=precision, **cwt_args())
+        L = ts.step(a, b, sync=True, keep=True)
+        gn = ts.grad_norms()
+        ts0 = fresh_step(fa, O, precision=precision)
+        L0 = ts0.step(a, b, sync=True, keep=True)
+        gn0 = ts0.grad_norms()
+    finally:
+        fa.TrainStep.overlap_min_pixels = saved
+    assert "loss_cwt" not in L0 and ts0.cwt_loss is None
+    T = L["tensors"]
+    bank = bufs("a")
+    want = 0.5 * sum(float(restate(rec, real, bank, "symmetric", 2, x_grad=False, y_grad=False)["loss"])
+                     for rec, real in ((T["recovered_A"], a), (T["recovered_B"], b)))
+    print("DTCWT_LOSS_ERR step %s two_chains=%s: loss_cwt %.7f restatement %.7f, loss_G %.6f against %.6f at weight 0, |grad A2B| %.5f against %.5f, "
+          "|grad B2A| %.5f against %.5f" % (precision, two_chains, L["loss_cwt"], want, L["loss_G"], L0["loss_G"], gn["A2B"], gn0["A2B"], gn["B2A"], gn0["B2A"]))
+    assert abs(L["loss_cwt"] - want) <= 1e-3 * abs(want)
+    assert abs((L["loss_G"] - L0["loss_G"]) - L["loss_cwt"]) <= 1e-3 * abs(L["loss_G"])
+    assert abs(gn["A2B"] - gn0["A2B"]) > 1e-3 * gn0["A2B"] or abs(gn["B2A"] - gn0["B2A"]) > 1e-3 * gn0["B2A"], (gn, gn0)
+    for k in L0:
+        if k not in ("tensors", "loss_G"):
+            assert abs(L[k] - L0[k]) <= 1e-3 * max(abs(L0[k]), 2e-2), (k, L[k], L0[k])
+
+
+def test_graph_captured_step_with_cwt_term(fa, O):
+    """The step with the term as one captured hipGraph: three replays follow the eager step at the bars of the existing graph
+    test (2e-4 relative at step 0; later 3e-3 on the tight losses, 0.03 / 0.06 absolute on the others)."""
+    batches = [tuple(t.cuda() for t in O.synthetic_batch(2, 192, seed=1234 + 17 * s)) for s in range(3)]
+    eager = fresh_step(fa, O, precision="f32", **cwt_args())
+    Le = [eager.step(a, b, sync=True) for a, b in batches]
+    ts = fresh_step(fa, O, precision="f32", **cwt_args())
+    gs = fa.GraphedTrainStep(ts, batches[0][0], batches[0][1])
+    Lg = [gs.step(a, b, sync=True) for a, b in batches]
+    for s in range(3):
+        print("DTCWT_LOSS_ERR graph step %d: loss_cwt %.7f eager %.7f, loss_G %.6f eager %.6f" % (s, Lg[s]["loss_cwt"], Le[s]["loss_cwt"], Lg[s]["loss_G"], Le[s]["loss_G"]))
+        for k in ("loss_cwt", "loss_G"):
+            tol = 2e-4 if s == 0 else (3e-3 if k in TIGHT else None)
+            if tol is not None:
+                assert Lg[s][k] == pytest.approx(Le[s][k], rel=tol, abs=1e-6), (s, k, Lg[s][k], Le[s][k])
+            else:
+                assert Lg[s][k] == pytest.approx(Le[s][k], abs=0.03 if s == 1 else 0.06), (s, k)
+    assert ts.opt_G.step_count == 3
