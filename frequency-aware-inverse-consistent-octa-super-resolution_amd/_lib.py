@@ -79,6 +79,14 @@ _SIG = {
     "scat_fwd_j2": (_I, "p lll p ll p lll p i ff l iii pppp i p"),
     "scat_bwd_j1": (_I, "p ll i p lll p p l iii pi pi i p"),
     "scat_bwd_j2": (_I, "p ll p lll p p l iii pppp i p"),
+    "dtcwt_fwd_j1_bp": (_I, "p lll pp llllll i l iii pi pi pi i p"),
+    "dtcwt_fwd_j2_bp": (_I, "p lll pp llllll i l iii pppppp i p"),
+    "dtcwt_inv_j1_bp": (_I, "p lll p llllll p l iii pi pi pi i p"),
+    "dtcwt_inv_j2_bp": (_I, "p lll p llllll p l iii pppppp i p"),
+    "scat_fwd_j1_bp": (_I, "p lll p ll i p lll p i ff l iii pi pi pi i p"),
+    "scat_fwd_j2_bp": (_I, "p lll p ll p lll p i ff l iii pppppp i p"),
+    "scat_bwd_j1_bp": (_I, "p ll i p lll p p l iii pi pi pi i p"),
+    "scat_bwd_j2_bp": (_I, "p ll p lll p p l iii pppppp i p"),
     "dtcwt_loss_workspace_floats": (_L, "l iii i"),
     "dtcwt_loss_fwd_j1": (_I, "p lll p lll pp pp p ff l iii pi pi i p"),
     "dtcwt_loss_fwd_j2": (_I, "p lll p lll pp pp p ff l iii pppp i p"),

@@ -21,6 +21,14 @@
 //   depend on the parity of m/2 and on whether the call is a lowpass or a highpass one (lowlevel.py:154-239; the host builds
 //   the table, dtcwt_ifilt_taps below).
 //
+// Three-filter ("_bp", rotationally symmetric) banks: the diagonal band hh has a bandpass filter h2 of its own on both axes
+// (transform_funcs.py fwd_j1_rot, fwd_j2plus_rot, inv_j1_rot, inv_j2plus_rot); every kernel has a compile-time form BP for them.
+//   forward:  ba = row(x, h2),  hh = col(ba, h2);  ll, lh, hl as above.  Level 1: h2 has an odd length of its own (the halo is the
+//     largest half-length of the three).  Level >= 2: (h2b, h2a) is a highpass call, with the index formula of (h1b, h1a).
+//   inverse:  lo = col(lh, g1) + col(ll, g0),  hi = col(hl, g0),  ba = col(hh, g2);   y = (row(hi, g1) + row(lo, g0)) + row(ba, g2),
+//     the three row sums added in this order.  Level >= 2: (g2b, g2a) is a highpass call with a third table of dtcwt_ifilt_taps.
+//   The two-filter forms (BP = false) take the argument structs and compile to the instructions they had before BP existed.
+//
 // Every kernel: a block owns a tile of one (n, c) plane, stages its input patch (tile + halo) in LDS through the index map --
 // the inverses apply c2q while staging --, runs the first pass into LDS and the second into registers, applies q2c there and
 // stores.  The input is read once (plus the halo), every output written once, nothing intermediate leaves the CU; the taps
@@ -37,13 +45,15 @@ namespace faoctasr {
 // ---------------------------------------------------------------------------------------------------------------------------
 // level 1 forward
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool HIGHS>
+template <bool HIGHS, bool BP>
 __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x, DtLow xs, float* __restrict__ ll, float* __restrict__ hi,
                                                     DtStr hs, int vec, int C, int H, int W, int tiles_h, int tiles_w, int L0, int L1,
-                                                    int sym, DtTaps1 taps) {
+                                                    int sym, typename DtBank<BP>::T1 taps) {
+    static_assert(HIGHS || !BP, "the lowpass-only form has no third filter");
     __shared__ float patch[J1_PR][J1_PC];
     __shared__ __attribute__((aligned(16))) float mid_lo[J1_PR][J1_TW];
     __shared__ __attribute__((aligned(16))) float mid_hi[HIGHS ? J1_PR : 1][J1_TW];
+    __shared__ __attribute__((aligned(16))) float mid_ba[BP ? J1_PR : 1][J1_TW];
     const int tid = threadIdx.x;
     int b = blockIdx.x;
     const int tw = b % tiles_w; b /= tiles_w;
@@ -51,7 +61,7 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x,
     const long plane = b / tiles_h;
     const long n = plane / C, c = plane % C;
     const int oi0 = th * J1_TH, oj0 = tw * J1_TW;
-    const int hm = (L0 > L1 ? L0 : L1) >> 1, a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
+    const int hm = dt_halo1<BP>(L0, L1, taps), a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
     const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;               // <= J1_PR, J1_PC
     const float* xp = x + n * xs.n + c * xs.c;
 
@@ -75,6 +85,12 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x,
                 for (int t = 0; t < L1; ++t) hv = fmaf(taps.f1[t], patch[r][cc + t + a1], hv);
                 mid_hi[r][cc] = hv;
             }
+            if constexpr (BP) {
+                const int a2 = hm - (taps.L2 >> 1);
+                float bv = 0.f;
+                for (int t = 0; t < taps.L2; ++t) bv = fmaf(taps.f2[t], patch[r][cc + t + a2], bv);
+                mid_ba[r][cc] = bv;
+            }
         }
     }
     __syncthreads();
@@ -95,13 +111,21 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x,
             float2 u = make_float2(0.f, 0.f), p = u, q = u;
             for (int t = 0; t < L1; ++t) {
                 const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a1][2 * qj]);
-                const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a1][2 * qj]);
+                float2 w;
+                if constexpr (!BP) w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a1][2 * qj]);
                 u.x = fmaf(taps.f1[t], v.x, u.x); u.y = fmaf(taps.f1[t], v.y, u.y);
-                q.x = fmaf(taps.f1[t], w.x, q.x); q.y = fmaf(taps.f1[t], w.y, q.y);
+                if constexpr (!BP) { q.x = fmaf(taps.f1[t], w.x, q.x); q.y = fmaf(taps.f1[t], w.y, q.y); }
             }
             for (int t = 0; t < L0; ++t) {
                 const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a0][2 * qj]);
                 p.x = fmaf(taps.f0[t], w.x, p.x); p.y = fmaf(taps.f0[t], w.y, p.y);
+            }
+            if constexpr (BP) {                                           // hh = col(ba, h2)
+                const int a2 = hm - (taps.L2 >> 1);
+                for (int t = 0; t < taps.L2; ++t) {
+                    const float2 w = *reinterpret_cast<const float2*>(&mid_ba[2 * qi + d + t + a2][2 * qj]);
+                    q.x = fmaf(taps.f2[t], w.x, q.x); q.y = fmaf(taps.f2[t], w.y, q.y);
+                }
             }
             vlh[d] = u; vhl[d] = p; vhh[d] = q;
         }
@@ -122,12 +146,15 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x,
 // ---------------------------------------------------------------------------------------------------------------------------
 // level >= 2 forward: x [H, W] (multiples of 4) -> ll [H/2, W/2], six complex bands [H/4, W/4]
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool HIGHS>
+template <bool HIGHS, bool BP>
 __global__ __launch_bounds__(256) void dtcwt_fwd_j2(const float* __restrict__ x, DtLow xs, float* __restrict__ ll, float* __restrict__ hi,
-                                                    DtStr hs, int vec, int C, int H, int W, int tiles_h, int tiles_w, int m, DtTaps2 taps) {
+                                                    DtStr hs, int vec, int C, int H, int W, int tiles_h, int tiles_w, int m,
+                                                    typename DtBank<BP>::T2 taps) {
+    static_assert(HIGHS || !BP, "the lowpass-only form has no third filter");
     __shared__ __attribute__((aligned(16))) float patch[F2_PR][F2_PC];
     __shared__ __attribute__((aligned(16))) float mid_lo[F2_PR][F2_TW];
     __shared__ __attribute__((aligned(16))) float mid_hi[HIGHS ? F2_PR : 1][F2_TW];
+    __shared__ __attribute__((aligned(16))) float mid_ba[BP ? F2_PR : 1][F2_TW];
     const int tid = threadIdx.x;
     int b = blockIdx.x;
     const int tw = b % tiles_w; b /= tiles_w;
@@ -149,19 +176,22 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j2(const float* __restrict__ x,
     {   // W pass: tile column cc = 2 i + p; the float2 at patch column 4 i + 2 t holds the samples at offsets 2 - m and 3 - m
         const int cc = tid & 63, i = cc >> 1, p = cc & 1;
         for (int r = tid >> 6; r < rows; r += 4) {
-            float lo = 0.f, hv = 0.f;
+            float lo = 0.f, hv = 0.f, bv = 0.f;
             for (int t = 0; t < m; ++t) {
                 const float2 v = *reinterpret_cast<const float2*>(&patch[r][4 * i + 2 * t]);
                 lo = fmaf(p ? taps.lo1[t] : taps.lo0[t], p ? v.y : v.x, lo);
                 if (HIGHS) hv = fmaf(p ? taps.hi1[t] : taps.hi0[t], p ? v.x : v.y, hv);
+                if constexpr (BP) bv = fmaf(p ? taps.ba1[t] : taps.ba0[t], p ? v.x : v.y, bv);
             }
             mid_lo[r][cc] = lo;
             if (HIGHS) mid_hi[r][cc] = hv;
+            if constexpr (BP) mid_ba[r][cc] = bv;
         }
     }
     __syncthreads();
 
-    // H pass: 4 x 32 quads; threads 0..127 take the W-lowpass plane (ll, lh), threads 128..255 the W-highpass plane (hl, hh)
+    // H pass: 4 x 32 quads; threads 0..127 take the W-lowpass plane (ll, lh), threads 128..255 the W-highpass plane (hl, hh);
+    // BP: the latter take hl from the W-highpass plane and hh from the W-bandpass one, with the bandpass taps
     const int path = tid >> 7, qi = (tid & 127) >> 5, qj = tid & 31;
     if (!HIGHS && path) return;
     const int oi = 2 * (i0 + qi), oj = 2 * (j0 + qj);                      // top-left of the quad in ll
@@ -172,7 +202,13 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j2(const float* __restrict__ x,
         const float2 r0 = *reinterpret_cast<const float2*>(mp), r1 = *reinterpret_cast<const float2*>(mp + F2_TW);
         l0.x = fmaf(taps.lo0[t], r0.x, l0.x); l0.y = fmaf(taps.lo0[t], r0.y, l0.y);
         l1.x = fmaf(taps.lo1[t], r1.x, l1.x); l1.y = fmaf(taps.lo1[t], r1.y, l1.y);
-        if (HIGHS) {
+        if constexpr (BP) {
+            const float* bp = path ? &mid_ba[4 * qi + 2 * t][2 * qj] : mp;
+            const float2 b0 = *reinterpret_cast<const float2*>(bp), b1 = *reinterpret_cast<const float2*>(bp + F2_TW);
+            const float k0 = path ? taps.ba0[t] : taps.hi0[t], k1 = path ? taps.ba1[t] : taps.hi1[t];
+            h0.x = fmaf(k0, b1.x, h0.x); h0.y = fmaf(k0, b1.y, h0.y);
+            h1.x = fmaf(k1, b0.x, h1.x); h1.y = fmaf(k1, b0.y, h1.y);
+        } else if (HIGHS) {
             h0.x = fmaf(taps.hi0[t], r1.x, h0.x); h0.y = fmaf(taps.hi0[t], r1.y, h0.y);
             h1.x = fmaf(taps.hi1[t], r0.x, h1.x); h1.y = fmaf(taps.hi1[t], r0.y, h1.y);
         }
@@ -196,11 +232,12 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j2(const float* __restrict__ x,
 // ---------------------------------------------------------------------------------------------------------------------------
 // level 1 inverse: ll [H, W], six complex bands [H/2, W/2] (either may be null = zeros, its path is skipped) -> y [H, W]
 // ---------------------------------------------------------------------------------------------------------------------------
+template <bool BP>
 __global__ __launch_bounds__(256) void dtcwt_inv_j1(const float* __restrict__ ll, DtLow ls, const float* __restrict__ hi, DtStr hs,
                                                     float* __restrict__ y, int C, int H, int W, int tiles_h, int tiles_w, int L0, int L1,
-                                                    int sym, DtTaps1 taps) {
+                                                    int sym, typename DtBank<BP>::T1 taps) {
     __shared__ float cf[4][J1_PR][J1_PC];
-    __shared__ float mid_lo[J1_TH][J1_PC], mid_hi[J1_TH][J1_PC];
+    __shared__ float mid_lo[J1_TH][J1_PC], mid_hi[J1_TH][J1_PC], mid_ba[BP ? J1_TH : 1][J1_PC];
     const int tid = threadIdx.x;
     int b = blockIdx.x;
     const int tw = b % tiles_w; b /= tiles_w;
@@ -208,7 +245,7 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j1(const float* __restrict__ ll
     const long plane = b / tiles_h;
     const long n = plane / C, c = plane % C;
     const int t0 = th * J1_TH, s0 = tw * J1_TW;
-    const int hm = (L0 > L1 ? L0 : L1) >> 1, a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
+    const int hm = dt_halo1<BP>(L0, L1, taps), a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
     const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;
     const float* lp = ll ? ll + n * ls.n + c * ls.c : nullptr;
     const float* hp = hi ? hi + n * hs.n + c * hs.c : nullptr;
@@ -223,21 +260,27 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j1(const float* __restrict__ ll
     }
     __syncthreads();
 
-    // H pass: lo = col(lh, g1) + col(ll, g0), hi = col(hh, g1) + col(hl, g0), for every tile row and patch column
+    // H pass: lo = col(lh, g1) + col(ll, g0), hi = col(hh, g1) + col(hl, g0), for every tile row and patch column;
+    // BP: hi = col(hl, g0), ba = col(hh, g2)
     for (int tt = tid >> 6; tt < J1_TH; tt += 4) {
         for (int cc = tid & 63; cc < cols; cc += 64) {
             float l1 = 0.f, l0 = 0.f, h1 = 0.f, h0 = 0.f;
             if (hp) {
                 for (int t = 0; t < L1; ++t) {
                     l1 = fmaf(taps.f1[t], cf[1][tt + t + a1][cc], l1);
-                    h1 = fmaf(taps.f1[t], cf[3][tt + t + a1][cc], h1);
+                    if constexpr (!BP) h1 = fmaf(taps.f1[t], cf[3][tt + t + a1][cc], h1);
                 }
                 for (int t = 0; t < L0; ++t) h0 = fmaf(taps.f0[t], cf[2][tt + t + a0][cc], h0);
+                if constexpr (BP) {
+                    const int a2 = hm - (taps.L2 >> 1);
+                    for (int t = 0; t < taps.L2; ++t) h1 = fmaf(taps.f2[t], cf[3][tt + t + a2][cc], h1);
+                }
             }
             if (lp)
                 for (int t = 0; t < L0; ++t) l0 = fmaf(taps.f0[t], cf[0][tt + t + a0][cc], l0);
             mid_lo[tt][cc] = l1 + l0;
-            mid_hi[tt][cc] = h1 + h0;
+            if constexpr (BP) { mid_hi[tt][cc] = h0; mid_ba[tt][cc] = h1; }
+            else mid_hi[tt][cc] = h1 + h0;
         }
     }
     __syncthreads();
@@ -251,19 +294,29 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j1(const float* __restrict__ ll
         if (hp)
             for (int k = 0; k < L1; ++k) vh = fmaf(taps.f1[k], mid_hi[tt][ss + k + a1], vh);
         for (int k = 0; k < L0; ++k) vl = fmaf(taps.f0[k], mid_lo[tt][ss + k + a0], vl);
-        yp[(long)t * W + s] = vh + vl;
+        if constexpr (BP) {
+            const int a2 = hm - (taps.L2 >> 1);
+            float vb = 0.f;
+            if (hp)
+                for (int k = 0; k < taps.L2; ++k) vb = fmaf(taps.f2[k], mid_ba[tt][ss + k + a2], vb);
+            yp[(long)t * W + s] = (vh + vl) + vb;
+        } else {
+            yp[(long)t * W + s] = vh + vl;
+        }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // level >= 2 inverse: ll [R, Q], six complex bands [R/2, Q/2] (either may be null) -> y [2R, 2Q]; always symmetric
 // ---------------------------------------------------------------------------------------------------------------------------
+template <bool BP>
 __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll, DtLow ls, const float* __restrict__ hi, DtStr hs,
-                                                    float* __restrict__ y, int C, int R, int Q, int tiles_h, int tiles_w, int m2, DtTapsI taps) {
+                                                    float* __restrict__ y, int C, int R, int Q, int tiles_h, int tiles_w, int m2,
+                                                    typename DtBank<BP>::TI taps) {
     __shared__ float cf[4][I2_PR][I2_PC];
-    __shared__ float mid_lo[I2_TH][I2_PC], mid_hi[I2_TH][I2_PC];
-    __shared__ float tl[2][4][DT_MAXL / 2];
-    __shared__ int td[2][4];
+    __shared__ float mid_lo[I2_TH][I2_PC], mid_hi[I2_TH][I2_PC], mid_ba[BP ? I2_TH : 1][I2_PC];
+    __shared__ float tl[BP ? 3 : 2][4][DT_MAXL / 2];
+    __shared__ int td[BP ? 3 : 2][4];
     const int tid = threadIdx.x;
     int b = blockIdx.x;
     const int tw = b % tiles_w; b /= tiles_w;
@@ -279,8 +332,12 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll
     if (tid < 4 * (DT_MAXL / 2)) {                                        // the per-phase taps, for the lane-varying phase of the W pass
         tl[0][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.lo[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
         tl[1][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.hi[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
+        if constexpr (BP) tl[2][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.ba[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
     }
-    if (tid < 4) { td[0][tid] = taps.dlo[tid]; td[1][tid] = taps.dhi[tid]; }
+    if (tid < 4) {
+        td[0][tid] = taps.dlo[tid]; td[1][tid] = taps.dhi[tid];
+        if constexpr (BP) td[2][tid] = taps.dba[tid];
+    }
     for (int r = tid >> 6; r < rows; r += 4) {
         const int sr = dt_map(2 * i0 - m2 + r, R, 1);
         for (int cc = tid & 63; cc < cols; cc += 64)
@@ -291,19 +348,20 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll
     // H pass: a wave takes a tile row (its phase q is uniform), lanes the patch columns
     for (int tt = tid >> 6; tt < I2_TH; tt += 4) {
         const int q = tt & 3, ii = tt >> 2;                               // t0 is a multiple of 4
-        const int rl = 2 * ii + td[0][q], rh = 2 * ii + td[1][q];
+        const int rl = 2 * ii + td[0][q], rh = 2 * ii + td[1][q], rb = 2 * ii + td[BP ? 2 : 1][q];
         for (int cc = tid & 63; cc < cols; cc += 64) {
             float l1 = 0.f, l0 = 0.f, h1 = 0.f, h0 = 0.f;
             if (hp)
                 for (int t = 0; t < m2; ++t) {
                     l1 = fmaf(tl[1][q][t], cf[1][rh + 2 * t][cc], l1);
-                    h1 = fmaf(tl[1][q][t], cf[3][rh + 2 * t][cc], h1);
+                    h1 = fmaf(tl[BP ? 2 : 1][q][t], cf[3][rb + 2 * t][cc], h1);     // BP: ba = col(hh, g2)
                     h0 = fmaf(tl[0][q][t], cf[2][rl + 2 * t][cc], h0);
                 }
             if (lp)
                 for (int t = 0; t < m2; ++t) l0 = fmaf(tl[0][q][t], cf[0][rl + 2 * t][cc], l0);
             mid_lo[tt][cc] = l1 + l0;
-            mid_hi[tt][cc] = h1 + h0;
+            if constexpr (BP) { mid_hi[tt][cc] = h0; mid_ba[tt][cc] = h1; }
+            else mid_hi[tt][cc] = h1 + h0;
         }
     }
     __syncthreads();
@@ -318,7 +376,15 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll
         if (hp)
             for (int k = 0; k < m2; ++k) vh = fmaf(tl[1][q][k], mid_hi[tt][ch + 2 * k], vh);
         for (int k = 0; k < m2; ++k) vl = fmaf(tl[0][q][k], mid_lo[tt][cl + 2 * k], vl);
-        yp[(long)t * OW + s] = vh + vl;
+        if constexpr (BP) {
+            const int cb = 2 * jj + td[2][q];
+            float vb = 0.f;
+            if (hp)
+                for (int k = 0; k < m2; ++k) vb = fmaf(tl[2][q][k], mid_ba[tt][cb + 2 * k], vb);
+            yp[(long)t * OW + s] = (vh + vl) + vb;
+        } else {
+            yp[(long)t * OW + s] = vh + vl;
+        }
     }
 }
 
@@ -326,85 +392,178 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll
 
 using namespace faoctasr;
 
+// The entry points of a kernel's two forms share everything but the taps: run_* takes them checked and packed.
+template <bool BP>
+static int run_fwd_j1(const char* what, const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                      long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W, int L0, int L1,
+                      const typename DtBank<BP>::T1& t, int mode, faoctasr_stream_t stream) {
+    if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be even and at least 2", what, H, W);
+    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d", what, mode);
+    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
+    long blocks;
+    int rc;
+    if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
+    const DtLow xs{x_sn, x_sc, x_sr};
+    const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
+    if constexpr (BP) {
+        if (!hi) return fail(FAOCTASR_EINVAL, "%s: the lowpass alone takes no third filter, call dtcwt_fwd_j1", what);
+        hipLaunchKernelGGL((dtcwt_fwd_j1<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C,
+                           H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
+    } else if (hi) {
+        hipLaunchKernelGGL((dtcwt_fwd_j1<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C,
+                           H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
+    } else {
+        hipLaunchKernelGGL((dtcwt_fwd_j1<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, 0, C, H, W,
+                           tiles_h, tiles_w, L0, L1, mode == 1, t);
+    }
+    return check_launch(what);
+}
+
+template <bool BP>
+static int run_fwd_j2(const char* what, const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                      long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W, int m,
+                      const typename DtBank<BP>::T2& t, faoctasr_stream_t stream) {
+    if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
+    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be multiples of 4", what, H, W);
+    const int tiles_h = (H / 2 + F2_TH - 1) / F2_TH, tiles_w = (W / 2 + F2_TW - 1) / F2_TW;
+    long blocks;
+    int rc;
+    if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
+    const DtLow xs{x_sn, x_sc, x_sr};
+    const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
+    if constexpr (BP) {
+        if (!hi) return fail(FAOCTASR_EINVAL, "%s: the lowpass alone takes no third filter, call dtcwt_fwd_j2", what);
+        hipLaunchKernelGGL((dtcwt_fwd_j2<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C,
+                           H, W, tiles_h, tiles_w, m, t);
+    } else if (hi) {
+        hipLaunchKernelGGL((dtcwt_fwd_j2<true, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C,
+                           H, W, tiles_h, tiles_w, m, t);
+    } else {
+        hipLaunchKernelGGL((dtcwt_fwd_j2<false, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, 0, C, H, W,
+                           tiles_h, tiles_w, m, t);
+    }
+    return check_launch(what);
+}
+
+template <bool BP>
+static int run_inv_j1(const char* what, const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                      long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W, int L0, int L1,
+                      const typename DtBank<BP>::T1& t, int mode, faoctasr_stream_t stream) {
+    if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
+    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be even and at least 2", what, H, W);
+    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d", what, mode);
+    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
+    long blocks;
+    int rc;
+    if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
+    hipLaunchKernelGGL(dtcwt_inv_j1<BP>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
+                       DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
+    return check_launch(what);
+}
+
+template <bool BP>
+static int run_inv_j2(const char* what, const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                      long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W, int m,
+                      const typename DtBank<BP>::TI& t, faoctasr_stream_t stream) {
+    if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
+    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "%s: the result's H %d W %d must be multiples of 4", what, H, W);
+    const int tiles_h = (H + I2_TH - 1) / I2_TH, tiles_w = (W + I2_TW - 1) / I2_TW;
+    long blocks;
+    int rc;
+    if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
+    hipLaunchKernelGGL(dtcwt_inv_j2<BP>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
+                       DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H / 2, W / 2, tiles_h, tiles_w, m / 2, t);
+    return check_launch(what);
+}
+
 extern "C" int faoctasr_dtcwt_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
                                      const float* h0, int L0, const float* h1, int L1, int mode, faoctasr_stream_t stream) {
     DtTaps1 t;
-    int rc = dt_taps1("dtcwt_fwd_j1", h0, L0, h1, L1, &t);
+    const int rc = dt_taps1("dtcwt_fwd_j1", h0, L0, h1, L1, &t);
     if (rc) return rc;
-    if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j1: null pointer");
-    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j1: H %d W %d must be even and at least 2", H, W);
-    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j1: unknown padding mode %d", mode);
-    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
-    long blocks;
-    if ((rc = dt_blocks("dtcwt_fwd_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
-    const DtLow xs{x_sn, x_sc, x_sr};
-    const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
-    if (hi)
-        hipLaunchKernelGGL(dtcwt_fwd_j1<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C, H, W,
-                           tiles_h, tiles_w, L0, L1, mode == 1, t);
-    else
-        hipLaunchKernelGGL(dtcwt_fwd_j1<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, 0, C, H, W,
-                           tiles_h, tiles_w, L0, L1, mode == 1, t);
-    return check_launch("dtcwt_fwd_j1");
+    return run_fwd_j1<false>("dtcwt_fwd_j1", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, L0, L1, t,
+                             mode, stream);
+}
+
+extern "C" int faoctasr_dtcwt_fwd_j1_bp(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                                        long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
+                                        const float* h0, int L0, const float* h1, int L1, const float* h2, int L2, int mode,
+                                        faoctasr_stream_t stream) {
+    DtTaps1R t;
+    const int rc = dt_taps1r("dtcwt_fwd_j1_bp", h0, L0, h1, L1, h2, L2, &t);
+    if (rc) return rc;
+    return run_fwd_j1<true>("dtcwt_fwd_j1_bp", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, L0, L1,
+                            t, mode, stream);
 }
 
 extern "C" int faoctasr_dtcwt_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
                                      const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
                                      faoctasr_stream_t stream) {
-    int rc = dt_taps2_check("dtcwt_fwd_j2", h0a, h0b, h1a, h1b, m);
+    const int rc = dt_taps2_check("dtcwt_fwd_j2", h0a, h0b, h1a, h1b, m);
     if (rc) return rc;
-    if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j2: null pointer");
-    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "dtcwt_fwd_j2: H %d W %d must be multiples of 4", H, W);
-    const int tiles_h = (H / 2 + F2_TH - 1) / F2_TH, tiles_w = (W / 2 + F2_TW - 1) / F2_TW;
-    long blocks;
-    if ((rc = dt_blocks("dtcwt_fwd_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
     DtTaps2 t = {};
-    for (int k = 0; k < m; ++k) { t.lo0[k] = h0b[k]; t.lo1[k] = h0a[k]; t.hi0[k] = h1a[k]; t.hi1[k] = h1b[k]; }
-    const DtLow xs{x_sn, x_sc, x_sr};
-    const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
-    if (hi)
-        hipLaunchKernelGGL(dtcwt_fwd_j2<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C, H, W,
-                           tiles_h, tiles_w, m, t);
-    else
-        hipLaunchKernelGGL(dtcwt_fwd_j2<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, 0, C, H, W,
-                           tiles_h, tiles_w, m, t);
-    return check_launch("dtcwt_fwd_j2");
+    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, m);
+    return run_fwd_j2<false>("dtcwt_fwd_j2", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, m, t,
+                             stream);
+}
+
+extern "C" int faoctasr_dtcwt_fwd_j2_bp(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
+                                        long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
+                                        const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                                        const float* h2b, int m, faoctasr_stream_t stream) {
+    const int rc = dt_taps2r_check("dtcwt_fwd_j2_bp", h0a, h0b, h1a, h1b, h2a, h2b, m);
+    if (rc) return rc;
+    DtTaps2R t = {};
+    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, h2a, h2b, m);
+    return run_fwd_j2<true>("dtcwt_fwd_j2_bp", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, m, t,
+                            stream);
 }
 
 extern "C" int faoctasr_dtcwt_inv_j1(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
                                      const float* g0, int L0, const float* g1, int L1, int mode, faoctasr_stream_t stream) {
     DtTaps1 t;
-    int rc = dt_taps1("dtcwt_inv_j1", g0, L0, g1, L1, &t);
+    const int rc = dt_taps1("dtcwt_inv_j1", g0, L0, g1, L1, &t);
     if (rc) return rc;
-    if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j1: null pointer");
-    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j1: H %d W %d must be even and at least 2", H, W);
-    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j1: unknown padding mode %d", mode);
-    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
-    long blocks;
-    if ((rc = dt_blocks("dtcwt_inv_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
-    hipLaunchKernelGGL(dtcwt_inv_j1, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
-                       DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
-    return check_launch("dtcwt_inv_j1");
+    return run_inv_j1<false>("dtcwt_inv_j1", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, L0, L1, t, mode,
+                             stream);
+}
+
+extern "C" int faoctasr_dtcwt_inv_j1_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                                        long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
+                                        const float* g0, int L0, const float* g1, int L1, const float* g2, int L2, int mode,
+                                        faoctasr_stream_t stream) {
+    DtTaps1R t;
+    const int rc = dt_taps1r("dtcwt_inv_j1_bp", g0, L0, g1, L1, g2, L2, &t);
+    if (rc) return rc;
+    return run_inv_j1<true>("dtcwt_inv_j1_bp", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, L0, L1, t,
+                            mode, stream);
 }
 
 extern "C" int faoctasr_dtcwt_inv_j2(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
                                      const float* g0a, const float* g0b, const float* g1a, const float* g1b, int m,
                                      faoctasr_stream_t stream) {
-    int rc = dt_taps2_check("dtcwt_inv_j2", g0a, g0b, g1a, g1b, m);
+    const int rc = dt_taps2_check("dtcwt_inv_j2", g0a, g0b, g1a, g1b, m);
     if (rc) return rc;
-    if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j2: null pointer");
-    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "dtcwt_inv_j2: the result's H %d W %d must be multiples of 4", H, W);
-    const int tiles_h = (H + I2_TH - 1) / I2_TH, tiles_w = (W + I2_TW - 1) / I2_TW;
-    long blocks;
-    if ((rc = dt_blocks("dtcwt_inv_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
     DtTapsI t = {};
     dtcwt_ifilt_taps(g0b, g0a, m, 0, t.lo, t.dlo);                        // colifilt(X, g0b, g0a, False)
     dtcwt_ifilt_taps(g1b, g1a, m, 1, t.hi, t.dhi);                        // colifilt(X, g1b, g1a, True)
-    hipLaunchKernelGGL(dtcwt_inv_j2, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
-                       DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H / 2, W / 2, tiles_h, tiles_w, m / 2, t);
-    return check_launch("dtcwt_inv_j2");
+    return run_inv_j2<false>("dtcwt_inv_j2", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, m, t, stream);
+}
+
+extern "C" int faoctasr_dtcwt_inv_j2_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
+                                        long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
+                                        const float* g0a, const float* g0b, const float* g1a, const float* g1b, const float* g2a,
+                                        const float* g2b, int m, faoctasr_stream_t stream) {
+    const int rc = dt_taps2r_check("dtcwt_inv_j2_bp", g0a, g0b, g1a, g1b, g2a, g2b, m);
+    if (rc) return rc;
+    DtTapsIR t = {};
+    dtcwt_ifilt_taps(g0b, g0a, m, 0, t.lo, t.dlo);                        // colifilt(X, g0b, g0a, False)
+    dtcwt_ifilt_taps(g1b, g1a, m, 1, t.hi, t.dhi);                        // colifilt(X, g1b, g1a, True)
+    dtcwt_ifilt_taps(g2b, g2a, m, 1, t.ba, t.dba);                        // colifilt(X, g2b, g2a, True)
+    return run_inv_j2<true>("dtcwt_inv_j2_bp", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, m, t, stream);
 }

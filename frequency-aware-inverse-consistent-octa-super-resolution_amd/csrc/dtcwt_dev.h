@@ -16,11 +16,26 @@ struct DtLow { long n, c, r; };                  // lowpass input element stride
 struct DtTaps1 { float f0[DT_MAXL], f1[DT_MAXL]; };                      // level 1: lowpass, highpass
 struct DtTaps2 { float lo0[DT_MAXL], lo1[DT_MAXL], hi0[DT_MAXL], hi1[DT_MAXL]; };   // level >= 2 analysis, by output phase
 struct DtTapsI { float lo[4][DT_MAXL / 2], hi[4][DT_MAXL / 2]; int dlo[4], dhi[4]; };   // level >= 2 synthesis, by output phase q
+// the three-filter (rotationally symmetric, "_bp") banks: the two-filter taps and the bandpass filter of the diagonal band hh
+struct DtTaps1R : DtTaps1 { float f2[DT_MAXL]; int L2; };               // level 1: + bandpass, of its own odd length
+struct DtTaps2R : DtTaps2 { float ba0[DT_MAXL], ba1[DT_MAXL]; };        // level >= 2 analysis: + the bandpass pair, phased as hi0, hi1
+struct DtTapsIR : DtTapsI { float ba[4][DT_MAXL / 2]; int dba[4]; };    // level >= 2 synthesis: + a third (highpass-call) table
+// the tap structs of a kernel's two-filter (BP = false) and three-filter (BP = true) form
+template <bool BP> struct DtBank { using T1 = DtTaps1; using T2 = DtTaps2; using TI = DtTapsI; };
+template <> struct DtBank<true> { using T1 = DtTaps1R; using T2 = DtTaps2R; using TI = DtTapsIR; };
 
 // level-1 tiles (forward: of ll; inverse: of y) and the level >= 2 ones (forward: of ll = 4 x 32 quads; inverse: of y)
 constexpr int J1_TH = 16, J1_TW = 64, J1_PR = J1_TH + DT_MAXL - 2, J1_PC = J1_TW + DT_MAXL - 2;          // halo 2 * 9
 constexpr int F2_TH = 8, F2_TW = 64, F2_PR = 2 * F2_TH + 2 * DT_MAXL - 4, F2_PC = 2 * F2_TW + 2 * DT_MAXL - 4;
 constexpr int I2_TH = 32, I2_TW = 64, I2_PR = I2_TH / 2 + DT_MAXL, I2_PC = I2_TW / 2 + DT_MAXL;
+
+// level-1 halo: the largest half-length of the bank's filters
+template <bool BP>
+__device__ __forceinline__ int dt_halo1(int L0, int L1, const typename DtBank<BP>::T1& taps) {
+    int L = L0 > L1 ? L0 : L1;
+    if constexpr (BP) L = taps.L2 > L ? taps.L2 : L;
+    return L >> 1;
+}
 
 // index of the sample that position j of the extension reads; -1 for a zero
 __device__ __forceinline__ int dt_map(int j, int N, int sym) {
@@ -96,10 +111,41 @@ inline int dt_taps1(const char* what, const float* f0, int L0, const float* f1, 
     return FAOCTASR_OK;
 }
 
+// the third level-1 filter joins a checked two-filter set
+inline int dt_taps1r(const char* what, const float* f0, int L0, const float* f1, int L1, const float* f2, int L2, DtTaps1R* t) {
+    DtTaps1 two;
+    const int rc = dt_taps1(what, f0, L0, f1, L1, &two);
+    if (rc) return rc;
+    if (!f2) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
+    if (L2 < 3 || L2 >= DT_MAXL || !(L2 & 1))
+        return fail(FAOCTASR_EINVAL, "%s: level-1 third-filter tap count %d must be odd and within 3..%d", what, L2, DT_MAXL - 1);
+    *t = DtTaps1R{};
+    static_cast<DtTaps1&>(*t) = two;
+    for (int k = 0; k < L2; ++k) t->f2[k] = f2[k];
+    t->L2 = L2;
+    return FAOCTASR_OK;
+}
+
 inline int dt_taps2_check(const char* what, const float* a, const float* b, const float* c, const float* d, int m) {
     if (!a || !b || !c || !d) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
     if (m < 4 || m > DT_MAXL || (m & 1)) return fail(FAOCTASR_EINVAL, "%s: q-shift tap count %d must be even and within 4..%d", what, m, DT_MAXL);
     return FAOCTASR_OK;
+}
+
+inline int dt_taps2r_check(const char* what, const float* a, const float* b, const float* c, const float* d, const float* e, const float* f,
+                           int m) {
+    if (!e || !f) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
+    return dt_taps2_check(what, a, b, c, d, m);
+}
+
+// analysis taps by output phase: the lowpass call reads (h0b, h0a), the highpass calls (h1a, h1b) and (h2a, h2b)
+inline void dt_taps2_fill(DtTaps2* t, const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m) {
+    for (int k = 0; k < m; ++k) { t->lo0[k] = h0b[k]; t->lo1[k] = h0a[k]; t->hi0[k] = h1a[k]; t->hi1[k] = h1b[k]; }
+}
+inline void dt_taps2_fill(DtTaps2R* t, const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                          const float* h2b, int m) {
+    dt_taps2_fill(static_cast<DtTaps2*>(t), h0a, h0b, h1a, h1b, m);
+    for (int k = 0; k < m; ++k) { t->ba0[k] = h2a[k]; t->ba1[k] = h2b[k]; }
 }
 
 // the table of lowlevel.py:154-239: per output phase q the polyphase half and offset of colifilt(X, fa, fb, highpass)

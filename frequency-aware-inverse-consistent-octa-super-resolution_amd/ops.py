@@ -1383,21 +1383,45 @@ def dtcwt_sizes(H, W, J):
     return out
 
 
-def _dtcwt_taps1(f0, f1):
+def _dtcwt_taps1(f0, f1, f2=None):
+    """The level-1 taps as host tuples: (f0, f1), or (f0, f1, f2) with the third (bandpass) filter of a three-filter bank."""
     f0, f1 = host_taps(f0), host_taps(f1)
     for f in (f0, f1):
         if len(f) % 2 == 0 or not 3 <= len(f) < DTCWT_MAX_TAPS:
             raise ValueError("filter length %d: the level-1 filters take an odd number of taps, 3 to %d" % (len(f), DTCWT_MAX_TAPS - 1))
-    return f0, f1
+    if f2 is None:
+        return f0, f1
+    f2 = host_taps(f2)
+    if len(f2) % 2 == 0 or not 3 <= len(f2) < DTCWT_MAX_TAPS:
+        raise ValueError("filter length %d: the third level-1 filter takes an odd number of taps, 3 to %d" % (len(f2), DTCWT_MAX_TAPS - 1))
+    return f0, f1, f2
 
 
-def _dtcwt_taps2(fa0, fb0, fa1, fb1):
+def _dtcwt_taps2(fa0, fb0, fa1, fb1, fa2=None, fb2=None):
+    """The q-shift taps as host tuples: (a0, b0, a1, b1), or with the third pair of a three-filter bank (a0, b0, a1, b1, a2, b2)."""
     f = tuple(host_taps(t) for t in (fa0, fb0, fa1, fb1))
     if len(set(len(t) for t in f)) != 1:
         raise ValueError("the four q-shift filters must have the same length, got %s" % [len(t) for t in f])
     if len(f[0]) % 2 or not 4 <= len(f[0]) <= DTCWT_MAX_TAPS:
         raise ValueError("filter length %d: the q-shift filters take an even number of taps, 4 to %d" % (len(f[0]), DTCWT_MAX_TAPS))
-    return f
+    if fa2 is None and fb2 is None:
+        return f
+    if fa2 is None or fb2 is None:
+        raise ValueError("the third q-shift filters come as a pair (tree a, tree b), got one of them")
+    g = (host_taps(fa2), host_taps(fb2))
+    if any(len(t) != len(f[0]) for t in g):
+        raise ValueError("the third q-shift filters must have the length of the other four (%d), got %s" % (len(f[0]), [len(t) for t in g]))
+    return f + g
+
+
+def _taps1_args(taps):
+    """(pointer, length) of every level-1 filter, as the entry points take them."""
+    return tuple(a for t in taps for a in (_tap_array(t), len(t)))
+
+
+def _bp(name, taps, level1):
+    """The entry point of a launch: the ``_bp`` twin where the taps carry a third filter."""
+    return name + "_bp" if len(taps) == (3 if level1 else 6) else name
 
 
 def _dtcwt_dev(t, what):
@@ -1454,12 +1478,14 @@ def _dtcwt_forward(x, taps, level1, mode, names, want_ll=True, want_hi=True):
         size = {"n": N, "c": C, "o": 6, "h": lh // 2, "w": lw // 2, "r": 2}
         hi = torch.empty(tuple(size[k] for k in names), dtype=torch.float32, device=x.device)
         st, vec = _dtcwt_high_strides(hi, names)
+    if not want_hi:                         # the lowpass of a three-filter bank is the two-filter one: the existing entry
+        taps = taps[:2] if level1 else taps[:4]
     if level1:
-        call("dtcwt_fwd_j1", x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, _tap_array(taps[0]), len(taps[0]),
-             _tap_array(taps[1]), len(taps[1]), mode, stream_ptr())
-    else:
-        call("dtcwt_fwd_j2", x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]),
+        call(_bp("dtcwt_fwd_j1", taps, True), x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, *_taps1_args(taps), mode,
              stream_ptr())
+    else:
+        call(_bp("dtcwt_fwd_j2", taps, False), x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W,
+             *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
     return ll, hi
 
 
@@ -1490,15 +1516,15 @@ def _dtcwt_inverse(ll, hi, taps, level1, mode, names):
     y = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
     lp, hp = (ll.data_ptr() if ll is not None else None), (hi.data_ptr() if hi is not None else None)
     if level1:
-        call("dtcwt_inv_j1", lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, _tap_array(taps[0]), len(taps[0]), _tap_array(taps[1]),
-             len(taps[1]), mode, stream_ptr())
+        call(_bp("dtcwt_inv_j1", taps, True), lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *_taps1_args(taps), mode, stream_ptr())
     else:
-        call("dtcwt_inv_j2", lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+        call(_bp("dtcwt_inv_j2", taps, False), lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]),
+             stream_ptr())
     return y
 
 
 def _swap_ab(t):
-    return (t[1], t[0], t[3], t[2])
+    return (t[1], t[0], t[3], t[2]) + ((t[5], t[4]) if len(t) == 6 else ())
 
 
 class _DTCWTFwd(Function):
@@ -1561,30 +1587,34 @@ class _DTCWTInvJ2(_DTCWTInv):
     """transform_funcs.py:452-488 INV_J2PLUS."""
 
 
-def dtcwt_fwd_j1(x, h0o, h1o, skip_hps=False, o_dim=2, ri_dim=-1, mode=1):
+def dtcwt_fwd_j1(x, h0o, h1o, skip_hps=False, o_dim=2, ri_dim=-1, mode=1, h2o=None):
     """Level 1 of the forward transform: x (N, C, H, W), H and W even -> (ll (N, C, H, W), highs in the ``o_dim`` / ``ri_dim`` layout,
     default (N, C, 6, H/2, W/2, 2)).  The filters are tensors or sequences as the modules register them (taps reversed).
-    ``mode`` 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code pads with zeros, as the reference does."""
+    ``mode`` 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code pads with zeros, as the reference does.
+    ``h2o``: the bandpass filter of a three-filter bank (fwd_j1_rot), which the diagonal orientations then take on both axes."""
     names = dtcwt_layout(o_dim, ri_dim)
-    return _DTCWTFwdJ1.apply(x, _dtcwt_taps1(h0o, h1o), True, bool(skip_hps), names, int(mode))
+    return _DTCWTFwdJ1.apply(x, _dtcwt_taps1(h0o, h1o, h2o), True, bool(skip_hps), names, int(mode))
 
 
-def dtcwt_fwd_j2(x, h0a, h0b, h1a, h1b, skip_hps=False, o_dim=2, ri_dim=-1):
-    """A level >= 2 of the forward transform: x (N, C, H, W), multiples of 4 -> (ll (N, C, H/2, W/2), highs (.., H/4, W/4, ..))."""
+def dtcwt_fwd_j2(x, h0a, h0b, h1a, h1b, skip_hps=False, o_dim=2, ri_dim=-1, h2a=None, h2b=None):
+    """A level >= 2 of the forward transform: x (N, C, H, W), multiples of 4 -> (ll (N, C, H/2, W/2), highs (.., H/4, W/4, ..)).
+    ``h2a``, ``h2b``: the bandpass pair of a three-filter bank (fwd_j2plus_rot)."""
     names = dtcwt_layout(o_dim, ri_dim)
-    return _DTCWTFwdJ2.apply(x, _dtcwt_taps2(h0a, h0b, h1a, h1b), False, bool(skip_hps), names, 1)
+    return _DTCWTFwdJ2.apply(x, _dtcwt_taps2(h0a, h0b, h1a, h1b, h2a, h2b), False, bool(skip_hps), names, 1)
 
 
-def dtcwt_inv_j1(ll, highs, g0o, g1o, o_dim=2, ri_dim=-1, mode=1):
-    """Level 1 of the inverse: ll (N, C, H, W) and highs (.., H/2, W/2, ..) -> y (N, C, H, W); either may be None for zeros."""
+def dtcwt_inv_j1(ll, highs, g0o, g1o, o_dim=2, ri_dim=-1, mode=1, g2o=None):
+    """Level 1 of the inverse: ll (N, C, H, W) and highs (.., H/2, W/2, ..) -> y (N, C, H, W); either may be None for zeros.
+    ``g2o``: the bandpass filter of a three-filter bank (inv_j1_rot)."""
     names = dtcwt_layout(o_dim, ri_dim)
-    return _DTCWTInvJ1.apply(ll, highs, _dtcwt_taps1(g0o, g1o), True, names, int(mode))
+    return _DTCWTInvJ1.apply(ll, highs, _dtcwt_taps1(g0o, g1o, g2o), True, names, int(mode))
 
 
-def dtcwt_inv_j2(ll, highs, g0a, g0b, g1a, g1b, o_dim=2, ri_dim=-1):
-    """A level >= 2 of the inverse: ll (N, C, R, Q) and highs (.., R/2, Q/2, ..) -> y (N, C, 2R, 2Q); either may be None."""
+def dtcwt_inv_j2(ll, highs, g0a, g0b, g1a, g1b, o_dim=2, ri_dim=-1, g2a=None, g2b=None):
+    """A level >= 2 of the inverse: ll (N, C, R, Q) and highs (.., R/2, Q/2, ..) -> y (N, C, 2R, 2Q); either may be None.
+    ``g2a``, ``g2b``: the bandpass pair of a three-filter bank (inv_j2plus_rot)."""
     names = dtcwt_layout(o_dim, ri_dim)
-    return _DTCWTInvJ2.apply(ll, highs, _dtcwt_taps2(g0a, g0b, g1a, g1b), False, names, 1)
+    return _DTCWTInvJ2.apply(ll, highs, _dtcwt_taps2(g0a, g0b, g1a, g1b, g2a, g2b), False, names, 1)
 
 
 # ----------------------------------------------------------------------------------------
@@ -1808,11 +1838,11 @@ def _scat_fwd(x, taps, level1, mode, bias, low, pool, mag, phase, colour):
     x, sn, sc, sr = _dtcwt_low(x)
     b = float(bias)
     if level1:
-        call("scat_fwd_j1", x.data_ptr(), sn, sc, sr, *_scat_low(low), int(pool), *_scat_mag(mag, colour), ptr(phase), int(colour), b, b * b,
-             N, C, H, W, _tap_array(taps[0]), len(taps[0]), _tap_array(taps[1]), len(taps[1]), mode, stream_ptr())
+        call(_bp("scat_fwd_j1", taps, True), x.data_ptr(), sn, sc, sr, *_scat_low(low), int(pool), *_scat_mag(mag, colour), ptr(phase),
+             int(colour), b, b * b, N, C, H, W, *_taps1_args(taps), mode, stream_ptr())
     else:
-        call("scat_fwd_j2", x.data_ptr(), sn, sc, sr, *_scat_low(low), *_scat_mag(mag, colour), ptr(phase), int(colour), b, b * b,
-             N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+        call(_bp("scat_fwd_j2", taps, False), x.data_ptr(), sn, sc, sr, *_scat_low(low), *_scat_mag(mag, colour), ptr(phase), int(colour), b,
+             b * b, N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
 
 
 def _scat_bwd(dlow, pool, dmag, phase, taps, level1, mode, colour, shape):
@@ -1820,11 +1850,11 @@ def _scat_bwd(dlow, pool, dmag, phase, taps, level1, mode, colour, shape):
     N, C, H, W = shape
     dx = torch.empty(shape, dtype=torch.float32, device=phase.device)
     if level1:
-        call("scat_bwd_j1", *_scat_low(dlow), int(pool), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W, _tap_array(taps[0]),
-             len(taps[0]), _tap_array(taps[1]), len(taps[1]), mode, stream_ptr())
+        call(_bp("scat_bwd_j1", taps, True), *_scat_low(dlow), int(pool), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W,
+             *_taps1_args(taps), mode, stream_ptr())
     else:
-        call("scat_bwd_j2", *_scat_low(dlow), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W, *(_tap_array(t) for t in taps),
-             len(taps[0]), stream_ptr())
+        call(_bp("scat_bwd_j2", taps, False), *_scat_low(dlow), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W,
+             *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
     return dx
 
 
@@ -1918,21 +1948,27 @@ class _ScatJ2(Function):
         return (dx,) + (None,) * 6
 
 
-def scat_layer_j1(x, h0o, h1o, mode=1, magbias=1e-2, combine_colour=False):
+def scat_layer_j1(x, h0o, h1o, mode=1, magbias=1e-2, combine_colour=False, h2o=None):
     """One order of scattering at one scale: x (N, C, H, W), H and W even -> Z (N, 7, C, H/2, W/2): the 2x2 mean of the level-1
     lowpass, then ``sqrt(re^2 + im^2 + magbias^2) - magbias`` of the six orientations; with ``combine_colour`` (C == 3) the
     magnitude runs over the three channels too and Z is (N, 9, H/2, W/2).  Filters as the modules register them (taps reversed);
-    ``mode`` 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code pads with zeros."""
-    taps = _dtcwt_taps1(h0o, h1o)
+    ``mode`` 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code pads with zeros.  ``h2o``: the bandpass filter
+    of a three-filter bank (ScatLayerj1_rot_f)."""
+    taps = _dtcwt_taps1(h0o, h1o, h2o)
     _scat_check(x, None, int(mode), combine_colour)
     return _ScatJ1.apply(x, taps, int(mode), float(magbias), bool(combine_colour), torch.is_grad_enabled() and x.requires_grad)
 
 
-def scat_layer_j2(x, h0o, h1o, h0a, h0b, h1a, h1b, mode=1, magbias=1e-2, combine_colour=False):
+def scat_layer_j2(x, h0o, h1o, h0a, h0b, h1a, h1b, mode=1, magbias=1e-2, combine_colour=False, h2o=None, h2a=None, h2b=None):
     """Second-order scattering over two scales: x (N, C, H, W), multiples of 8 -> Z (N, 49, C, H/4, W/4): the lowpass, the six
     first-order magnitudes of level 1 (pooled) and of level 2, and the 36 second-order ones (index 6 o2 + o1); with
-    ``combine_colour`` (N, 51, H/4, W/4) = 3 + 6 + 6 + 36.  Only ``mode`` 1 (symmetric), as in the reference."""
-    taps1, taps2 = _dtcwt_taps1(h0o, h1o), _dtcwt_taps2(h0a, h0b, h1a, h1b)
+    ``combine_colour`` (N, 51, H/4, W/4) = 3 + 6 + 6 + 36.  Only ``mode`` 1 (symmetric), as in the reference.  ``h2o``, ``h2a``,
+    ``h2b``: the bandpass filters of a three-filter bank (ScatLayerj2_rot_f), all three or none."""
+    third = [t is not None for t in (h2o, h2a, h2b)]
+    if any(third) and not all(third):
+        raise ValueError("a three-filter bank takes all of h2o, h2a and h2b; got only %s"
+                         % ", ".join(n for n, g in zip(("h2o", "h2a", "h2b"), third) if g))
+    taps1, taps2 = _dtcwt_taps1(h0o, h1o, h2o), _dtcwt_taps2(h0a, h0b, h1a, h1b, h2a, h2b)
     _scat_check(x, taps2, int(mode), combine_colour)
     return _ScatJ2.apply(x, taps1, taps2, int(mode), float(magbias), bool(combine_colour), torch.is_grad_enabled() and x.requires_grad)
 

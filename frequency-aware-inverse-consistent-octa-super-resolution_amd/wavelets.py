@@ -489,30 +489,67 @@ def dtcwt_qshift(name):
     return _dtcwt_provider("qshift", name)[:8]
 
 
-def _dtcwt_taps(biort, qshift, analysis):
+def dtcwt_biort_bp(name):
+    """(h0o, g0o, h1o, g1o, h2o, g2o) of a three-filter level-1 bank ('near_sym_b_bp'), the reference's ``coeffs.biort`` order;
+    provider only.  ``ScatLayer(biort=(b[0], b[2], b[4]))`` builds the layer the reference names 'near_sym_b_bp'."""
+    taps = _dtcwt_provider("biort", name)
+    if len(taps) != 6:
+        raise ValueError("%r is no three-filter level-1 bank: its table lists %d filters, not 6" % (name, len(taps)))
+    return taps
+
+
+def dtcwt_qshift_bp(name):
+    """(h0a, h0b, g0a, g0b, h1a, h1b, g1a, g1b, h2a, h2b, g2a, g2b) of a three-filter q-shift bank ('qshift_b_bp'), the
+    reference's ``coeffs.qshift`` order; provider only.  The analysis 6-tuple is ``(q[0], q[1], q[4], q[5], q[8], q[9])``."""
+    taps = _dtcwt_provider("qshift", name)
+    if len(taps) != 12:
+        raise ValueError("%r is no three-filter q-shift bank: its table lists %d filters, not 12" % (name, len(taps)))
+    return taps
+
+
+def _dtcwt_taps(biort, qshift, analysis, three=True):
+    """The taps of a bank as float64 arrays, level 1 first: 2 (+ 4) of a two-filter bank, 3 (+ 6) of a three-filter one (the
+    rotationally symmetric banks, given as tuples; ``three`` False refuses them)."""
     if isinstance(biort, str):
         b = dtcwt_biort(biort)
         biort = (b[0], b[2]) if analysis else (b[1], b[3])
-    elif len(biort) != 2:
-        raise ValueError("biort must be a name or a 2-tuple of tap sequences (lowpass, highpass); got %d sequences" % len(biort))
+    elif len(biort) != 2 and not (three and len(biort) == 3):
+        raise ValueError("biort must be a name or a 2-tuple of tap sequences (lowpass, highpass)%s; got %d sequences"
+                         % (", or a 3-tuple (lowpass, highpass, bandpass) of a three-filter bank" if three else "", len(biort)))
     if qshift is None:                      # a level-1 bank alone (ScatLayer)
         qshift = ()
     elif isinstance(qshift, str):
         q = dtcwt_qshift(qshift)
         qshift = (q[0], q[1], q[4], q[5]) if analysis else (q[2], q[3], q[6], q[7])
-    elif len(qshift) != 4:
-        raise ValueError("qshift must be a name or a 4-tuple of tap sequences (tree a low, tree b low, tree a high, tree b high); got %d "
-                         "sequences" % len(qshift))
+    elif len(qshift) != 4 and not (three and len(qshift) == 6):
+        raise ValueError("qshift must be a name or a 4-tuple of tap sequences (tree a low, tree b low, tree a high, tree b high)%s; got "
+                         "%d sequences" % (", or a 6-tuple with the bandpass pair of a three-filter bank" if three else "", len(qshift)))
+    if qshift and (len(biort) == 3) != (len(qshift) == 6):
+        raise ValueError("a three-filter biort (3 tap sequences) goes with a three-filter qshift (6 tap sequences) and a two-filter "
+                         "one with a two-filter one; got %d and %d sequences" % (len(biort), len(qshift)))
     taps = [np.asarray(torch.as_tensor(t).detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=np.float64).ravel()
             for t in tuple(biort) + tuple(qshift)]
-    ops._dtcwt_taps1(taps[0], taps[1])
+    ops._dtcwt_taps1(*taps[:len(biort)])
     if qshift:
-        ops._dtcwt_taps2(*taps[2:])
+        ops._dtcwt_taps2(*taps[len(biort):])
     return taps
 
 
+def _bp_names(names, taps, order):
+    """The tap names of a module whose bank may carry third filters: ``names`` as they stand for 2 / 6 taps; for 3 / 9 the
+    names of ``taps``' order (level 1, then the q-shift pairs) and the order the module registers them in (``order``: the
+    reference's, which a state dict follows).  Returns (names in registration order, taps in that order)."""
+    if len(taps) == len(names):
+        return names, taps
+    p = names[0][0]                         # 'h' or 'g'
+    given = (p + "0o", p + "1o", p + "2o", p + "0a", p + "0b", p + "1a", p + "1b", p + "2a", p + "2b")[:len(taps)]
+    by_name = dict(zip(given, taps))
+    reg = tuple(n for n in order if n in by_name)
+    return reg, [by_name[n] for n in reg]
+
+
 def _register_dtcwt(module, taps):
-    """prep_filt (dtcwt/lowlevel.py:58-67): shape (1, 1, L, 1), the taps reversed."""
+    """prep_filt (dtcwt/lowlevel.py:58-67): shape (1, 1, L, 1), the taps reversed; ``taps`` in the order of ``module._tap_names``."""
     for name, t in zip(module._tap_names, taps):
         module.register_buffer(name, torch.tensor(np.ascontiguousarray(t[::-1]), dtype=torch.get_default_dtype()).reshape(1, 1, -1, 1))
     _record(module, module._tap_names)
@@ -537,7 +574,10 @@ class DTCWTForward(_TapModule):
     level's lowpass (a 0-d zero where not asked for).  A level in ``skip_hps`` computes its lowpass only and returns a 0-d zero.
     ``biort``: 'legall' or 'near_sym_a' (built from their closed forms), another name if ``pytorch_wavelets.dtcwt.coeffs`` or
     ``dtcwt.coeffs`` is importable, or a 2-tuple (h0o, h1o) of odd length 3..19; ``qshift``: a provider's name or a 4-tuple
-    (h0a, h0b, h1a, h1b) of one even length 4..``ops.DTCWT_MAX_TAPS``.  ``mode`` acts on level 1 only: 'symmetric', or zero padding
+    (h0a, h0b, h1a, h1b) of one even length 4..``ops.DTCWT_MAX_TAPS``.  A 3-tuple (h0o, h1o, h2o) with a 6-tuple (h0a, h0b, h1a, h1b,
+    h2a, h2b) is a rotationally symmetric three-filter bank (the reference's near_sym_b_bp / qshift_b_bp, whose names stay refused
+    for want of their tables): the diagonal bands take the bandpass filters h2 on both axes, the buffers ``h2o, h2a, h2b`` follow the
+    six, ``bandpass_diag`` is True and the launches are the ``_bp`` entry points of csrc/dtcwt.hip.  ``mode`` acts on level 1 only: 'symmetric', or zero padding
     for any other name; the later levels always extend symmetrically.  An odd side has its last row / column repeated; a lowpass
     side that is no multiple of 4 has its first and last row / column repeated before the next level (torch ops outside the
     kernels -- the sizes 192, 256, 512 never take them up to J = 3).  Otherwise a forward is J launches of csrc/dtcwt.hip."""
@@ -551,7 +591,9 @@ class DTCWTForward(_TapModule):
             raise ValueError("Orientations and real/imaginary parts must be in different dimensions.")
         ops.dtcwt_layout(o_dim, ri_dim)
         self.biort, self.qshift, self.J, self.o_dim, self.ri_dim, self.mode = biort, qshift, J, o_dim, ri_dim, mode
-        _register_dtcwt(self, _dtcwt_taps(biort, qshift, analysis=True))
+        self._tap_names, taps = _bp_names(self._tap_names, _dtcwt_taps(biort, qshift, analysis=True), self._tap_names + ("h2o", "h2a", "h2b"))
+        self.bandpass_diag = len(taps) == 9     # a three-filter bank: the diagonal bands on a bandpass filter of their own
+        _register_dtcwt(self, taps)
         self.skip_hps = _per_level(skip_hps, J, "skip_hps")
         self.include_scale = _per_level(include_scale, J, "include_scale")
 
@@ -566,14 +608,16 @@ class DTCWTForward(_TapModule):
             x = torch.cat((x, x[:, :, -1:]), dim=2)
         if x.shape[3] % 2:
             x = torch.cat((x, x[:, :, :, -1:]), dim=3)
-        low, h = ops.dtcwt_fwd_j1(x, self.h0o, self.h1o, self.skip_hps[0], self.o_dim, self.ri_dim, mode)
+        bp = self.bandpass_diag
+        low, h = ops.dtcwt_fwd_j1(x, self.h0o, self.h1o, self.skip_hps[0], self.o_dim, self.ri_dim, mode, self.h2o if bp else None)
         highs, scales = [h], [low if self.include_scale[0] else None]
         for j in range(1, self.J):
             if low.shape[2] % 4:
                 low = torch.cat((low[:, :, 0:1], low, low[:, :, -1:]), dim=2)
             if low.shape[3] % 4:
                 low = torch.cat((low[:, :, :, 0:1], low, low[:, :, :, -1:]), dim=3)
-            low, h = ops.dtcwt_fwd_j2(low, self.h0a, self.h0b, self.h1a, self.h1b, self.skip_hps[j], self.o_dim, self.ri_dim)
+            low, h = ops.dtcwt_fwd_j2(low, self.h0a, self.h0b, self.h1a, self.h1b, self.skip_hps[j], self.o_dim, self.ri_dim,
+                                      self.h2a if bp else None, self.h2b if bp else None)
             highs.append(h)
             scales.append(low if self.include_scale[j] else None)
         if True in self.include_scale:
@@ -596,7 +640,9 @@ class DTCWTInverse(_TapModule):
             raise ValueError("Orientations and real/imaginary parts must be in different dimensions.")
         self._names = ops.dtcwt_layout(o_dim, ri_dim)
         self.biort, self.qshift, self.o_dim, self.ri_dim, self.mode = biort, qshift, o_dim, ri_dim, mode
-        _register_dtcwt(self, _dtcwt_taps(biort, qshift, analysis=False))
+        self._tap_names, taps = _bp_names(self._tap_names, _dtcwt_taps(biort, qshift, analysis=False), self._tap_names + ("g2o", "g2a", "g2b"))
+        self.bandpass_diag = len(taps) == 9
+        _register_dtcwt(self, taps)
 
     def _fit(self, low, h):
         if _missing(low) or _missing(h) or h.dim() != 6:
@@ -613,11 +659,13 @@ class DTCWTInverse(_TapModule):
         mode = mode_to_int(self.mode)
         _prime(self, self._tap_names)
         low = None if _missing(low) else low
+        bp = self.bandpass_diag
         for h in list(highs)[:0:-1]:
             h = None if _missing(h) else h
-            low = ops.dtcwt_inv_j2(self._fit(low, h), h, self.g0a, self.g0b, self.g1a, self.g1b, self.o_dim, self.ri_dim)
+            low = ops.dtcwt_inv_j2(self._fit(low, h), h, self.g0a, self.g0b, self.g1a, self.g1b, self.o_dim, self.ri_dim,
+                                   self.g2a if bp else None, self.g2b if bp else None)
         h = None if _missing(highs[0]) else highs[0]
-        return ops.dtcwt_inv_j1(self._fit(low, h), h, self.g0o, self.g1o, self.o_dim, self.ri_dim, mode)
+        return ops.dtcwt_inv_j1(self._fit(low, h), h, self.g0o, self.g1o, self.o_dim, self.ri_dim, mode, self.g2o if bp else None)
 
 
 # ----------------------------------------------------------------------------------------
@@ -634,8 +682,15 @@ def _register_scat(module, taps):
 def _refuse_bp(biort, qshift):
     for name in (biort, qshift):
         if isinstance(name, str) and name.endswith("_bp"):
-            raise NotImplementedError("%r: the rotationally symmetric three-filter variants (near_sym_b_bp / qshift_b_bp) need a third "
-                                      "filter path in every kernel of csrc/scat.hip and are not built" % name)
+            raise NotImplementedError("%r: the name is not resolved.  The rotationally symmetric three-filter variants (near_sym_b_bp / "
+                                      "qshift_b_bp) run on the third filter path of csrc/dtcwt.hip and csrc/scat.hip, but their tap "
+                                      "tables are not this package's data: pass the taps, a 3-tuple (h0o, h1o, h2o) as biort and a "
+                                      "6-tuple (h0a, h0b, h1a, h1b, h2a, h2b) as qshift (wavelets.dtcwt_biort_bp / dtcwt_qshift_bp read "
+                                      "them from an installed provider).  DTCWTMagnitudeLoss takes two-filter banks only" % name)
+
+
+#: the reference's registration order of a three-filter scattering layer's parameters (scatternet/layers.py)
+_SCAT_BP_ORDER = ("h0o", "h1o", "h2o", "h0a", "h0b", "h1a", "h1b", "h2a", "h2b")
 
 
 def _scat_taps(biort, qshift):
@@ -656,8 +711,9 @@ class ScatLayer(_TapModule):
     def __init__(self, biort="near_sym_a", mode="symmetric", magbias=1e-2, combine_colour=False):
         super().__init__()
         self.biort, self.mode_str, self.mode, self.magbias, self.combine_colour = biort, mode, mode_to_int(mode), magbias, combine_colour
-        self.bandpass_diag = False
-        _register_scat(self, _scat_taps(biort, None))
+        self._tap_names, taps = _bp_names(self._tap_names, _scat_taps(biort, None), _SCAT_BP_ORDER)
+        self.bandpass_diag = len(taps) == 3     # a three-filter bank (the reference's biort='near_sym_b_bp')
+        _register_scat(self, taps)
 
     def forward(self, x):
         if x.dim() != 4:
@@ -669,7 +725,7 @@ class ScatLayer(_TapModule):
             x = torch.cat((x, x[:, :, -1:]), dim=2)
         if x.shape[3] % 2:
             x = torch.cat((x, x[:, :, :, -1:]), dim=3)
-        Z = ops.scat_layer_j1(x, self.h0o, self.h1o, self.mode, self.magbias, self.combine_colour)
+        Z = ops.scat_layer_j1(x, self.h0o, self.h1o, self.mode, self.magbias, self.combine_colour, self.h2o if self.bandpass_diag else None)
         return Z if self.combine_colour else Z.view(Z.shape[0], 7 * Z.shape[2], Z.shape[3], Z.shape[4])
 
     def extra_repr(self):
@@ -689,8 +745,10 @@ class ScatLayerj2(_TapModule):
     def __init__(self, biort="near_sym_a", qshift="qshift_a", mode="symmetric", magbias=1e-2, combine_colour=False):
         super().__init__()
         self.biort, self.qshift, self.mode_str, self.mode = biort, qshift, mode, mode_to_int(mode)
-        self.magbias, self.combine_colour, self.bandpass_diag = magbias, combine_colour, False
-        _register_scat(self, _scat_taps(biort, qshift))
+        self.magbias, self.combine_colour = magbias, combine_colour
+        self._tap_names, taps = _bp_names(self._tap_names, _scat_taps(biort, qshift), _SCAT_BP_ORDER)
+        self.bandpass_diag = len(taps) == 9
+        _register_scat(self, taps)
 
     def forward(self, x):
         if self.mode != 1:
@@ -707,7 +765,9 @@ class ScatLayerj2(_TapModule):
                 before, after = (8 - rem) // 2, (9 - rem) // 2
                 n = x.shape[dim]
                 x = torch.cat((x.narrow(dim, 0, before), x, x.narrow(dim, n - after, after)), dim=dim)
-        Z = ops.scat_layer_j2(x, self.h0o, self.h1o, self.h0a, self.h0b, self.h1a, self.h1b, self.mode, self.magbias, self.combine_colour)
+        third = (self.h2o, self.h2a, self.h2b) if self.bandpass_diag else (None,) * 3
+        Z = ops.scat_layer_j2(x, self.h0o, self.h1o, self.h0a, self.h0b, self.h1a, self.h1b, self.mode, self.magbias, self.combine_colour,
+                              *third)
         return Z if self.combine_colour else Z.view(Z.shape[0], 49 * Z.shape[2], Z.shape[3], Z.shape[4])
 
     def extra_repr(self):
@@ -742,7 +802,7 @@ class DTCWTMagnitudeLoss(_TapModule):
         self.level_weights = None if level_weights is None else tuple(float(w) for w in level_weights)
         self._tap_names = DTCWTForward._tap_names if self.J >= 2 else DTCWTForward._tap_names[:2]
         _refuse_bp(biort, qshift)
-        _register_dtcwt(self, _dtcwt_taps(biort, qshift if self.J >= 2 else None, analysis=True))
+        _register_dtcwt(self, _dtcwt_taps(biort, qshift if self.J >= 2 else None, analysis=True, three=False))
 
     def forward(self, x, y):
         mode = mode_to_int(self.mode)
