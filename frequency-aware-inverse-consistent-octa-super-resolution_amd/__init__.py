@@ -16,7 +16,7 @@ from .data import GpuTransformA, GpuTransformB, crop_resize_normalize, random_cr
 from .train import GraphedTrainStep, ParamArena, TrainStep, live_parameters
 from .utils import (DeviceReplayBuffer, LambdaLR, ReplayBuffer, frequency_split, high_pass, low_pass, psnr, set_requires_grad, weights_init_normal)
 from .wavelets import AFB1D, AFB2D, SFB1D, SFB2D, DWT1DForward, DWT1DInverse, DWTForward, DWTInverse, SWTForward, SWTInverse, daubechies
-from .wavelets import DTCWTForward, DTCWTInverse, ScatLayer, ScatLayerj2, DTCWTMagnitudeLoss
+from .wavelets import DTCWTForward, DTCWTInverse, ScatLayer, ScatLayerj2, DTCWTMagnitudeLoss, CWSSIM
 DTCWT, IDTCWT = DTCWTForward, DTCWTInverse          # the reference's aliases (pytorch_wavelets/__init__.py)
 from .ops import DWT1D_FUSED_MAX
 

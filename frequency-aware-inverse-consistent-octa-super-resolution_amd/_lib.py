@@ -91,6 +91,10 @@ _SIG = {
     "dtcwt_loss_fwd_j1": (_I, "p lll p lll pp pp p ff l iii pi pi i p"),
     "dtcwt_loss_fwd_j2": (_I, "p lll p lll pp pp p ff l iii pppp i p"),
     "dtcwt_loss_final": (_I, "p pp i p p"),
+    "cwssim_workspace_floats": (_L, "l iii"),
+    "cwssim_index": (_I, "pp pp p l iii f p"),
+    "cwssim_grad": (_I, "pp pp pp p l l iii p"),
+    "cwssim_final": (_I, "p l l iii pp p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

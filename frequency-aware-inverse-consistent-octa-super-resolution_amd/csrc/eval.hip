@@ -55,52 +55,59 @@ __global__ __launch_bounds__(256) void eval_minmax_kernel(const float* __restric
     }
 }
 
-// squared error over the image and the 7x7 uniform-window SSIM map over its valid region: sums[n][2] += {sum (y-g)^2, sum S}
+// squared error over the image and the 7x7 uniform-window SSIM map over its valid region: block p of image n takes the 32 x 32
+// tiles p, p + EV_P, ... in that order and stores sums[n][p][2] = {sum (y-g)^2, sum S} of them -- plain stores, no atomics, so
+// that the finish kernel's fixed-order sum makes two calls on the same images agree bit for bit
 __global__ __launch_bounds__(256) void eval_sqerr_ssim_kernel(const float* __restrict__ y, const float* __restrict__ g, double* __restrict__ sums,
                                                               int H, int W, float data_range) {
     constexpr int T = 32, PW = T + 2 * EV_PAD;
     __shared__ float ys[PW * PW], gs[PW * PW];
     __shared__ double red[4];
-    const int n = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
+    const int n = blockIdx.y, p = blockIdx.x;
+    const int tiles_x = (W + T - 1) / T, tiles = tiles_x * ((H + T - 1) / T);
     const float* yp = y + (long)n * H * W;
     const float* gp = g + (long)n * H * W;
-    for (int i = threadIdx.x; i < PW * PW; i += 256) {
-        const int r = i / PW, c = i - r * PW;
-        const int yy = y0 + r - EV_PAD, xx = x0 + c - EV_PAD;
-        const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-        ys[i] = in ? yp[(long)yy * W + xx] : 0.f;
-        gs[i] = in ? gp[(long)yy * W + xx] : 0.f;
-    }
-    __syncthreads();
     // fp64 throughout (the kernel is nowhere near a bottleneck): in fp32 the variances of flat regions are rounding noise that is
     // not small against C2 = (0.03 R)^2 (two constant images: 2e-4 relative on the result)
     const double C1 = (0.01 * (double)data_range) * (0.01 * (double)data_range), C2 = (0.03 * (double)data_range) * (0.03 * (double)data_range);
     const double inv = 1.0 / (double)(EV_WIN * EV_WIN), cov_norm = (double)(EV_WIN * EV_WIN) / (double)(EV_WIN * EV_WIN - 1);
     double se = 0.0, ss = 0.0;
-    for (int i = threadIdx.x; i < T * T; i += 256) {
-        const int r = i / T, c = i - r * T;
-        const int yy = y0 + r, xx = x0 + c;
-        if (yy >= H || xx >= W) continue;
-        const double d = (double)ys[(r + EV_PAD) * PW + c + EV_PAD] - (double)gs[(r + EV_PAD) * PW + c + EV_PAD];
-        se += d * d;
-        if (yy < EV_PAD || yy >= H - EV_PAD || xx < EV_PAD || xx >= W - EV_PAD) continue;      // skimage crops the map by (win-1)/2
-        double sa = 0.0, sb = 0.0, saa = 0.0, sbb = 0.0, sab = 0.0;
+    for (int tile = p; tile < tiles; tile += EV_P) {
+        const int y0 = (tile / tiles_x) * T, x0 = (tile % tiles_x) * T;
+        __syncthreads();                                                      // the previous tile's windows have been read
+        for (int i = threadIdx.x; i < PW * PW; i += 256) {
+            const int r = i / PW, c = i - r * PW;
+            const int yy = y0 + r - EV_PAD, xx = x0 + c - EV_PAD;
+            const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
+            ys[i] = in ? yp[(long)yy * W + xx] : 0.f;
+            gs[i] = in ? gp[(long)yy * W + xx] : 0.f;
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < T * T; i += 256) {
+            const int r = i / T, c = i - r * T;
+            const int yy = y0 + r, xx = x0 + c;
+            if (yy >= H || xx >= W) continue;
+            const double d = (double)ys[(r + EV_PAD) * PW + c + EV_PAD] - (double)gs[(r + EV_PAD) * PW + c + EV_PAD];
+            se += d * d;
+            if (yy < EV_PAD || yy >= H - EV_PAD || xx < EV_PAD || xx >= W - EV_PAD) continue;      // skimage crops the map by (win-1)/2
+            double sa = 0.0, sb = 0.0, saa = 0.0, sbb = 0.0, sab = 0.0;
 #pragma unroll
-        for (int u = 0; u < EV_WIN; ++u)
+            for (int u = 0; u < EV_WIN; ++u)
 #pragma unroll
-            for (int v = 0; v < EV_WIN; ++v) {
-                const double a = (double)ys[(r + u) * PW + c + v], b = (double)gs[(r + u) * PW + c + v];
-                sa += a; sb += b; saa += a * a; sbb += b * b; sab += a * b;
-            }
-        const double ux = sa * inv, uy = sb * inv;
-        const double vx = cov_norm * (saa * inv - ux * ux), vy = cov_norm * (sbb * inv - uy * uy), vxy = cov_norm * (sab * inv - ux * uy);
-        ss += ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
+                for (int v = 0; v < EV_WIN; ++v) {
+                    const double a = (double)ys[(r + u) * PW + c + v], b = (double)gs[(r + u) * PW + c + v];
+                    sa += a; sb += b; saa += a * a; sbb += b * b; sab += a * b;
+                }
+            const double ux = sa * inv, uy = sb * inv;
+            const double vx = cov_norm * (saa * inv - ux * ux), vy = cov_norm * (sbb * inv - uy * uy), vxy = cov_norm * (sab * inv - ux * uy);
+            ss += ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
+        }
     }
     se = block_sum_256d(se, red);
     ss = block_sum_256d(ss, red);
     if (threadIdx.x == 0) {
-        atomicAdd(sums + 2 * n, se);
-        atomicAdd(sums + 2 * n + 1, ss);
+        sums[((long)n * EV_P + p) * 2] = se;
+        sums[((long)n * EV_P + p) * 2 + 1] = ss;
     }
 }
 
@@ -174,11 +181,16 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const unsigned* __rest
     ha = block_sum_256d(ha, red);
     hb = block_sum_256d(hb, red);
     if (threadIdx.x == 0) {
-        const double mse = sums[2 * n] / total;
+        double se = 0.0, ss = 0.0;
+        for (int q = 0; q < EV_P; ++q) {                                  // the blocks' partials, in their order
+            se += sums[((long)n * EV_P + q) * 2];
+            ss += sums[((long)n * EV_P + q) * 2 + 1];
+        }
+        const double mse = se / total;
         const double nvalid = (double)(H - 2 * EV_PAD) * (double)(W - 2 * EV_PAD);
         double* o = out + 4 * n;
         o[0] = mse > 0.0 ? 10.0 * log10((double)data_range * (double)data_range / mse) : INFINITY;
-        o[1] = sums[2 * n + 1] / nvalid;
+        o[1] = ss / nvalid;
         o[2] = mse;
         o[3] = hj > 0.0 ? (ha + hb) / hj : 1.0;                              // two constant images: skimage returns 1
     }
@@ -209,7 +221,7 @@ extern "C" {
 
 long faoctasr_eval_workspace_bytes(int N, int bins) {
     if (N <= 0 || bins <= 0) return 0;
-    return (long)N * EV_P * 4 * sizeof(float) + (long)N * 2 * sizeof(double) + (long)N * bins * bins * sizeof(unsigned) + 64;
+    return (long)N * EV_P * 4 * sizeof(float) + (long)N * EV_P * 2 * sizeof(double) + (long)N * bins * bins * sizeof(unsigned) + 64;
 }
 
 // y, gt: [N][H][W] fp32 device images (single channel); out: [N][4] doubles {psnr, ssim, mse, nmi}; workspace:
@@ -223,12 +235,12 @@ int faoctasr_eval_metrics(const float* y, const float* gt, double* out, void* wo
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
     double* sums = reinterpret_cast<double*>(workspace);
-    float* mm = reinterpret_cast<float*>(sums + 2L * N);
+    float* mm = reinterpret_cast<float*>(sums + 2L * EV_P * N);
     unsigned* hist = reinterpret_cast<unsigned*>(mm + (long)N * EV_P * 4);
-    if (hipMemsetAsync(sums, 0, sizeof(double) * 2 * N, st) != hipSuccess || hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)N * bins * bins, st) != hipSuccess)
+    if (hipMemsetAsync(hist, 0, sizeof(unsigned) * (size_t)N * bins * bins, st) != hipSuccess)
         return fail(FAOCTASR_EHIP, "eval_metrics: memset failed");
     hipLaunchKernelGGL(eval_minmax_kernel, dim3(EV_P, N), dim3(256), 0, st, y, gt, mm, HW);
-    hipLaunchKernelGGL(eval_sqerr_ssim_kernel, dim3((W + 31) / 32, (H + 31) / 32, N), dim3(256), 0, st, y, gt, sums, H, W, data_range);
+    hipLaunchKernelGGL(eval_sqerr_ssim_kernel, dim3(EV_P, N), dim3(256), 0, st, y, gt, sums, H, W, data_range);
     hipLaunchKernelGGL(eval_hist2d_kernel, dim3(EV_P, N), dim3(256), 0, st, y, gt, mm, hist, HW, bins);
     hipLaunchKernelGGL(eval_finish_kernel, dim3(N), dim3(256), 2 * bins * sizeof(double), st, hist, sums, out, H, W, bins, data_range);
     return check_launch("eval_metrics");

@@ -22,10 +22,12 @@ def super_resolve(model, lr_img, r_hp=10, r_lp=8):
 
 
 @torch.no_grad()
-def image_metrics(y, gt, data_range=2.0, bins=100):
+def image_metrics(y, gt, data_range=2.0, bins=100, cw_ssim=None):
     """y, gt: (N,1,H,W) or (N,H,W) device tensors -> float64 tensor (N,4) on the device: PSNR, SSIM, MSE, NMI per image pair
     (skimage.metrics.peak_signal_noise_ratio(data_range=2) / structural_similarity / mean_squared_error /
-    normalized_mutual_information with their defaults, utils.py:209-212)."""
+    normalized_mutual_information with their defaults, utils.py:209-212).  ``cw_ssim``: a ``wavelets.CWSSIM`` module; the result
+    is then (N,5), the fifth column the module's per-image complex-wavelet index, which unlike SSIM hardly moves under a
+    one-pixel misregistration of the pair.  Every sum has a fixed order: two calls on the same images agree bit for bit."""
     y, gt = ops._c(y), ops._c(gt)
     if y.shape != gt.shape:
         raise _lib.KernelError("image_metrics: shapes differ: %s vs %s" % (tuple(y.shape), tuple(gt.shape)))
@@ -39,18 +41,21 @@ def image_metrics(y, gt, data_range=2.0, bins=100):
     nbytes = _lib.load().faoctasr_eval_workspace_bytes(N, bins)
     ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=y.device)
     call("eval_metrics", ptr(y), ptr(gt), out.data_ptr(), ws.data_ptr(), N, H, W, float(data_range), int(bins), stream_ptr())
+    if cw_ssim is not None:
+        out = torch.cat((out, cw_ssim.index(y.reshape(N, 1, H, W), gt.reshape(N, 1, H, W), True).double().reshape(N, 1)), dim=1)
     return out
 
 
-def evaluate_pairs(model, pairs):
+def evaluate_pairs(model, pairs, cw_ssim=None):
     """pairs: iterable of (lr (B,1,H,W), hr (B,1,H,W)) device tensors.  Returns mean PSNR / SSIM / MSE / NMI like the print at
-    utils.py:214,242; one host read at the end."""
+    utils.py:214,242; one host read at the end.  With a ``wavelets.CWSSIM`` module as ``cw_ssim`` also the key "cw_ssim"."""
+    keys = ("psnr", "ssim", "mse", "nmi") + (("cw_ssim",) if cw_ssim is not None else ())
     acc, n = None, 0
     for lr, hr in pairs:
-        m = image_metrics(super_resolve(model, lr), hr).sum(0)
+        m = image_metrics(super_resolve(model, lr), hr, cw_ssim=cw_ssim).sum(0)
         acc = m if acc is None else acc + m
         n += lr.shape[0]
     if acc is None:
-        return {"psnr": 0.0, "ssim": 0.0, "mse": 0.0, "nmi": 0.0}
+        return dict.fromkeys(keys, 0.0)
     vals = (acc / n).tolist()
-    return dict(zip(("psnr", "ssim", "mse", "nmi"), vals))
+    return dict(zip(keys, vals))

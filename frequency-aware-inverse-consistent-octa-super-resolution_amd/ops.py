@@ -1786,6 +1786,180 @@ def dtcwt_mag_loss(x, y, h0o, h1o, qshift=None, J=1, mode=1, magbias=1e-2, level
 
 
 # ----------------------------------------------------------------------------------------
+# complex-wavelet structural similarity (csrc/cwssim.hip): a windowed complex correlation over the bands of a dual-tree level
+# ----------------------------------------------------------------------------------------
+CWSSIM_MAX_WIN = 11
+
+
+def _cwssim_check_scalars(win, K):
+    if int(win) != win or not 1 <= win <= CWSSIM_MAX_WIN:
+        raise ValueError("the window side win must be an integer 1..%d, got %r" % (CWSSIM_MAX_WIN, win))
+    if not (K > 0 and K < float("inf")):
+        raise ValueError("the constant K must be positive and finite (it keeps the index defined where both bands vanish), got %r" % (K,))
+
+
+def _cwssim_check_bands(hx, hy, win):
+    """Every refusal of ``cw_ssim_bands`` that concerns the tensors, the device check last."""
+    for t, what in ((hx, "hx"), (hy, "hy")):
+        if t.dtype != torch.float32:
+            raise ValueError("%s must be float32, got %s" % (what, t.dtype))
+        if t.dim() != 6 or t.shape[2] != 6 or t.shape[5] != 2:
+            raise ValueError("%s must be a band tensor (N, C, 6, h, w, 2), got %s" % (what, tuple(t.shape)))
+    if hx.shape != hy.shape:
+        raise ValueError("hx and hy must have the same shape, got %s and %s" % (tuple(hx.shape), tuple(hy.shape)))
+    if hx.shape[0] < 1 or hx.shape[1] < 1:
+        raise ValueError("the index takes non-empty bands, got %s" % (tuple(hx.shape),))
+    if hx.shape[3] < win or hx.shape[4] < win:
+        raise ValueError("a %d x %d band holds no %d x %d window" % (hx.shape[3], hx.shape[4], win, win))
+    for t, what in ((hx, "hx"), (hy, "hy")):
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    if hx.device != hy.device:
+        raise ValueError("hx and hy must be on one device, got %s and %s" % (hx.device, hy.device))
+
+
+class _CWSSIMBands(Function):
+    """``apply(hx, hy, win, K, per_image, want_x, want_y) -> S``: ``cwssim_index`` and ``cwssim_final`` forward; where an input needs
+    a gradient the index launch also stores the two maps, which with the bands are all that is saved, and the backward is one
+    ``cwssim_grad`` launch that writes the cotangents asked for and reads the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, hx, hy, win, K, per_image, want_x, want_y):
+        N, C, _, h, w, _ = hx.shape
+        dev = hx.device
+        planes = N * C * 6
+        n = _lib.load().faoctasr_cwssim_workspace_floats(planes, h, w, win)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_cwssim_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "cwssim")                 # per stream: consumed by the same call's second launch
+        map_a = map_b = None
+        if want_x or want_y:
+            map_a = torch.empty((planes, h - win + 1, w - win + 1, 2), dtype=torch.float32, device=dev)
+            map_b = torch.empty((planes, h - win + 1, w - win + 1), dtype=torch.float32, device=dev)
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = torch.empty((), dtype=torch.float32, device=dev)
+        call("cwssim_index", ptr(hx), ptr(hy), ptr(map_a), ptr(map_b), ws.data_ptr(), planes, h, w, win, K, stream_ptr())
+        call("cwssim_final", ws.data_ptr(), N, planes, h, w, win, ptr(out_image), ptr(out_mean), stream_ptr())
+        ctx.cfg = (win, per_image, want_x, want_y)
+        if want_x or want_y:
+            ctx.save_for_backward(hx, hy, map_a, map_b)
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        win, per_image, want_x, want_y = ctx.cfg
+        need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_y):
+            return (None,) * 7
+        if (need_x and not want_x) or (need_y and not want_y):
+            raise _lib.KernelError("the index's forward ran without gradients enabled for this input: no maps were saved")
+        hx, hy, map_a, map_b = ctx.saved_tensors
+        N, C, _, h, w, _ = hx.shape
+        gscale = g.contiguous() if per_image else (g / N).expand(N).contiguous()      # on the device: no host read
+        gx = torch.empty_like(hx) if need_x else None
+        gy = torch.empty_like(hy) if need_y else None
+        call("cwssim_grad", ptr(hx), ptr(hy), ptr(map_a), ptr(map_b), ptr(gx), ptr(gy), ptr(gscale), N, N * C * 6, h, w, win, stream_ptr())
+        return (gx, gy) + (None,) * 5
+
+
+def cw_ssim_bands(hx, hy, win=7, K=0.01, per_image=False):
+    """The complex-wavelet structural similarity of two bands ``(N, C, 6, h, w, 2)`` of one dual-tree level: the mean over n, c, the
+    six orientations and the ``(h - win + 1) x (w - win + 1)`` valid positions p of a ``win x win`` box window of
+
+        S_p = (2 |z_p| + K) / (E_p + K),   z_p = sum_W hx conj(hy),   E_p = sum_W |hx|^2 + sum_W |hy|^2,
+
+    as a 0-d fp32 tensor, or per image as ``(N,)`` with ``per_image``; 0 < S <= 1, and a small translation of one image turns every
+    coefficient of a window by nearly the same phase, which |z_p| does not see.  Gradients to both bands.  Two launches of
+    csrc/cwssim.hip forward and one backward; under ``no_grad``, or for inputs that need no gradient, no map is stored.
+    ``S(x, x) == 1`` with zero gradients and ``S(x, y) == S(y, x)`` hold bit for bit; runs are bit-reproducible.  Non-contiguous
+    bands are copied.  No double backward."""
+    _cwssim_check_scalars(win, K)
+    _cwssim_check_bands(hx, hy, int(win))
+    grad = torch.is_grad_enabled()
+    return _CWSSIMBands.apply(hx.contiguous(), hy.contiguous(), int(win), float(K), bool(per_image), grad and hx.requires_grad,
+                              grad and hy.requires_grad)
+
+
+def _cwssim_check(x, y, taps1, taps2, J, mode, win, K, level_weights):
+    """Every refusal of ``cw_ssim``, the device check last; returns the level weights as floats."""
+    if int(J) != J or J < 1:
+        raise ValueError("the index takes J >= 1 levels, got %r" % (J,))
+    if J >= 2 and taps2 is None:
+        raise ValueError("J = %d needs the q-shift filters (levels >= 2), got None" % J)
+    if taps2 is not None and (len(taps1) == 3) != (len(taps2) == 6):
+        raise ValueError("a three-filter level-1 bank (h2o) goes with the q-shift bandpass pair (h2ab) and a two-filter one without")
+    _cwssim_check_scalars(win, K)
+    w = [1.0] * J if level_weights is None else [float(v) for v in level_weights]
+    if len(w) != J:
+        raise ValueError("level_weights lists one weight per level: %d entries for J = %d" % (len(w), J))
+    if not sum(w) > 0:
+        raise ValueError("level_weights must have a positive sum (the index is their weighted mean), got %r" % (w,))
+    if x.dim() != 4 or y.dim() != 4:
+        raise ValueError("the index takes inputs of 4 dimensions (N, C, H, W), got %d and %d" % (x.dim(), y.dim()))
+    if x.shape != y.shape:
+        raise ValueError("x and y must have the same shape, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if min(x.shape) < 1:
+        raise ValueError("the index takes non-empty inputs, got %s" % (tuple(x.shape),))
+    if not 0 <= mode <= 6:
+        raise ValueError("Unkown pad type: {}".format(mode))
+    for t, what in ((x, "x"), (y, "y")):
+        if t.dtype != torch.float32:
+            raise ValueError("%s must be float32, got %s" % (what, t.dtype))
+    for j, (_, _, (bh, bw)) in enumerate(dtcwt_sizes(x.shape[2], x.shape[3], int(J))):
+        if bh < win or bw < win:
+            raise ValueError("level %d of a %d x %d image has bands of %d x %d, which hold no %d x %d window"
+                             % (j + 1, x.shape[2], x.shape[3], bh, bw, win, win))
+    _dtcwt_dev(x, "x")
+    _dtcwt_dev(y, "y")
+    if x.device != y.device:
+        raise ValueError("x and y must be on one device, got %s and %s" % (x.device, y.device))
+    return w
+
+
+def cw_ssim(x, y, h0o, h1o, qshift=None, J=1, mode=1, win=7, K=0.01, level_weights=None, per_image=False, h2o=None, h2ab=None):
+    """The complex-wavelet structural similarity of two images (N, C, H, W): ``S = sum_j w_j S_j / sum_j w_j`` with ``S_j`` the
+    index ``cw_ssim_bands`` of the bands of level j = 1..J of the dual-tree transform of x and y; a 0-d fp32 tensor, or ``(N,)``
+    with ``per_image``, with gradients to both images (the loss is ``1 - S``).  Filters as the modules register them (taps
+    reversed): ``h0o``, ``h1o`` and, for J >= 2, ``qshift`` = (h0a, h0b, h1a, h1b); ``h2o`` and ``h2ab`` = (h2a, h2b) are the bandpass
+    filters of a three-filter bank.  ``mode`` acts on level 1: 1 is the symmetric extension, any other ``wavelets.mode_to_int`` code
+    pads with zeros.  ``level_weights``: one weight per level (default all 1), of positive sum.  Every level's bands must hold a
+    window.
+
+    The levels are the autograd ops of the transform with ``DTCWTForward``'s padding (an odd side repeats its last row / column, a
+    lowpass side that is no multiple of 4 its first and last), so any size the transform takes runs: per level one analysis launch
+    per image, ``cwssim_index`` and ``cwssim_final``; backward one ``cwssim_grad`` and the transform's adjoint."""
+    taps1 = _dtcwt_taps1(h0o, h1o, h2o)
+    taps2 = _dtcwt_taps2(*(tuple(qshift) + (tuple(h2ab) if h2ab is not None else ()))) if qshift is not None else None
+    w = _cwssim_check(x, y, taps1, taps2, J, int(mode), win, K, level_weights)
+    J, win = int(J), int(win)
+    lows = []
+    for t in (x, y):
+        if t.shape[2] % 2:
+            t = torch.cat((t, t[:, :, -1:]), dim=2)
+        if t.shape[3] % 2:
+            t = torch.cat((t, t[:, :, :, -1:]), dim=3)
+        lows.append(t)
+    total = None
+    for j in range(J):
+        bands = []
+        for k in (0, 1):
+            low = lows[k]
+            if j == 0:
+                low, h = _DTCWTFwdJ1.apply(low, taps1, True, False, _DTCWT_NAMES, int(mode))
+            else:
+                if low.shape[2] % 4:
+                    low = torch.cat((low[:, :, 0:1], low, low[:, :, -1:]), dim=2)
+                if low.shape[3] % 4:
+                    low = torch.cat((low[:, :, :, 0:1], low, low[:, :, :, -1:]), dim=3)
+                low, h = _DTCWTFwdJ2.apply(low, taps2, False, False, _DTCWT_NAMES, 1)
+            lows[k] = low
+            bands.append(h)
+        term = w[j] * cw_ssim_bands(bands[0], bands[1], win, K, per_image)
+        total = term if total is None else total + term
+    return total / sum(w)
+
+
+# ----------------------------------------------------------------------------------------
 # DTCWT scattering layers (csrc/scat.hip): a dual-tree level, smoothed magnitudes and the pooled lowpass in one launch
 # ----------------------------------------------------------------------------------------
 def scat_sizes(H, W, order):

@@ -20,7 +20,7 @@ from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
-from .wavelets import DTCWTMagnitudeLoss, DWTForward, SWTForward
+from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
 # parameters that exist in the reference's state_dict but never receive a gradient
 # (model.py:241,254-257: unet/unet_up of NetworkA2B; model.py:281-284: skip of NetworkB2A);
@@ -262,7 +262,8 @@ class TrainStep:
                  beta1=0.25, beta2=10.0, beta3=2.0, beta4=0.5, beta5=0.5, ssim_weight=0.0, whf_weight=0.0, dwt_levels=1,
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
                  reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
-                 dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric"):
+                 dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
+                 cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric"):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -284,7 +285,13 @@ class TrainStep:
         ``cwt_weight`` (default 0: nothing is constructed or launched): adds ``loss_cwt = cwt_weight * (L(recovered_A, real_A) +
         L(recovered_B, real_B))`` to ``loss_G``, L the dual-tree magnitude loss ``DTCWTMagnitudeLoss(cwt_biort, cwt_qshift,
         J=cwt_levels, mode=cwt_mode)``: six orientations, nearly shift-invariant magnitudes.  ``cwt_qshift`` is resolved only for
-        ``cwt_levels`` >= 2 (a name needs a tap provider; a 4-tuple of tap sequences does not)."""
+        ``cwt_levels`` >= 2 (a name needs a tap provider; a 4-tuple of tap sequences does not).
+
+        ``cwssim_weight`` (default 0: nothing is constructed or launched): adds ``loss_cwssim = cwssim_weight * ((1 - S(recovered_A,
+        real_A)) + (1 - S(recovered_B, real_B)))`` to ``loss_G``, S the complex-wavelet structural similarity ``CWSSIM(cwssim_biort,
+        cwssim_qshift, J=cwssim_levels, mode=cwssim_mode, win=cwssim_win)``: a windowed complex correlation of the dual-tree bands,
+        nearly unchanged by a small misregistration and, unlike the magnitude term, sensitive to the phase structure inside a window.
+        ``cwssim_qshift`` is resolved only for ``cwssim_levels`` >= 2."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -314,6 +321,10 @@ class TrainStep:
         self.cwt_weight = cwt_weight
         self.cwt_loss = (DTCWTMagnitudeLoss(biort=cwt_biort, qshift=cwt_qshift, J=cwt_levels, mode=cwt_mode).to(dev)
                          if cwt_weight else None)
+        #: opt-in complex-wavelet SSIM term on the cycle reconstructions (wavelets.CWSSIM; 0 = off, no module is built)
+        self.cwssim_weight = cwssim_weight
+        self.cwssim = (CWSSIM(biort=cwssim_biort, qshift=cwssim_qshift, J=cwssim_levels, mode=cwssim_mode, win=cwssim_win).to(dev)
+                       if cwssim_weight else None)
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -617,6 +628,8 @@ class TrainStep:
             t["loss_phase"] = self.phase_weight * (1 + ops.phase_loss(rec, real, self.phase_radius))
         if self.cwt_weight:
             t["loss_cwt"] = self.cwt_weight * self.cwt_loss(rec, real)
+        if self.cwssim_weight:
+            t["loss_cwssim"] = self.cwssim_weight * (1 - self.cwssim(rec, real))
         return t
 
     def generator_loss(self, o, real_A, real_B):
@@ -657,6 +670,9 @@ class TrainStep:
         if self.cwt_weight:
             L["loss_cwt"] = self.cwt_weight * (self.cwt_loss(o["recovered_A"], real_A) + self.cwt_loss(o["recovered_B"], real_B))
             total = total + L["loss_cwt"]
+        if self.cwssim_weight:
+            L["loss_cwssim"] = self.cwssim_weight * ((1 - self.cwssim(o["recovered_A"], real_A)) + (1 - self.cwssim(o["recovered_B"], real_B)))
+            total = total + L["loss_cwssim"]
         if self.tv_weight:
             L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
             total = total + L["loss_tv"]

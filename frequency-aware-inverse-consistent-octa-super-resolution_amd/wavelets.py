@@ -812,3 +812,58 @@ class DTCWTMagnitudeLoss(_TapModule):
 
     def extra_repr(self):
         return "biort='{}', J={}, mode='{}', magbias={}".format(self.biort, self.J, self.mode, self.magbias)
+
+
+# ----------------------------------------------------------------------------------------
+# complex-wavelet structural similarity -> csrc/cwssim.hip
+# ----------------------------------------------------------------------------------------
+class CWSSIM(_TapModule):
+    """forward(x, y) -> the complex-wavelet structural similarity (CW-SSIM; Wang & Simoncelli 2005, Sampat et al. 2009) of two
+    images (N, C, H, W) over the levels j = 1..J of ``DTCWTForward(biort, qshift, J, mode)``: ``S = sum_j w_j S_j / sum_j w_j``, S_j
+    the mean over n, c, the six orientations and every valid position p of a ``win x win`` box window of
+
+        S_p = (2 |z_p| + K) / (E_p + K),   z_p = sum_W cx conj(cy),   E_p = sum_W |cx|^2 + sum_W |cy|^2.
+
+    0 < S <= 1 and S(x, x) = 1; the module returns the index, as ``ssim`` does, and the loss is ``1 - S``.  A small translation
+    turns every coefficient of a window by nearly the same phase and leaves |z_p| nearly unchanged, and unlike a magnitude
+    comparison the index keeps the relative phase inside a window: it tells a vessel from a blur of the same energy.  A 0-d
+    tensor, or ``(N,)`` with ``per_image``; gradients to both images.
+
+    ``biort`` / ``qshift`` / ``mode`` as ``DTCWTForward`` takes them, registered under the same buffer names and in the same order,
+    three-filter banks (a 3-tuple with a 6-tuple) included; ``qshift`` is resolved only when J >= 2, and the ``*_bp`` names stay
+    refused for want of their tables.  ``level_weights``: one weight per level (default all 1).  ``1 <= win <= 11``; every level's
+    bands must hold a window.  fp32, box window, no double backward (``ops.cw_ssim``)."""
+
+    def __init__(self, biort="near_sym_a", qshift="qshift_a", J=3, mode="symmetric", win=7, K=1e-2, level_weights=None, per_image=False):
+        super().__init__()
+        if int(J) != J or J < 1:
+            raise ValueError("the index takes J >= 1 levels, got %r" % (J,))
+        ops._cwssim_check_scalars(win, K)
+        if level_weights is not None and len(level_weights) != J:
+            raise ValueError("level_weights lists one weight per level: %d entries for J = %d" % (len(level_weights), J))
+        if level_weights is not None and not sum(float(w) for w in level_weights) > 0:
+            raise ValueError("level_weights must have a positive sum (the index is their weighted mean), got %r" % (level_weights,))
+        self.biort, self.qshift, self.J, self.mode, self.win, self.K = biort, qshift, int(J), mode, int(win), float(K)
+        self.level_weights = None if level_weights is None else tuple(float(w) for w in level_weights)
+        self.per_image = bool(per_image)
+        _refuse_bp(biort, qshift)
+        names = DTCWTForward._tap_names if self.J >= 2 else DTCWTForward._tap_names[:2]
+        self._tap_names, taps = _bp_names(names, _dtcwt_taps(biort, qshift if self.J >= 2 else None, analysis=True),
+                                          DTCWTForward._tap_names + ("h2o", "h2a", "h2b"))
+        self.bandpass_diag = "h2o" in self._tap_names
+        _register_dtcwt(self, taps)
+
+    def index(self, x, y, per_image):
+        """The index with ``per_image`` as given instead of the module's."""
+        mode = mode_to_int(self.mode)
+        _prime(self, self._tap_names)
+        bp = self.bandpass_diag
+        q = (self.h0a, self.h0b, self.h1a, self.h1b) if self.J >= 2 else None
+        return ops.cw_ssim(x, y, self.h0o, self.h1o, q, self.J, mode, self.win, self.K, self.level_weights, per_image,
+                           self.h2o if bp else None, (self.h2a, self.h2b) if bp and self.J >= 2 else None)
+
+    def forward(self, x, y):
+        return self.index(x, y, self.per_image)
+
+    def extra_repr(self):
+        return "biort='{}', J={}, mode='{}', win={}, K={}, per_image={}".format(self.biort, self.J, self.mode, self.win, self.K, self.per_image)

@@ -479,6 +479,28 @@ int faoctasr_dtcwt_loss_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, 
 int faoctasr_dtcwt_loss_final(const float* workspace, const long* level_floats, const double* level_scale, int levels, float* out,
                               faoctasr_stream_t stream);
 
+/* ---- complex-wavelet structural similarity (csrc/cwssim.hip) ------------------------------------------
+ * cx, cy: two complex bands of one level, contiguous (planes, h, w, 2), planes = N * C * 6; a win x win box window (1 <= win <= 11,
+ * h, w >= win) at each of the (h - win + 1) x (w - win + 1) valid positions p:
+ *   z_p = sum_W cx conj(cy),  E_p = sum_W |cx|^2 + sum_W |cy|^2,  S_p = (2 |z_p| + K) / (E_p + K),  K > 0.
+ * index: part[0, blocks) gets one partial sum of S_p per block, blocks = faoctasr_cwssim_workspace_floats(planes, h, w, win) (-1 on
+ *   a bad shape), plane-major.  map_a (planes, h - win + 1, w - win + 1, 2) and map_b (planes, h - win + 1, w - win + 1), both or
+ *   neither NULL: a_p z_p / |z_p| (0 where z_p = 0) and b_p, a_p = 2 / (E_p + K), b_p = 2 S_p / (E_p + K).
+ * final: out_image[n] = the mean of S_p over image n (planes / N planes each), out_mean[0] = the mean of those; added in double in
+ *   a fixed order.  planes, h, w, win as given to index.
+ * grad: with A_q, B_q the sums of map_a, map_b over the windows that contain q,
+ *   gx_q = (cy_q A_q - cx_q B_q) gscale[n] / count,  gy_q = (cx_q conj(A_q) - cy_q B_q) gscale[n] / count,
+ *   count = (planes / N) (h - win + 1) (w - win + 1), gscale a DEVICE array of N floats (the upstream gradient per image); gx or gy
+ *   may be NULL (not computed), not both.
+ * For cx == cy S_p is exactly 1 and both gradients exactly 0; swapping cx and cy leaves every S_p bit for bit and swaps gx, gy. */
+long faoctasr_cwssim_workspace_floats(long planes, int h, int w, int win);
+int faoctasr_cwssim_index(const float* cx, const float* cy, float* map_a, float* map_b, float* part, long planes, int h, int w, int win,
+                          float K, faoctasr_stream_t stream);
+int faoctasr_cwssim_grad(const float* cx, const float* cy, const float* map_a, const float* map_b, float* gx, float* gy,
+                         const float* gscale, long N, long planes, int h, int w, int win, faoctasr_stream_t stream);
+int faoctasr_cwssim_final(const float* part, long N, long planes, int h, int w, int win, float* out_image, float* out_mean,
+                          faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
@@ -529,7 +551,8 @@ int faoctasr_param_broadcast(float* buf, long count, int root, void* comm, faoct
  * The four skimage metrics of utils.py:209-212 on device images: y, gt [N][H][W] fp32; out [N][4] doubles = {PSNR
  * (peak_signal_noise_ratio, data_range), SSIM (structural_similarity defaults: 7x7 uniform window, sample covariance, map cropped
  * by 3), MSE, NMI (normalized_mutual_information: joint bins x bins histogram over each image's [min, max], numpy.histogram2d
- * bin semantics)}.  data_range = 2, bins = 100 reproduce the reference.  workspace: faoctasr_eval_workspace_bytes(N, bins) bytes. */
+ * bin semantics)}.  data_range = 2, bins = 100 reproduce the reference.  workspace: faoctasr_eval_workspace_bytes(N, bins) bytes.
+ * Every sum has a fixed order (no floating-point atomics): two calls on the same images give the same bits. */
 long faoctasr_eval_workspace_bytes(int N, int bins);
 int faoctasr_eval_metrics(const float* y, const float* gt, double* out, void* workspace, int N, int H, int W, float data_range, int bins,
                           faoctasr_stream_t stream);
