@@ -10,7 +10,7 @@ from .model import (Discriminator, FS_DiscriminatorA, FS_DiscriminatorB, Network
                     ResnetGenerator, TVLoss, UnetGenerator, UnetSkipConnectionBlock, phase_consistency_loss, shallowNet)
 from .evaluate import evaluate_pairs, image_metrics, super_resolve
 from . import ssim                # stays the MODULE: the reference does `import ssim; ssim.SSIM()` (train.py:24,97)
-from .ssim import SSIM
+from .ssim import SSIM, MSSSIM, ms_ssim
 from .ssim import ssim as ssim_fn  # the function ssim.py:65-73; not exported under the submodule's name
 from .data import GpuTransformA, GpuTransformB, crop_resize_normalize, random_crop_offsets
 from .train import GraphedTrainStep, ParamArena, TrainStep, live_parameters

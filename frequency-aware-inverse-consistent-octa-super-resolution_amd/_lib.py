@@ -95,6 +95,10 @@ _SIG = {
     "cwssim_index": (_I, "pp pp p l iii f p"),
     "cwssim_grad": (_I, "pp pp pp p l l iii p"),
     "cwssim_final": (_I, "p l l iii pp p"),
+    "msssim_workspace_floats": (_L, "l iii"),
+    "msssim_scale_fwd": (_I, "pp pp p l iii i ff p"),
+    "msssim_final": (_I, "p ll iii p i ppp p"),
+    "msssim_scale_bwd": (_I, "pp p p i pp pp ll iii i ff p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

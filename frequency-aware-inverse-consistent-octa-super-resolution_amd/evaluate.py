@@ -46,13 +46,19 @@ def image_metrics(y, gt, data_range=2.0, bins=100, cw_ssim=None):
     return out
 
 
-def evaluate_pairs(model, pairs, cw_ssim=None):
+def evaluate_pairs(model, pairs, cw_ssim=None, ms_ssim=None):
     """pairs: iterable of (lr (B,1,H,W), hr (B,1,H,W)) device tensors.  Returns mean PSNR / SSIM / MSE / NMI like the print at
-    utils.py:214,242; one host read at the end.  With a ``wavelets.CWSSIM`` module as ``cw_ssim`` also the key "cw_ssim"."""
-    keys = ("psnr", "ssim", "mse", "nmi") + (("cw_ssim",) if cw_ssim is not None else ())
+    utils.py:214,242; one host read at the end.  With a ``wavelets.CWSSIM`` module as ``cw_ssim`` also the key "cw_ssim"; with an
+    ``ssim.MSSSIM`` module as ``ms_ssim`` also the key "ms_ssim", the mean of the module's per-image multi-scale index of
+    ``(super_resolve(lr), hr)``."""
+    keys = ("psnr", "ssim", "mse", "nmi") + (("cw_ssim",) if cw_ssim is not None else ()) + (("ms_ssim",) if ms_ssim is not None else ())
     acc, n = None, 0
     for lr, hr in pairs:
-        m = image_metrics(super_resolve(model, lr), hr, cw_ssim=cw_ssim).sum(0)
+        sr = super_resolve(model, lr)
+        m = image_metrics(sr, hr, cw_ssim=cw_ssim).sum(0)
+        if ms_ssim is not None:
+            with torch.no_grad():
+                m = torch.cat((m, ms_ssim.index(sr, hr, True).double().sum(0, keepdim=True)))
         acc = m if acc is None else acc + m
         n += lr.shape[0]
     if acc is None:

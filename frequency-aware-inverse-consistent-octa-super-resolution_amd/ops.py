@@ -2450,3 +2450,124 @@ class _SSIM(Function):
 
 def ssim(a, b, size_average=True):
     return _SSIM.apply(a, b, bool(size_average))
+
+
+# ----------------------------------------------------------------------------------------
+# multi-scale SSIM (csrc/msssim.hip): the contrast-structure factor at every dyadic scale, the luminance factor at the coarsest
+# ----------------------------------------------------------------------------------------
+MSSSIM_MAX_LEVELS = 5
+#: Wang, Simoncelli & Bovik 2003; the first M are used as they stand
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def _msssim_check_scalars(levels, weights, data_range):
+    """The refusals of ``ms_ssim`` that concern no tensor; returns the weights as floats."""
+    if isinstance(levels, bool) or int(levels) != levels or not 1 <= levels <= MSSSIM_MAX_LEVELS:
+        raise ValueError("levels must be an integer 1..%d, got %r" % (MSSSIM_MAX_LEVELS, levels))
+    levels = int(levels)
+    w = MSSSIM_WEIGHTS[:levels] if weights is None else tuple(float(v) for v in weights)
+    if len(w) != levels:
+        raise ValueError("weights lists one weight per scale: %d entries for levels = %d" % (len(w), levels))
+    if not all(v > 0 and v < float("inf") for v in w):
+        raise ValueError("every weight must be positive and finite, got %r" % (w,))
+    if not (data_range > 0 and data_range < float("inf")):
+        raise ValueError("data_range must be positive and finite, got %r" % (data_range,))
+    return w
+
+
+def _msssim_check(a, b, levels, weights, data_range):
+    """Every refusal of ``ms_ssim``, the device check last; returns the weights as floats."""
+    w = _msssim_check_scalars(levels, weights, data_range)
+    levels = len(w)
+    for t, what in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError("%s must be a float32 tensor, got %s" % (what, getattr(t, "dtype", type(t))))
+        if t.dim() != 4:
+            raise ValueError("%s must be (N, C, H, W), got %s" % (what, tuple(t.shape)))
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("the index takes non-empty images, got %s" % (tuple(a.shape),))
+    if min(a.shape[2], a.shape[3]) < 2 ** (levels - 1):
+        raise ValueError("a %d x %d image leaves scale %d empty: every side must be at least %d"
+                         % (a.shape[2], a.shape[3], levels, 2 ** (levels - 1)))
+    for t, what in ((a, "a"), (b, "b")):
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    if a.device != b.device:
+        raise ValueError("a and b must be on one device, got %s and %s" % (a.device, b.device))
+    return w
+
+
+class _MSSSIM(Function):
+    """``apply(a, b, weights, C1, C2, per_image, want_a, want_b) -> MS``: one ``msssim_scale_fwd`` per scale and ``msssim_final``
+    forward; where an input needs a gradient the pooled pairs of scales 2..M and the coefficient table are saved, and the backward is
+    one ``msssim_scale_bwd`` per scale, coarsest first, reading the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, a, b, weights, C1, C2, per_image, want_a, want_b):
+        N, C, H, W = a.shape
+        M, dev = len(weights), a.device
+        n = _lib.load().faoctasr_msssim_workspace_floats(N * C, H, W, M)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_msssim_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "msssim")                 # per stream: consumed by the same call's last launch
+        pairs = [(a, b)]
+        for j in range(M):
+            pa = pb = None
+            if j < M - 1:
+                pa = torch.empty((N, C, H >> (j + 1), W >> (j + 1)), dtype=torch.float32, device=dev)
+                pb = torch.empty_like(pa)
+                pairs.append((pa, pb))
+            call("msssim_scale_fwd", ptr(pairs[j][0]), ptr(pairs[j][1]), ptr(pa), ptr(pb), ws.data_ptr(), N * C, H, W, M, j, C1, C2, stream_ptr())
+        want = want_a or want_b
+        coef = torch.empty((M, N), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = torch.empty((), dtype=torch.float32, device=dev)
+        call("msssim_final", ws.data_ptr(), N, C, H, W, M, ctypes.cast((ctypes.c_double * M)(*weights), ctypes.c_void_p), int(not per_image),
+             ptr(out_image), ptr(out_mean), ptr(coef), stream_ptr())
+        ctx.cfg = (M, C1, C2, want_a, want_b)
+        if want:
+            ctx.save_for_backward(coef, *(t for p in pairs for t in p))
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        M, C1, C2, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 8
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("ms_ssim's forward ran without gradients enabled for this input: nothing was saved")
+        coef, *flat = ctx.saved_tensors
+        N, C, H, W = flat[0].shape
+        g = _c(g).reshape(-1)
+        da = db = None
+        for j in range(M - 1, -1, -1):
+            aj, bj = flat[2 * j], flat[2 * j + 1]
+            dca, dcb = da, db
+            da = torch.empty_like(aj) if need_a else None
+            db = torch.empty_like(bj) if need_b else None
+            call("msssim_scale_bwd", ptr(aj), ptr(bj), ptr(coef), ptr(g), g.numel(), ptr(dca), ptr(dcb), ptr(da), ptr(db), N, C, H, W, M, j,
+                 C1, C2, stream_ptr())
+        return (da, db) + (None,) * 6
+
+
+def ms_ssim(a, b, levels=5, weights=None, data_range=1.0, per_image=False):
+    """Multi-scale SSIM (Wang, Simoncelli & Bovik 2003) of two images ``(N, C, H, W)``: scale 1 is the input and scale j + 1 is
+    ``avg_pool2d(scale j, 2)``; with the moments of ``ssim`` (11-tap sigma-1.5 Gaussian, zero padding 5) at every scale
+
+        cs_p = (2 s12 + C2) / (s11 + s22 + C2),   l_p = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1),   C1 = (0.01 L)^2, C2 = (0.03 L)^2,
+
+    ``F_j[n]`` the mean of cs_p over image n at scale j < M and of l_p cs_p at scale M = ``levels``, the score is
+    ``MS[n] = prod_j max(F_j[n], 0)^w_j``: the mean over n as a 0-d fp32 tensor, or ``(N,)`` with ``per_image``.  ``weights``
+    defaults to the first M of (0.0448, 0.2856, 0.3001, 0.2363, 0.1333), not renormalised; ``levels=1, weights=(1,)`` is ``ssim``.
+    Where a factor is <= 0 the image's score is 0 and its gradient exactly zero.  Gradients to both images; M + 1 launches of
+    csrc/msssim.hip forward and M backward; under ``no_grad``, or for inputs that need no gradient, nothing is saved.
+    ``MS(x, x) == 1`` with zero gradients and ``MS(x, y) == MS(y, x)`` hold bit for bit; runs are bit-reproducible.  Every side
+    must be at least ``2^(M - 1)``.  fp32, no double backward."""
+    w = _msssim_check(a, b, levels, weights, data_range)
+    L = float(data_range)
+    grad = torch.is_grad_enabled()
+    return _MSSSIM.apply(a.contiguous(), b.contiguous(), w, (0.01 * L) ** 2, (0.03 * L) ** 2, bool(per_image), grad and a.requires_grad,
+                         grad and b.requires_grad)

@@ -1,4 +1,5 @@
-"""SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel."""
+"""SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
+same window behind the same interface (csrc/msssim.hip)."""
 from math import exp
 
 import torch
@@ -41,3 +42,36 @@ class SSIM(torch.nn.Module):
 
     def forward(self, img1, img2):
         return ops.ssim(img1, img2, self.size_average)
+
+
+def ms_ssim(img1, img2, window_size=11, size_average=True, levels=5, weights=None, data_range=1.0):
+    """Multi-scale SSIM with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with ``size_average=False`` (``ops.ms_ssim``)."""
+    _check(window_size)
+    return ops.ms_ssim(img1, img2, levels, weights, data_range, not size_average)
+
+
+class MSSSIM(torch.nn.Module):
+    """forward(img1, img2) -> multi-scale SSIM (Wang, Simoncelli & Bovik 2003) with ``SSIM``'s interface: the contrast-structure
+    factor of ssim.py:17-32 at ``levels`` dyadic scales (scale j + 1 = ``avg_pool2d(scale j, 2)``) and the luminance factor at the
+    coarsest, ``MS[n] = prod_j max(F_j[n], 0)^w_j``.  ``weights`` defaults to the first ``levels`` of (0.0448, 0.2856, 0.3001, 0.2363,
+    0.1333), not renormalised; ``data_range`` L sets C1 = (0.01 L)^2, C2 = (0.03 L)^2.  ``levels=1, weights=(1,)`` is ``SSIM``.  The
+    mean over the batch, or ``(N,)`` with ``size_average=False``; the loss is ``1 - MS``.  Every side must be at least
+    ``2^(levels - 1)``; fp32, 11-tap window only, no double backward."""
+
+    def __init__(self, window_size=11, size_average=True, levels=5, weights=None, data_range=1.0):
+        super().__init__()
+        _check(window_size)
+        ops._msssim_check_scalars(levels, weights, data_range)
+        self.window_size, self.size_average = window_size, size_average
+        self.levels, self.data_range = int(levels), float(data_range)
+        self.weights = None if weights is None else tuple(float(w) for w in weights)
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.ms_ssim(img1, img2, self.levels, self.weights, self.data_range, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "levels={}, weights={}, data_range={}, size_average={}".format(self.levels, self.weights, self.data_range, self.size_average)

@@ -19,6 +19,7 @@ import torch.distributed as dist
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
+from .ssim import MSSSIM
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
@@ -263,7 +264,8 @@ class TrainStep:
                  process_group=None, distributed=None, init=True, precision="f32", overlap_wgrad=True,
                  reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
-                 cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric"):
+                 cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
+                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -291,7 +293,12 @@ class TrainStep:
         real_A)) + (1 - S(recovered_B, real_B)))`` to ``loss_G``, S the complex-wavelet structural similarity ``CWSSIM(cwssim_biort,
         cwssim_qshift, J=cwssim_levels, mode=cwssim_mode, win=cwssim_win)``: a windowed complex correlation of the dual-tree bands,
         nearly unchanged by a small misregistration and, unlike the magnitude term, sensitive to the phase structure inside a window.
-        ``cwssim_qshift`` is resolved only for ``cwssim_levels`` >= 2."""
+        ``cwssim_qshift`` is resolved only for ``cwssim_levels`` >= 2.
+
+        ``msssim_weight`` (default 0: nothing is constructed or launched): adds ``loss_msssim = msssim_weight * ((1 - MS(recovered_A,
+        real_A)) + (1 - MS(recovered_B, real_B)))`` to ``loss_G``, MS the multi-scale SSIM ``MSSSIM(levels=msssim_levels,
+        weights=msssim_weights)``: the contrast-structure factor at every dyadic scale and the luminance factor at the coarsest, so
+        that a reconstruction with the capillaries right and the large-vessel contrast wrong no longer scores well."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -325,6 +332,9 @@ class TrainStep:
         self.cwssim_weight = cwssim_weight
         self.cwssim = (CWSSIM(biort=cwssim_biort, qshift=cwssim_qshift, J=cwssim_levels, mode=cwssim_mode, win=cwssim_win).to(dev)
                        if cwssim_weight else None)
+        #: opt-in multi-scale SSIM term on the cycle reconstructions (ssim.MSSSIM; 0 = off, no module is built)
+        self.msssim_weight = msssim_weight
+        self.msssim = MSSSIM(levels=msssim_levels, weights=msssim_weights).to(dev) if msssim_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -630,6 +640,8 @@ class TrainStep:
             t["loss_cwt"] = self.cwt_weight * self.cwt_loss(rec, real)
         if self.cwssim_weight:
             t["loss_cwssim"] = self.cwssim_weight * (1 - self.cwssim(rec, real))
+        if self.msssim_weight:
+            t["loss_msssim"] = self.msssim_weight * (1 - self.msssim(rec, real))
         return t
 
     def generator_loss(self, o, real_A, real_B):
@@ -673,6 +685,9 @@ class TrainStep:
         if self.cwssim_weight:
             L["loss_cwssim"] = self.cwssim_weight * ((1 - self.cwssim(o["recovered_A"], real_A)) + (1 - self.cwssim(o["recovered_B"], real_B)))
             total = total + L["loss_cwssim"]
+        if self.msssim_weight:
+            L["loss_msssim"] = self.msssim_weight * ((1 - self.msssim(o["recovered_A"], real_A)) + (1 - self.msssim(o["recovered_B"], real_B)))
+            total = total + L["loss_msssim"]
         if self.tv_weight:
             L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
             total = total + L["loss_tv"]

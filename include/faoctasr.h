@@ -501,6 +501,29 @@ int faoctasr_cwssim_grad(const float* cx, const float* cy, const float* map_a, c
 int faoctasr_cwssim_final(const float* part, long N, long planes, int h, int w, int win, float* out_image, float* out_mean,
                           faoctasr_stream_t stream);
 
+/* ---- multi-scale SSIM (csrc/msssim.hip) -----------------------------------------------------------------
+ * a, b: scale `scale` (0-based) of a pair whose scale 0 is (planes, H, W), planes = N * C: contiguous (planes, H >> scale, W >> scale);
+ * scale j + 1 is the 2 x 2 mean of scale j (floor).  1 <= levels <= 5 scales, none empty.  Moments as faoctasr_ssim_fwd (11-tap
+ * sigma-1.5 Gaussian, zero padding 5):  cs_p = (2 s12 + C2) / (s11 + s22 + C2),  l_p = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1).
+ * scale_fwd: one partial sum per block of cs_p (of l_p cs_p at scale levels - 1) into this scale's part of the workspace of
+ *   faoctasr_msssim_workspace_floats(planes, H, W, levels) floats (-1 on a bad shape); no atomics.  pa, pb (planes, H >> (scale + 1),
+ *   W >> (scale + 1)) get the next scale of both images; both NULL at the last scale and only there.
+ * final: F_j[n] = the mean of scale j's map over image n, MS[n] = prod_j max(F_j[n], 0)^weights[j] (weights: HOST array of `levels`
+ *   positive doubles), out_image[n] = MS[n], out_mean[0] = their mean; added in double in a fixed order.  coef (levels, N), may be
+ *   NULL: w_j MS[n] / F_j[n] / (C h_j w_j), 0 for an image with a factor <= 0, times 1 / N when average != 0.
+ * scale_bwd: da, db (either may be NULL, not both) = coef[scale][n] g[n or 0] d(sum of scale's map)/d(a|b) + the adjoint of the
+ *   pooling applied to dca, dcb, the gradients of scale + 1 (NULL at the last scale; required for a side that is written elsewhere).
+ *   g is a DEVICE array of gN floats (1 = shared, or N).  Run from scale levels - 1 down to 0; scale 0 writes the input gradients.
+ * For a == b MS is exactly 1 and both gradients exactly 0; swapping a and b leaves MS bit for bit and swaps the gradients. */
+long faoctasr_msssim_workspace_floats(long planes, int H, int W, int levels);
+int faoctasr_msssim_scale_fwd(const float* a, const float* b, float* pa, float* pb, float* workspace, long planes, int H, int W, int levels,
+                              int scale, float C1, float C2, faoctasr_stream_t stream);
+int faoctasr_msssim_final(const float* workspace, long N, long C, int H, int W, int levels, const double* weights, int average,
+                          float* out_image, float* out_mean, float* coef, faoctasr_stream_t stream);
+int faoctasr_msssim_scale_bwd(const float* a, const float* b, const float* coef, const float* g, int gN, const float* dca, const float* dcb,
+                              float* da, float* db, long N, long C, int H, int W, int levels, int scale, float C1, float C2,
+                              faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
