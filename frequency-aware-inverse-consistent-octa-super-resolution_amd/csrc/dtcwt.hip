@@ -34,6 +34,9 @@
 // stores.  The input is read once (plus the halo), every output written once, nothing intermediate leaves the CU; the taps
 // travel by value in the kernel arguments (no device allocation, no state, capturable).  Every output is a fixed-order sum
 // (t = 0 .. L-1 per pass, no atomics), whatever the tile it falls in: bit-reproducible.
+// The staging and the two filter passes are the four tile bodies of dtcwt_dev.h (dt_fwd1_*, dt_fwd2_*, dt_inv1, dt_inv2), which the
+// scattering layers (scat.hip) and the magnitude loss (dtcwt_loss.hip) run as well; a kernel here decodes its block, declares the
+// LDS arrays, calls the body and, in the forwards, applies q2c and stores.
 //
 // The bandpass tensor is addressed through element strides of its (n, c, orientation, row, column, re/im) axes, so any
 // o_dim / ri_dim layout and any view runs without a copy; where re/im are adjacent and 8-byte aligned the pair moves as one
@@ -43,7 +46,7 @@
 namespace faoctasr {
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// level 1 forward
+// level 1 forward: x [H, W] even -> ll [H, W] (optional), six complex bands [H/2, W/2] (HIGHS)
 // ---------------------------------------------------------------------------------------------------------------------------
 template <bool HIGHS, bool BP>
 __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x, DtLow xs, float* __restrict__ ll, float* __restrict__ hi,
@@ -54,92 +57,25 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j1(const float* __restrict__ x,
     __shared__ __attribute__((aligned(16))) float mid_lo[J1_PR][J1_TW];
     __shared__ __attribute__((aligned(16))) float mid_hi[HIGHS ? J1_PR : 1][J1_TW];
     __shared__ __attribute__((aligned(16))) float mid_ba[BP ? J1_PR : 1][J1_TW];
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w; b /= tiles_w;
-    const int th = b % tiles_h;
-    const long plane = b / tiles_h;
-    const long n = plane / C, c = plane % C;
-    const int oi0 = th * J1_TH, oj0 = tw * J1_TW;
-    const int hm = dt_halo1<BP>(L0, L1, taps), a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
-    const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;               // <= J1_PR, J1_PC
-    const float* xp = x + n * xs.n + c * xs.c;
+    const DtTile b = dt_tile(tiles_h, tiles_w);
+    const long n = b.plane / C, c = b.plane % C;
+    const int oi0 = b.th * J1_TH, oj0 = b.tw * J1_TW;
+    dt_fwd1_rows<HIGHS, BP>(x + n * xs.n + c * xs.c, xs.r, oi0, oj0, H, W, sym, L0, L1, taps, patch, mid_lo, mid_hi, mid_ba);
 
-    for (int r = tid >> 6; r < rows; r += 4) {
-        const int sr = dt_map(oi0 - hm + r, H, sym);
-        for (int cc = tid & 63; cc < cols; cc += 64) {
-            const int sc = dt_map(oj0 - hm + cc, W, sym);
-            patch[r][cc] = (sr >= 0 && sc >= 0) ? xp[sr * xs.r + sc] : 0.f;
-        }
-    }
-    __syncthreads();
-
-    {   // W pass: thread (r, cc) filters patch row r at tile column cc
-        const int cc = tid & 63;
-        for (int r = tid >> 6; r < rows; r += 4) {
-            float lo = 0.f;
-            for (int t = 0; t < L0; ++t) lo = fmaf(taps.f0[t], patch[r][cc + t + a0], lo);
-            mid_lo[r][cc] = lo;
-            if (HIGHS) {
-                float hv = 0.f;
-                for (int t = 0; t < L1; ++t) hv = fmaf(taps.f1[t], patch[r][cc + t + a1], hv);
-                mid_hi[r][cc] = hv;
-            }
-            if constexpr (BP) {
-                const int a2 = hm - (taps.L2 >> 1);
-                float bv = 0.f;
-                for (int t = 0; t < taps.L2; ++t) bv = fmaf(taps.f2[t], patch[r][cc + t + a2], bv);
-                mid_ba[r][cc] = bv;
-            }
-        }
-    }
-    __syncthreads();
-
-    // H pass: a thread owns one 2x2 quad of the tile (8 x 32 quads), reads the column pair as float2
-    const int qi = tid >> 5, qj = tid & 31;
+    const int qi = threadIdx.x >> 5, qj = threadIdx.x & 31;
     const int oi = oi0 + 2 * qi, oj = oj0 + 2 * qj;
     if (oi >= H || oj >= W) return;                                       // H, W even: a quad is inside or outside as a whole
-    float2 vll[2], vlh[2], vhl[2], vhh[2];
-    for (int d = 0; d < 2; ++d) {
-        float2 s = make_float2(0.f, 0.f);
-        for (int t = 0; t < L0; ++t) {
-            const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a0][2 * qj]);
-            s.x = fmaf(taps.f0[t], v.x, s.x); s.y = fmaf(taps.f0[t], v.y, s.y);
-        }
-        vll[d] = s;
-        if (HIGHS) {
-            float2 u = make_float2(0.f, 0.f), p = u, q = u;
-            for (int t = 0; t < L1; ++t) {
-                const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a1][2 * qj]);
-                float2 w;
-                if constexpr (!BP) w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a1][2 * qj]);
-                u.x = fmaf(taps.f1[t], v.x, u.x); u.y = fmaf(taps.f1[t], v.y, u.y);
-                if constexpr (!BP) { q.x = fmaf(taps.f1[t], w.x, q.x); q.y = fmaf(taps.f1[t], w.y, q.y); }
-            }
-            for (int t = 0; t < L0; ++t) {
-                const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a0][2 * qj]);
-                p.x = fmaf(taps.f0[t], w.x, p.x); p.y = fmaf(taps.f0[t], w.y, p.y);
-            }
-            if constexpr (BP) {                                           // hh = col(ba, h2)
-                const int a2 = hm - (taps.L2 >> 1);
-                for (int t = 0; t < taps.L2; ++t) {
-                    const float2 w = *reinterpret_cast<const float2*>(&mid_ba[2 * qi + d + t + a2][2 * qj]);
-                    q.x = fmaf(taps.f2[t], w.x, q.x); q.y = fmaf(taps.f2[t], w.y, q.y);
-                }
-            }
-            vlh[d] = u; vhl[d] = p; vhh[d] = q;
-        }
-    }
+    const DtQuad1 v = dt_fwd1_quad<HIGHS, BP>(qi, qj, L0, L1, taps, mid_lo, mid_hi, mid_ba);
     if (ll) {
-        float* lp = ll + plane * H * (long)W + (long)oi * W + oj;
-        *reinterpret_cast<float2*>(lp) = vll[0];
-        *reinterpret_cast<float2*>(lp + W) = vll[1];
+        float* lp = ll + b.plane * H * (long)W + (long)oi * W + oj;
+        *reinterpret_cast<float2*>(lp) = v.ll[0];
+        *reinterpret_cast<float2*>(lp + W) = v.ll[1];
     }
     if (HIGHS) {
         float* q = hi + n * hs.n + c * hs.c + (long)(oi >> 1) * hs.r + (long)(oj >> 1) * hs.w;
-        dt_q2c(q, hs, vec, 0, 5, vlh[0], vlh[1]);
-        dt_q2c(q, hs, vec, 1, 4, vhh[0], vhh[1]);
-        dt_q2c(q, hs, vec, 2, 3, vhl[0], vhl[1]);
+        dt_q2c(q, hs, vec, 0, 5, v.lh[0], v.lh[1]);
+        dt_q2c(q, hs, vec, 1, 4, v.hh[0], v.hh[1]);
+        dt_q2c(q, hs, vec, 2, 3, v.hl[0], v.hl[1]);
     }
 }
 
@@ -155,76 +91,29 @@ __global__ __launch_bounds__(256) void dtcwt_fwd_j2(const float* __restrict__ x,
     __shared__ __attribute__((aligned(16))) float mid_lo[F2_PR][F2_TW];
     __shared__ __attribute__((aligned(16))) float mid_hi[HIGHS ? F2_PR : 1][F2_TW];
     __shared__ __attribute__((aligned(16))) float mid_ba[BP ? F2_PR : 1][F2_TW];
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w; b /= tiles_w;
-    const int th = b % tiles_h;
-    const long plane = b / tiles_h;
-    const long n = plane / C, c = plane % C;
+    const DtTile b = dt_tile(tiles_h, tiles_w);
+    const long n = b.plane / C, c = b.plane % C;
     const int OH = H >> 1, OW = W >> 1;
-    const int i0 = th * (F2_TH / 2), j0 = tw * (F2_TW / 2);               // first quad row / column = first index of the trees
-    const int rows = 2 * F2_TH + 2 * m - 4, cols = 2 * F2_TW + 2 * m - 4;  // <= F2_PR, F2_PC; patch (r, cc) is x position 4 i0 + 2 - m + r
-    const float* xp = x + n * xs.n + c * xs.c;
+    const int i0 = b.th * (F2_TH / 2), j0 = b.tw * (F2_TW / 2);           // first quad row / column = first index of the trees
+    dt_fwd2_rows<HIGHS, BP>(x + n * xs.n + c * xs.c, xs.r, i0, j0, H, W, m, taps, patch, mid_lo, mid_hi, mid_ba);
 
-    for (int r = tid >> 6; r < rows; r += 4) {
-        const int sr = dt_map(4 * i0 + 2 - m + r, H, 1);
-        for (int cc = tid & 63; cc < cols; cc += 64)
-            patch[r][cc] = xp[sr * xs.r + dt_map(4 * j0 + 2 - m + cc, W, 1)];
-    }
-    __syncthreads();
-
-    {   // W pass: tile column cc = 2 i + p; the float2 at patch column 4 i + 2 t holds the samples at offsets 2 - m and 3 - m
-        const int cc = tid & 63, i = cc >> 1, p = cc & 1;
-        for (int r = tid >> 6; r < rows; r += 4) {
-            float lo = 0.f, hv = 0.f, bv = 0.f;
-            for (int t = 0; t < m; ++t) {
-                const float2 v = *reinterpret_cast<const float2*>(&patch[r][4 * i + 2 * t]);
-                lo = fmaf(p ? taps.lo1[t] : taps.lo0[t], p ? v.y : v.x, lo);
-                if (HIGHS) hv = fmaf(p ? taps.hi1[t] : taps.hi0[t], p ? v.x : v.y, hv);
-                if constexpr (BP) bv = fmaf(p ? taps.ba1[t] : taps.ba0[t], p ? v.x : v.y, bv);
-            }
-            mid_lo[r][cc] = lo;
-            if (HIGHS) mid_hi[r][cc] = hv;
-            if constexpr (BP) mid_ba[r][cc] = bv;
-        }
-    }
-    __syncthreads();
-
-    // H pass: 4 x 32 quads; threads 0..127 take the W-lowpass plane (ll, lh), threads 128..255 the W-highpass plane (hl, hh);
-    // BP: the latter take hl from the W-highpass plane and hh from the W-bandpass one, with the bandpass taps
-    const int path = tid >> 7, qi = (tid & 127) >> 5, qj = tid & 31;
+    const int tid = threadIdx.x, path = tid >> 7, qi = (tid & 127) >> 5, qj = tid & 31;
     if (!HIGHS && path) return;
     const int oi = 2 * (i0 + qi), oj = 2 * (j0 + qj);                      // top-left of the quad in ll
     if (oi >= OH || oj >= OW) return;
-    float2 l0 = make_float2(0.f, 0.f), l1 = l0, h0 = l0, h1 = l0;         // lowpass call rows 2qi, 2qi+1; highpass call likewise
-    for (int t = 0; t < m; ++t) {
-        const float* mp = path ? &mid_hi[HIGHS ? 4 * qi + 2 * t : 0][2 * qj] : &mid_lo[4 * qi + 2 * t][2 * qj];
-        const float2 r0 = *reinterpret_cast<const float2*>(mp), r1 = *reinterpret_cast<const float2*>(mp + F2_TW);
-        l0.x = fmaf(taps.lo0[t], r0.x, l0.x); l0.y = fmaf(taps.lo0[t], r0.y, l0.y);
-        l1.x = fmaf(taps.lo1[t], r1.x, l1.x); l1.y = fmaf(taps.lo1[t], r1.y, l1.y);
-        if constexpr (BP) {
-            const float* bp = path ? &mid_ba[4 * qi + 2 * t][2 * qj] : mp;
-            const float2 b0 = *reinterpret_cast<const float2*>(bp), b1 = *reinterpret_cast<const float2*>(bp + F2_TW);
-            const float k0 = path ? taps.ba0[t] : taps.hi0[t], k1 = path ? taps.ba1[t] : taps.hi1[t];
-            h0.x = fmaf(k0, b1.x, h0.x); h0.y = fmaf(k0, b1.y, h0.y);
-            h1.x = fmaf(k1, b0.x, h1.x); h1.y = fmaf(k1, b0.y, h1.y);
-        } else if (HIGHS) {
-            h0.x = fmaf(taps.hi0[t], r1.x, h0.x); h0.y = fmaf(taps.hi0[t], r1.y, h0.y);
-            h1.x = fmaf(taps.hi1[t], r0.x, h1.x); h1.y = fmaf(taps.hi1[t], r0.y, h1.y);
-        }
-    }
+    const DtQuad2 v = dt_fwd2_quad<HIGHS, BP>(path, qi, qj, m, taps, mid_lo, mid_hi, mid_ba);
     if (!path && ll) {
-        float* lp = ll + plane * OH * (long)OW + (long)oi * OW + oj;
-        *reinterpret_cast<float2*>(lp) = l0;
-        *reinterpret_cast<float2*>(lp + OW) = l1;
+        float* lp = ll + b.plane * OH * (long)OW + (long)oi * OW + oj;
+        *reinterpret_cast<float2*>(lp) = v.l0;
+        *reinterpret_cast<float2*>(lp + OW) = v.l1;
     }
     if (HIGHS) {
         float* q = hi + n * hs.n + c * hs.c + (long)(i0 + qi) * hs.r + (long)(j0 + qj) * hs.w;
         if (path) {
-            dt_q2c(q, hs, vec, 2, 3, l0, l1);                             // hl
-            dt_q2c(q, hs, vec, 1, 4, h0, h1);                             // hh
+            dt_q2c(q, hs, vec, 2, 3, v.l0, v.l1);                         // hl
+            dt_q2c(q, hs, vec, 1, 4, v.h0, v.h1);                         // hh
         } else {
-            dt_q2c(q, hs, vec, 0, 5, h0, h1);                             // lh
+            dt_q2c(q, hs, vec, 0, 5, v.h0, v.h1);                         // lh
         }
     }
 }
@@ -238,72 +127,13 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j1(const float* __restrict__ ll
                                                     int sym, typename DtBank<BP>::T1 taps) {
     __shared__ float cf[4][J1_PR][J1_PC];
     __shared__ float mid_lo[J1_TH][J1_PC], mid_hi[J1_TH][J1_PC], mid_ba[BP ? J1_TH : 1][J1_PC];
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w; b /= tiles_w;
-    const int th = b % tiles_h;
-    const long plane = b / tiles_h;
-    const long n = plane / C, c = plane % C;
-    const int t0 = th * J1_TH, s0 = tw * J1_TW;
-    const int hm = dt_halo1<BP>(L0, L1, taps), a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
-    const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;
+    const DtTile b = dt_tile(tiles_h, tiles_w);
+    const long n = b.plane / C, c = b.plane % C;
     const float* lp = ll ? ll + n * ls.n + c * ls.c : nullptr;
     const float* hp = hi ? hi + n * hs.n + c * hs.c : nullptr;
-
-    for (int r = tid >> 6; r < rows; r += 4) {
-        const int sr = dt_map(t0 - hm + r, H, sym);
-        for (int cc = tid & 63; cc < cols; cc += 64) {
-            const int sc = dt_map(s0 - hm + cc, W, sym);
-            if (sr >= 0 && sc >= 0) dt_stage(lp, ls, hp, hs, sr, sc, &cf[0][r][cc], &cf[1][r][cc], &cf[2][r][cc], &cf[3][r][cc]);
-            else cf[0][r][cc] = cf[1][r][cc] = cf[2][r][cc] = cf[3][r][cc] = 0.f;
-        }
-    }
-    __syncthreads();
-
-    // H pass: lo = col(lh, g1) + col(ll, g0), hi = col(hh, g1) + col(hl, g0), for every tile row and patch column;
-    // BP: hi = col(hl, g0), ba = col(hh, g2)
-    for (int tt = tid >> 6; tt < J1_TH; tt += 4) {
-        for (int cc = tid & 63; cc < cols; cc += 64) {
-            float l1 = 0.f, l0 = 0.f, h1 = 0.f, h0 = 0.f;
-            if (hp) {
-                for (int t = 0; t < L1; ++t) {
-                    l1 = fmaf(taps.f1[t], cf[1][tt + t + a1][cc], l1);
-                    if constexpr (!BP) h1 = fmaf(taps.f1[t], cf[3][tt + t + a1][cc], h1);
-                }
-                for (int t = 0; t < L0; ++t) h0 = fmaf(taps.f0[t], cf[2][tt + t + a0][cc], h0);
-                if constexpr (BP) {
-                    const int a2 = hm - (taps.L2 >> 1);
-                    for (int t = 0; t < taps.L2; ++t) h1 = fmaf(taps.f2[t], cf[3][tt + t + a2][cc], h1);
-                }
-            }
-            if (lp)
-                for (int t = 0; t < L0; ++t) l0 = fmaf(taps.f0[t], cf[0][tt + t + a0][cc], l0);
-            mid_lo[tt][cc] = l1 + l0;
-            if constexpr (BP) { mid_hi[tt][cc] = h0; mid_ba[tt][cc] = h1; }
-            else mid_hi[tt][cc] = h1 + h0;
-        }
-    }
-    __syncthreads();
-
-    float* yp = y + plane * H * (long)W;
-    const int ss = tid & 63, s = s0 + ss;
-    for (int tt = tid >> 6; tt < J1_TH; tt += 4) {
-        const int t = t0 + tt;
-        if (t >= H || s >= W) continue;
-        float vh = 0.f, vl = 0.f;
-        if (hp)
-            for (int k = 0; k < L1; ++k) vh = fmaf(taps.f1[k], mid_hi[tt][ss + k + a1], vh);
-        for (int k = 0; k < L0; ++k) vl = fmaf(taps.f0[k], mid_lo[tt][ss + k + a0], vl);
-        if constexpr (BP) {
-            const int a2 = hm - (taps.L2 >> 1);
-            float vb = 0.f;
-            if (hp)
-                for (int k = 0; k < taps.L2; ++k) vb = fmaf(taps.f2[k], mid_ba[tt][ss + k + a2], vb);
-            yp[(long)t * W + s] = (vh + vl) + vb;
-        } else {
-            yp[(long)t * W + s] = vh + vl;
-        }
-    }
+    const auto stage = [&](int sr, int sc, float* o0, float* o1, float* o2, float* o3) { dt_stage(lp, ls, hp, hs, sr, sc, o0, o1, o2, o3); };
+    dt_inv1<BP>(stage, lp != nullptr, hp != nullptr, y + b.plane * H * (long)W, b.th * J1_TH, b.tw * J1_TW, H, W, sym, L0, L1, taps, cf, mid_lo,
+                mid_hi, mid_ba);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -317,75 +147,13 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll
     __shared__ float mid_lo[I2_TH][I2_PC], mid_hi[I2_TH][I2_PC], mid_ba[BP ? I2_TH : 1][I2_PC];
     __shared__ float tl[BP ? 3 : 2][4][DT_MAXL / 2];
     __shared__ int td[BP ? 3 : 2][4];
-    const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w; b /= tiles_w;
-    const int th = b % tiles_h;
-    const long plane = b / tiles_h;
-    const long n = plane / C, c = plane % C;
-    const int t0 = th * I2_TH, s0 = tw * I2_TW, OH = 2 * R, OW = 2 * Q;
-    const int i0 = t0 >> 2, j0 = s0 >> 2;
-    const int rows = I2_TH / 2 + 2 * m2, cols = I2_TW / 2 + 2 * m2;      // patch (r, cc) is coefficient position 2 i0 - m2 + r
+    const DtTile b = dt_tile(tiles_h, tiles_w);
+    const long n = b.plane / C, c = b.plane % C;
     const float* lp = ll ? ll + n * ls.n + c * ls.c : nullptr;
     const float* hp = hi ? hi + n * hs.n + c * hs.c : nullptr;
-
-    if (tid < 4 * (DT_MAXL / 2)) {                                        // the per-phase taps, for the lane-varying phase of the W pass
-        tl[0][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.lo[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
-        tl[1][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.hi[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
-        if constexpr (BP) tl[2][tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)] = taps.ba[tid / (DT_MAXL / 2)][tid % (DT_MAXL / 2)];
-    }
-    if (tid < 4) {
-        td[0][tid] = taps.dlo[tid]; td[1][tid] = taps.dhi[tid];
-        if constexpr (BP) td[2][tid] = taps.dba[tid];
-    }
-    for (int r = tid >> 6; r < rows; r += 4) {
-        const int sr = dt_map(2 * i0 - m2 + r, R, 1);
-        for (int cc = tid & 63; cc < cols; cc += 64)
-            dt_stage(lp, ls, hp, hs, sr, dt_map(2 * j0 - m2 + cc, Q, 1), &cf[0][r][cc], &cf[1][r][cc], &cf[2][r][cc], &cf[3][r][cc]);
-    }
-    __syncthreads();
-
-    // H pass: a wave takes a tile row (its phase q is uniform), lanes the patch columns
-    for (int tt = tid >> 6; tt < I2_TH; tt += 4) {
-        const int q = tt & 3, ii = tt >> 2;                               // t0 is a multiple of 4
-        const int rl = 2 * ii + td[0][q], rh = 2 * ii + td[1][q], rb = 2 * ii + td[BP ? 2 : 1][q];
-        for (int cc = tid & 63; cc < cols; cc += 64) {
-            float l1 = 0.f, l0 = 0.f, h1 = 0.f, h0 = 0.f;
-            if (hp)
-                for (int t = 0; t < m2; ++t) {
-                    l1 = fmaf(tl[1][q][t], cf[1][rh + 2 * t][cc], l1);
-                    h1 = fmaf(tl[BP ? 2 : 1][q][t], cf[3][rb + 2 * t][cc], h1);     // BP: ba = col(hh, g2)
-                    h0 = fmaf(tl[0][q][t], cf[2][rl + 2 * t][cc], h0);
-                }
-            if (lp)
-                for (int t = 0; t < m2; ++t) l0 = fmaf(tl[0][q][t], cf[0][rl + 2 * t][cc], l0);
-            mid_lo[tt][cc] = l1 + l0;
-            if constexpr (BP) { mid_hi[tt][cc] = h0; mid_ba[tt][cc] = h1; }
-            else mid_hi[tt][cc] = h1 + h0;
-        }
-    }
-    __syncthreads();
-
-    float* yp = y + plane * OH * (long)OW;
-    const int ss = tid & 63, s = s0 + ss, q = ss & 3, jj = ss >> 2;
-    const int cl = 2 * jj + td[0][q], ch = 2 * jj + td[1][q];
-    for (int tt = tid >> 6; tt < I2_TH; tt += 4) {
-        const int t = t0 + tt;
-        if (t >= OH || s >= OW) continue;
-        float vh = 0.f, vl = 0.f;
-        if (hp)
-            for (int k = 0; k < m2; ++k) vh = fmaf(tl[1][q][k], mid_hi[tt][ch + 2 * k], vh);
-        for (int k = 0; k < m2; ++k) vl = fmaf(tl[0][q][k], mid_lo[tt][cl + 2 * k], vl);
-        if constexpr (BP) {
-            const int cb = 2 * jj + td[2][q];
-            float vb = 0.f;
-            if (hp)
-                for (int k = 0; k < m2; ++k) vb = fmaf(tl[2][q][k], mid_ba[tt][cb + 2 * k], vb);
-            yp[(long)t * OW + s] = (vh + vl) + vb;
-        } else {
-            yp[(long)t * OW + s] = vh + vl;
-        }
-    }
+    const auto stage = [&](int sr, int sc, float* o0, float* o1, float* o2, float* o3) { dt_stage(lp, ls, hp, hs, sr, sc, o0, o1, o2, o3); };
+    dt_inv2<BP>(stage, lp != nullptr, hp != nullptr, y + b.plane * (2L * R) * (2L * Q), b.th * I2_TH, b.tw * I2_TW, R, Q, m2, taps, cf, mid_lo,
+                mid_hi, mid_ba, tl, td);
 }
 
 }  // namespace faoctasr
@@ -398,11 +166,10 @@ static int run_fwd_j1(const char* what, const float* x, long x_sn, long x_sc, lo
                       long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W, int L0, int L1,
                       const typename DtBank<BP>::T1& t, int mode, faoctasr_stream_t stream) {
     if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
-    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be even and at least 2", what, H, W);
-    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d", what, mode);
-    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
+    int rc, tiles_h, tiles_w;
     long blocks;
-    int rc;
+    if ((rc = dt_tiles1(what, H, W, &tiles_h, &tiles_w))) return rc;
+    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d", what, mode);
     if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
     const DtLow xs{x_sn, x_sc, x_sr};
     const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
@@ -425,10 +192,9 @@ static int run_fwd_j2(const char* what, const float* x, long x_sn, long x_sc, lo
                       long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W, int m,
                       const typename DtBank<BP>::T2& t, faoctasr_stream_t stream) {
     if (!x || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
-    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be multiples of 4", what, H, W);
-    const int tiles_h = (H / 2 + F2_TH - 1) / F2_TH, tiles_w = (W / 2 + F2_TW - 1) / F2_TW;
+    int rc, tiles_h, tiles_w;
     long blocks;
-    int rc;
+    if ((rc = dt_tiles2f(what, H, W, &tiles_h, &tiles_w))) return rc;
     if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
     const DtLow xs{x_sn, x_sc, x_sr};
     const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
@@ -451,11 +217,10 @@ static int run_inv_j1(const char* what, const float* ll, long ll_sn, long ll_sc,
                       long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W, int L0, int L1,
                       const typename DtBank<BP>::T1& t, int mode, faoctasr_stream_t stream) {
     if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
-    if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be even and at least 2", what, H, W);
-    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d", what, mode);
-    const int tiles_h = (H + J1_TH - 1) / J1_TH, tiles_w = (W + J1_TW - 1) / J1_TW;
+    int rc, tiles_h, tiles_w;
     long blocks;
-    int rc;
+    if ((rc = dt_tiles1(what, H, W, &tiles_h, &tiles_w))) return rc;
+    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d", what, mode);
     if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
     hipLaunchKernelGGL(dtcwt_inv_j1<BP>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
                        DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
@@ -467,10 +232,9 @@ static int run_inv_j2(const char* what, const float* ll, long ll_sn, long ll_sc,
                       long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W, int m,
                       const typename DtBank<BP>::TI& t, faoctasr_stream_t stream) {
     if (!y || (!ll && !hi)) return fail(FAOCTASR_EINVAL, "%s: null pointer", what);
-    if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "%s: the result's H %d W %d must be multiples of 4", what, H, W);
-    const int tiles_h = (H + I2_TH - 1) / I2_TH, tiles_w = (W + I2_TW - 1) / I2_TW;
+    int rc, tiles_h, tiles_w;
     long blocks;
-    int rc;
+    if ((rc = dt_tiles2i(what, H, W, &tiles_h, &tiles_w))) return rc;
     if ((rc = dt_blocks(what, N, C, tiles_h, tiles_w, &blocks))) return rc;
     hipLaunchKernelGGL(dtcwt_inv_j2<BP>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, DtLow{ll_sn, ll_sc, ll_sr}, hi,
                        DtStr{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si}, y, C, H / 2, W / 2, tiles_h, tiles_w, m / 2, t);

@@ -5,8 +5,8 @@
 // over the six complex bandpass orientations of every level of the dual-tree transform (dtcwt.hip); no lowpass term.  r is the
 // smoothed magnitude of the scattering layers (scat.hip) with its bias b, which cancels in the difference.
 //
-// The two analysis kernels are dtcwt_fwd_j1 / dtcwt_fwd_j2 -- same tiles, LDS staging, index maps and q2c (dtcwt_dev.h) -- run
-// by every block twice through the SAME LDS: its tile of x, then its tile of y.  The loop over the two images is not unrolled, so
+// The two analysis kernels run the forward tile bodies of dtcwt_dev.h, as dtcwt_fwd_j1 / dtcwt_fwd_j2 do (two-filter form), every
+// block twice through the SAME LDS: its tile of x, then its tile of y.  The loop over the two images is not unrolled, so
 // both run one instruction sequence (L(x, y) and L(y, x) agree bit for bit); x's complex values wait in registers while y's are
 // computed.  In the place of the bandpass stores:
 //   - one partial sum of |r_x - r_y| per block into `part`: per-thread sum (orientations in a fixed order), a 64-lane butterfly,
@@ -57,16 +57,10 @@ __global__ __launch_bounds__(256) void dtcwt_loss_fwd_j1(const float* __restrict
     __shared__ __attribute__((aligned(16))) float mid_lo[J1_PR][J1_TW];
     __shared__ __attribute__((aligned(16))) float mid_hi[J1_PR][J1_TW];
     __shared__ float red[4];
-    const int tid = threadIdx.x;
-    int bi = blockIdx.x;
-    const int tw = bi % tiles_w; bi /= tiles_w;
-    const int th = bi % tiles_h;
-    const long plane = bi / tiles_h;
-    const long n = plane / C, c = plane % C;
-    const int oi0 = th * J1_TH, oj0 = tw * J1_TW;
-    const int hm = (L0 > L1 ? L0 : L1) >> 1, a0 = hm - (L0 >> 1), a1 = hm - (L1 >> 1);
-    const int rows = J1_TH + 2 * hm, cols = J1_TW + 2 * hm;               // <= J1_PR, J1_PC
-    const int qi = tid >> 5, qj = tid & 31;                               // H pass: a thread owns one 2x2 quad of the tile
+    const DtTile t = dt_tile(tiles_h, tiles_w);
+    const long plane = t.plane, n = plane / C, c = plane % C;
+    const int oi0 = t.th * J1_TH, oj0 = t.tw * J1_TW;
+    const int qi = threadIdx.x >> 5, qj = threadIdx.x & 31;               // H pass: a thread owns one 2x2 quad of the tile
     const int oi = oi0 + 2 * qi, oj = oj0 + 2 * qj;
     const bool live = oi < H && oj < W;                                   // H, W even: a quad is inside or outside as a whole
     float2 z[6], zx[6];
@@ -75,56 +69,19 @@ __global__ __launch_bounds__(256) void dtcwt_loss_fwd_j1(const float* __restrict
 
 #pragma unroll 1
     for (int img = 0; img < 2; ++img) {                                   // one instruction sequence for both images
-        const float* xp = img ? y + n * ys.n + c * ys.c : x + n * xs.n + c * xs.c;
-        const long sr_ = img ? ys.r : xs.r;
         float* ll = img ? lly : llx;
-        for (int r = tid >> 6; r < rows; r += 4) {
-            const int sr = dt_map(oi0 - hm + r, H, sym);
-            for (int cc = tid & 63; cc < cols; cc += 64) {
-                const int sc = dt_map(oj0 - hm + cc, W, sym);
-                patch[r][cc] = (sr >= 0 && sc >= 0) ? xp[sr * sr_ + sc] : 0.f;
-            }
-        }
-        __syncthreads();                                                  // also: every thread is past the first image's H pass
-
-        {   // W pass: thread (r, cc) filters patch row r at tile column cc
-            const int cc = tid & 63;
-            for (int r = tid >> 6; r < rows; r += 4) {
-                float lo = 0.f, hv = 0.f;
-                for (int t = 0; t < L0; ++t) lo = fmaf(taps.f0[t], patch[r][cc + t + a0], lo);
-                for (int t = 0; t < L1; ++t) hv = fmaf(taps.f1[t], patch[r][cc + t + a1], hv);
-                mid_lo[r][cc] = lo;
-                mid_hi[r][cc] = hv;
-            }
-        }
-        __syncthreads();
-
+        dt_fwd1_rows<true, false>(img ? y + n * ys.n + c * ys.c : x + n * xs.n + c * xs.c, img ? ys.r : xs.r, oi0, oj0, H, W, sym, L0, L1, taps,
+                                  patch, mid_lo, mid_hi, nullptr);
         if (live) {
-            float2 vll[2], vlh[2], vhl[2], vhh[2];
-            for (int d = 0; d < 2; ++d) {
-                float2 s = make_float2(0.f, 0.f), u = s, p = s, q = s;
-                for (int t = 0; t < L0; ++t) {
-                    const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a0][2 * qj]);
-                    const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a0][2 * qj]);
-                    s.x = fmaf(taps.f0[t], v.x, s.x); s.y = fmaf(taps.f0[t], v.y, s.y);
-                    p.x = fmaf(taps.f0[t], w.x, p.x); p.y = fmaf(taps.f0[t], w.y, p.y);
-                }
-                for (int t = 0; t < L1; ++t) {
-                    const float2 v = *reinterpret_cast<const float2*>(&mid_lo[2 * qi + d + t + a1][2 * qj]);
-                    const float2 w = *reinterpret_cast<const float2*>(&mid_hi[2 * qi + d + t + a1][2 * qj]);
-                    u.x = fmaf(taps.f1[t], v.x, u.x); u.y = fmaf(taps.f1[t], v.y, u.y);
-                    q.x = fmaf(taps.f1[t], w.x, q.x); q.y = fmaf(taps.f1[t], w.y, q.y);
-                }
-                vll[d] = s; vlh[d] = u; vhl[d] = p; vhh[d] = q;
-            }
+            const DtQuad1 v = dt_fwd1_quad<true, false>(qi, qj, L0, L1, taps, mid_lo, mid_hi, nullptr);
             if (ll) {
                 float* lp = ll + plane * H * (long)W + (long)oi * W + oj;
-                *reinterpret_cast<float2*>(lp) = vll[0];
-                *reinterpret_cast<float2*>(lp + W) = vll[1];
+                *reinterpret_cast<float2*>(lp) = v.ll[0];
+                *reinterpret_cast<float2*>(lp + W) = v.ll[1];
             }
-            dt_q2c_val(vlh[0], vlh[1], &z[0], &z[5]);
-            dt_q2c_val(vhh[0], vhh[1], &z[1], &z[4]);
-            dt_q2c_val(vhl[0], vhl[1], &z[2], &z[3]);
+            dt_q2c_val(v.lh[0], v.lh[1], &z[0], &z[5]);
+            dt_q2c_val(v.hh[0], v.hh[1], &z[1], &z[4]);
+            dt_q2c_val(v.hl[0], v.hl[1], &z[2], &z[3]);
         }
         if (img == 0) {
 #pragma unroll
@@ -155,17 +112,11 @@ __global__ __launch_bounds__(256) void dtcwt_loss_fwd_j2(const float* __restrict
     __shared__ __attribute__((aligned(16))) float mid_lo[F2_PR][F2_TW];
     __shared__ __attribute__((aligned(16))) float mid_hi[F2_PR][F2_TW];
     __shared__ float red[4];
-    const int tid = threadIdx.x;
-    int bi = blockIdx.x;
-    const int tw = bi % tiles_w; bi /= tiles_w;
-    const int th = bi % tiles_h;
-    const long plane = bi / tiles_h;
-    const long n = plane / C, c = plane % C;
+    const DtTile t = dt_tile(tiles_h, tiles_w);
+    const long plane = t.plane, n = plane / C, c = plane % C;
     const int OH = H >> 1, OW = W >> 1, BH = H >> 2, BW = W >> 2;          // of ll; of the bands
-    const int i0 = th * (F2_TH / 2), j0 = tw * (F2_TW / 2);               // first quad row / column = first index of the trees
-    const int rows = 2 * F2_TH + 2 * m - 4, cols = 2 * F2_TW + 2 * m - 4;  // <= F2_PR, F2_PC; patch (r, cc) is x position 4 i0 + 2 - m + r
-    // H pass: 4 x 32 quads; threads 0..127 take the W-lowpass plane (ll, lh), threads 128..255 the W-highpass plane (hl, hh)
-    const int path = tid >> 7, qi = (tid & 127) >> 5, qj = tid & 31;
+    const int i0 = t.th * (F2_TH / 2), j0 = t.tw * (F2_TW / 2);           // first quad row / column = first index of the trees
+    const int tid = threadIdx.x, path = tid >> 7, qi = (tid & 127) >> 5, qj = tid & 31;
     const int pi = i0 + qi, pj = j0 + qj;
     const bool live = pi < BH && pj < BW;
     float2 z[4], zx[4];                                                   // path 0: lh z1, z2 (15, 165); path 1: hl z1, z2 (75, 105), hh z1, z2 (45, 135)
@@ -174,51 +125,21 @@ __global__ __launch_bounds__(256) void dtcwt_loss_fwd_j2(const float* __restrict
 
 #pragma unroll 1
     for (int img = 0; img < 2; ++img) {
-        const float* xp = img ? y + n * ys.n + c * ys.c : x + n * xs.n + c * xs.c;
-        const long sr_ = img ? ys.r : xs.r;
         float* ll = img ? lly : llx;
-        for (int r = tid >> 6; r < rows; r += 4) {
-            const int sr = dt_map(4 * i0 + 2 - m + r, H, 1);
-            for (int cc = tid & 63; cc < cols; cc += 64)
-                patch[r][cc] = xp[sr * sr_ + dt_map(4 * j0 + 2 - m + cc, W, 1)];
-        }
-        __syncthreads();
-
-        {   // W pass: tile column cc = 2 i + p; the float2 at patch column 4 i + 2 t holds the samples at offsets 2 - m and 3 - m
-            const int cc = tid & 63, i = cc >> 1, p = cc & 1;
-            for (int r = tid >> 6; r < rows; r += 4) {
-                float lo = 0.f, hv = 0.f;
-                for (int t = 0; t < m; ++t) {
-                    const float2 v = *reinterpret_cast<const float2*>(&patch[r][4 * i + 2 * t]);
-                    lo = fmaf(p ? taps.lo1[t] : taps.lo0[t], p ? v.y : v.x, lo);
-                    hv = fmaf(p ? taps.hi1[t] : taps.hi0[t], p ? v.x : v.y, hv);
-                }
-                mid_lo[r][cc] = lo;
-                mid_hi[r][cc] = hv;
-            }
-        }
-        __syncthreads();
-
+        dt_fwd2_rows<true, false>(img ? y + n * ys.n + c * ys.c : x + n * xs.n + c * xs.c, img ? ys.r : xs.r, i0, j0, H, W, m, taps, patch,
+                                  mid_lo, mid_hi, nullptr);
         if (live) {
-            float2 l0 = make_float2(0.f, 0.f), l1 = l0, h0 = l0, h1 = l0;     // lowpass call rows 2qi, 2qi+1; highpass call likewise
-            for (int t = 0; t < m; ++t) {
-                const float* mp = path ? &mid_hi[4 * qi + 2 * t][2 * qj] : &mid_lo[4 * qi + 2 * t][2 * qj];
-                const float2 r0 = *reinterpret_cast<const float2*>(mp), r1 = *reinterpret_cast<const float2*>(mp + F2_TW);
-                l0.x = fmaf(taps.lo0[t], r0.x, l0.x); l0.y = fmaf(taps.lo0[t], r0.y, l0.y);
-                l1.x = fmaf(taps.lo1[t], r1.x, l1.x); l1.y = fmaf(taps.lo1[t], r1.y, l1.y);
-                h0.x = fmaf(taps.hi0[t], r1.x, h0.x); h0.y = fmaf(taps.hi0[t], r1.y, h0.y);
-                h1.x = fmaf(taps.hi1[t], r0.x, h1.x); h1.y = fmaf(taps.hi1[t], r0.y, h1.y);
-            }
+            const DtQuad2 v = dt_fwd2_quad<true, false>(path, qi, qj, m, taps, mid_lo, mid_hi, nullptr);
             if (path) {
-                dt_q2c_val(l0, l1, &z[0], &z[1]);                         // hl
-                dt_q2c_val(h0, h1, &z[2], &z[3]);                         // hh
+                dt_q2c_val(v.l0, v.l1, &z[0], &z[1]);                     // hl
+                dt_q2c_val(v.h0, v.h1, &z[2], &z[3]);                     // hh
             } else {
                 if (ll) {
                     float* lp = ll + plane * OH * (long)OW + (long)(2 * pi) * OW + 2 * pj;
-                    *reinterpret_cast<float2*>(lp) = l0;
-                    *reinterpret_cast<float2*>(lp + OW) = l1;
+                    *reinterpret_cast<float2*>(lp) = v.l0;
+                    *reinterpret_cast<float2*>(lp + OW) = v.l1;
                 }
-                dt_q2c_val(h0, h1, &z[0], &z[1]);                         // lh
+                dt_q2c_val(v.h0, v.h1, &z[0], &z[1]);                     // lh
             }
         }
         if (img == 0) {
@@ -270,17 +191,6 @@ static int dl_common(const char* what, const void* x, const void* y, const void*
     return FAOCTASR_OK;
 }
 
-static int dl_tiles(const char* what, int H, int W, int level1, int* tiles_h, int* tiles_w) {
-    if (level1) {
-        if (H < 2 || W < 2 || (H & 1) || (W & 1)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be even and at least 2", what, H, W);
-        *tiles_h = (H + J1_TH - 1) / J1_TH; *tiles_w = (W + J1_TW - 1) / J1_TW;
-    } else {
-        if (H < 4 || W < 4 || (H & 3) || (W & 3)) return fail(FAOCTASR_EINVAL, "%s: H %d W %d must be multiples of 4", what, H, W);
-        *tiles_h = (H / 2 + F2_TH - 1) / F2_TH; *tiles_w = (W / 2 + F2_TW - 1) / F2_TW;
-    }
-    return FAOCTASR_OK;
-}
-
 }  // namespace faoctasr
 
 using namespace faoctasr;
@@ -288,7 +198,8 @@ using namespace faoctasr;
 extern "C" long faoctasr_dtcwt_loss_workspace_floats(long N, int C, int H, int W, int level1) {
     int tiles_h, tiles_w;
     long blocks;
-    if (dl_tiles("dtcwt_loss_workspace_floats", H, W, level1, &tiles_h, &tiles_w)) return -1;
+    if (level1 ? dt_tiles1("dtcwt_loss_workspace_floats", H, W, &tiles_h, &tiles_w) : dt_tiles2f("dtcwt_loss_workspace_floats", H, W, &tiles_h, &tiles_w))
+        return -1;
     if (dt_blocks("dtcwt_loss_workspace_floats", N, C, tiles_h, tiles_w, &blocks)) return -1;
     return blocks;
 }
@@ -303,7 +214,7 @@ extern "C" int faoctasr_dtcwt_loss_fwd_j1(const float* x, long x_sn, long x_sc, 
     if ((rc = dl_common("dtcwt_loss_fwd_j1", x, y, part, scale, bias2))) return rc;
     if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_loss_fwd_j1: unknown padding mode %d", mode);
     int tiles_h, tiles_w;
-    if ((rc = dl_tiles("dtcwt_loss_fwd_j1", H, W, 1, &tiles_h, &tiles_w))) return rc;
+    if ((rc = dt_tiles1("dtcwt_loss_fwd_j1", H, W, &tiles_h, &tiles_w))) return rc;
     long blocks;
     if ((rc = dt_blocks("dtcwt_loss_fwd_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
     hipLaunchKernelGGL(dtcwt_loss_fwd_j1, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, DtLow{x_sn, x_sc, x_sr}, y,
@@ -320,11 +231,11 @@ extern "C" int faoctasr_dtcwt_loss_fwd_j2(const float* x, long x_sn, long x_sc, 
     if (rc) return rc;
     if ((rc = dl_common("dtcwt_loss_fwd_j2", x, y, part, scale, bias2))) return rc;
     int tiles_h, tiles_w;
-    if ((rc = dl_tiles("dtcwt_loss_fwd_j2", H, W, 0, &tiles_h, &tiles_w))) return rc;
+    if ((rc = dt_tiles2f("dtcwt_loss_fwd_j2", H, W, &tiles_h, &tiles_w))) return rc;
     long blocks;
     if ((rc = dt_blocks("dtcwt_loss_fwd_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
     DtTaps2 t = {};
-    for (int k = 0; k < m; ++k) { t.lo0[k] = h0b[k]; t.lo1[k] = h0a[k]; t.hi0[k] = h1a[k]; t.hi1[k] = h1b[k]; }
+    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, m);
     hipLaunchKernelGGL(dtcwt_loss_fwd_j2, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, DtLow{x_sn, x_sc, x_sr}, y,
                        DtLow{y_sn, y_sc, y_sr}, llx, lly, reinterpret_cast<float2*>(gx), reinterpret_cast<float2*>(gy), part, scale, bias2, C,
                        H, W, tiles_h, tiles_w, m, t);
