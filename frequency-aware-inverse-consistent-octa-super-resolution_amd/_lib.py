@@ -61,6 +61,9 @@ _SIG = {
     "phase_loss_workspace_floats": (_L, "iiii"),
     "phase_loss_fwd": (_I, "pppp f ppp iiii p"),
     "phase_loss_bwd": (_I, "ppp f ppp iiii p"),
+    "ffl_workspace_floats": (_L, "iiii"),
+    "ffl_fwd": (_I, "pppp f ii ppp iiii p"),
+    "ffl_bwd": (_I, "pppp f i ppp iiii p"),
     "tv_loss_workspace_floats": (_L, "iiii"),
     "tv_loss_fwd": (_I, "ppp iiii f p"),
     "tv_loss_bwd": (_I, "ppp iiii f p"),

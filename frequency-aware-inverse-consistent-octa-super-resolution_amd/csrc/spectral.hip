@@ -21,6 +21,8 @@
 // would change the value everywhere).
 //
 // Block 256 threads, output tile 64x64, K chunk 16; waves 2x2, four 32x32 accumulators each (Re_x, J_x, Re_y, J_y).
+//
+// The focal frequency loss (second half of this file) runs on the same tables, row pass and tile, with two accumulators.
 #include <cstdint>
 #include "common.h"
 
@@ -307,6 +309,267 @@ static int phase_check(const char* what, const void* ws, int N, int C, int H, in
     return FAOCTASR_OK;
 }
 
+
+// ---- focal frequency loss (Jiang, Dai, Wu, Loy, ICCV 2021) -----------------------------------------------------------------
+//   D = fft2(x, ortho) - fft2(y, ortho) = fft2(x - y, ortho),  q = |D|^2,  w = phi(q) / phi(M),  L = mean(w q)
+//   phi(q) = q^(alpha/2) or log(q^(alpha/2) + 1),  M = max q over the plane (or the batch); w is a constant for the gradient.
+// One spectrum per image PAIR: the column pass stages P_x - P_y and Q_x - Q_y, so a wave tile carries two accumulators (Re, J).
+// The weight's normaliser factorises out of the sum, sum w q = (sum phi(q) q) / phi(M): one pass, a partial sum and a partial
+// maximum per block, and the finishing kernel divides.  dL/dx = (2/count) Re ifft2(w D, ortho) = -dL/dy: one transform per backward.
+struct FflWs {
+    double* stats;      // [N*C][2]: sum phi(q) q, max q
+    float* part;        // [N*C][tiles][2]
+    float* pq;          // [2 (x,y)][N*C][H][2W]: [P | Q] in the forward; its first half is [T1 | T2] in the backward
+    long total;
+};
+
+static FflWs ffl_ws(float* ws, long N, long C, long H, long W) {
+    FflWs p;
+    const long tiles = ((H + PH_T - 1) / PH_T) * ((W + PH_T - 1) / PH_T);
+    long off = 0;
+    p.stats = (double*)ws;
+    off += 4 * N * C;
+    p.part = ws + off;
+    off += 2 * N * C * tiles;
+    off = (off + 3) & ~3L;
+    p.pq = ws + off;
+    off += 4 * N * C * H * W;
+    p.total = off;
+    return p;
+}
+
+enum { FFL_ONE = 0, FFL_SQRT = 1, FFL_ID = 2, FFL_POW = 3 };
+
+// phi(q): the exact forms for alpha = 0, 1, 2 (0^0 = 1, as torch.pow), powf otherwise
+__device__ __forceinline__ float ffl_phi(float q, int form, float half_alpha, int logm) {
+    float w;
+    switch (form) {
+        case FFL_ONE: w = 1.f; break;
+        case FFL_SQRT: w = sqrtf(q); break;
+        case FFL_ID: w = q; break;
+        default: w = powf(q, half_alpha); break;
+    }
+    return logm ? log1pf(w) : w;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// column pass of the difference spectrum: Re = s (C_H P - S_H Q), J = s (S_H P + C_H Q) with P = P_x - P_y, Q = Q_x - Q_y formed
+// while staging and s = 1/sqrt(HW); q = Re^2 + J^2 in the accumulator registers; one partial (sum phi(q) q, max q) per block.
+// planes == nullptr: no gradient is wanted and the spectrum is not stored.
+__global__ __launch_bounds__(256) void ffl_col_fwd_kernel(const float* __restrict__ pq, const float* __restrict__ tabH,
+                                                          float* __restrict__ planes, float* __restrict__ part, int H, int W, long imgs,
+                                                          float scale, int form, float half_alpha, int logm) {
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[2][PH_KC * PH_T];
+    __shared__ float red[8];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int u0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const float* pqx = pq + img * H * 2 * W;
+    const float* pqy = pq + (imgs + img) * H * 2 * W;
+    f32x16 re, jm;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) re[r] = jm[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, u0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int k = k0 + (e >> 6), v = v0 + (e & 63);
+            const bool ok = k < H && v < W;
+            const long o = (long)k * 2 * W + v;
+            Bs[0][e] = ok ? pqx[o] - pqy[o] : 0.f;
+            Bs[1][e] = ok ? pqx[o + W] - pqy[o + W] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float p = Bs[0][bo], q = Bs[1][bo];
+            re = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, p, re, 0, 0, 0);
+            jm = __builtin_amdgcn_mfma_f32_32x32x2f32(as, p, jm, 0, 0, 0);
+            re = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, q, re, 0, 0, 0);
+            jm = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, q, jm, 0, 0, 0);
+        }
+    }
+    // epilogue: lanes outside the plane (remainder tiles) add 0 to the sum and to the maximum (q >= 0)
+    const int v = v0 + wn * 32 + l31;
+    float sum = 0.f, mx = 0.f;
+    if (v < W) {
+        const long hw = (long)H * W;
+        float* pl = planes ? planes + img * 2 * hw : nullptr;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int u = u0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (u < H) {
+                const float r = re[rr] * scale, j = jm[rr] * scale;
+                const float q = r * r + j * j;
+                sum += ffl_phi(q, form, half_alpha, logm) * q;
+                mx = fmaxf(mx, q);
+                if (pl) {
+                    const long o = (long)u * W + v;
+                    pl[o] = r;
+                    pl[hw + o] = j;
+                }
+            }
+        }
+    }
+    sum = wave_sum(sum);
+    mx = wave_max(mx);
+    if (lane == 0) {
+        red[wave] = sum;
+        red[4 + wave] = mx;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const long tile = (long)blockIdx.y * gridDim.x + blockIdx.x, tiles = (long)gridDim.x * gridDim.y;
+        float* o = part + (img * tiles + tile) * 2;
+        o[0] = (red[0] + red[1]) + (red[2] + red[3]);
+        o[1] = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
+    }
+}
+
+__device__ __forceinline__ double ffl_phi_d(double q, int form, double half_alpha, int logm) {
+    double w;
+    switch (form) {
+        case FFL_ONE: w = 1.0; break;
+        case FFL_SQRT: w = sqrt(q); break;
+        case FFL_ID: w = q; break;
+        default: w = pow(q, half_alpha); break;
+    }
+    return logm ? log1p(w) : w;
+}
+
+// single block.  Thread t owns planes t, t + 256, ...: it adds a plane's partial sums in index order in double and takes its
+// maximum; the block reduces the maxima over the batch (batch_matrix); every plane's sum is divided by phi(M) (a plane with
+// M = 0 adds exactly 0) and the quotients are added per thread in plane order, then over the threads by a fixed tree.
+// inv_phi (may be nullptr) keeps 1 / phi(M) per plane (0 where phi(M) = 0) for the backward.
+__global__ __launch_bounds__(256) void ffl_finish_kernel(const float* __restrict__ part, double* __restrict__ stats,
+                                                         float* __restrict__ inv_phi, float* __restrict__ loss, long imgs, long tiles,
+                                                         double count, int form, double half_alpha, int logm, int batch) {
+    __shared__ double red[256];
+    __shared__ float mxs[256];
+    const int tid = threadIdx.x;
+    float tmax = 0.f;
+    for (long p = tid; p < imgs; p += 256) {
+        const float* q = part + p * tiles * 2;
+        double s = 0.0;
+        float m = 0.f;
+        for (long i = 0; i < tiles; ++i) {
+            s += (double)q[2 * i];
+            m = fmaxf(m, q[2 * i + 1]);
+        }
+        stats[2 * p] = s;
+        stats[2 * p + 1] = (double)m;
+        tmax = fmaxf(tmax, m);
+    }
+    mxs[tid] = tmax;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) mxs[tid] = fmaxf(mxs[tid], mxs[tid + o]);
+        __syncthreads();
+    }
+    const double mall = (double)mxs[0];
+    double acc = 0.0;
+    for (long p = tid; p < imgs; p += 256) {
+        const double ph = ffl_phi_d(batch ? mall : stats[2 * p + 1], form, half_alpha, logm);
+        const bool ok = ph > 0.0;
+        if (inv_phi) inv_phi[p] = ok ? (float)(1.0 / ph) : 0.f;
+        if (ok) acc += stats[2 * p] / ph;
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) *loss = (float)(red[0] / count);
+}
+
+// [T1 | T2] = [C_H dRe + S_H dJ | C_H dJ - S_H dRe] with (dRe, dJ) = g * coef * phi(q) / phi(M) * (Re, J) formed from the saved
+// planes while they are staged; coef = +-2 / (count sqrt(HW)) carries the mean, the ortho scale and the side (dx: +, dy: -)
+__global__ __launch_bounds__(256) void ffl_col_bwd_kernel(const float* __restrict__ planes, const float* __restrict__ inv_phi,
+                                                          const float* __restrict__ tabH, const float* __restrict__ g,
+                                                          float* __restrict__ T, int H, int W, float coef, int form, float half_alpha,
+                                                          int logm) {
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[2][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int h0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const long hw = (long)H * W;
+    const float* pl = planes + img * 2 * hw;
+    const float gs = g[0] * coef, ip = inv_phi[img];
+    const int sv = v0 + (tid & 63);
+    f32x16 t1, t2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t1[r] = t2[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, h0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int u = k0 + (e >> 6);
+            float dr = 0.f, dj = 0.f;
+            if (u < H && sv < W) {
+                const long o = (long)u * W + sv;
+                const float R = pl[o], J = pl[hw + o];
+                const float w = gs * (ffl_phi(R * R + J * J, form, half_alpha, logm) * ip);
+                dr = w * R;
+                dj = w * J;
+            }
+            Bs[0][e] = dr;
+            Bs[1][e] = dj;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float dr = Bs[0][bo], dj = Bs[1][bo];
+            t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1, 0, 0, 0);
+            t2 = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2, 0, 0, 0);
+            t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1, 0, 0, 0);
+            t2 = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2, 0, 0, 0);
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < W) {
+        float* To = T + img * H * 2 * W;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int h = h0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (h < H) {
+                const long o = (long)h * 2 * W + v;
+                To[o] = t1[rr];
+                To[o + W] = t2[rr];
+            }
+        }
+    }
+}
+
+// the second gradient of the focal frequency loss: dy = -dx, exactly
+__global__ __launch_bounds__(256) void negate_kernel(const float* __restrict__ a, float* __restrict__ out, long n) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = -a[i];
+}
+
+static int ffl_check(const char* what, const void* ws, int N, int C, int H, int W, float alpha) {
+    int rc = phase_check(what, ws, N, C, H, W, 1.f);
+    if (rc) return rc;
+    if (!(alpha >= 0.f) || alpha > 3.0e38f) return fail(FAOCTASR_EINVAL, "%s: alpha %g must be finite and >= 0", what, (double)alpha);
+    return FAOCTASR_OK;
+}
+
+static int ffl_form(float alpha) { return alpha == 0.f ? FFL_ONE : alpha == 1.f ? FFL_SQRT : alpha == 2.f ? FFL_ID : FFL_POW; }
+
 }  // namespace faoctasr
 
 using namespace faoctasr;
@@ -376,4 +639,67 @@ extern "C" int faoctasr_phase_loss_bwd(const float* g, const float* tabH, const 
                                       stream);
     }
     return faoctasr_sgemm_batched(dx ? p.pq : p.pq + sT, stacked, dx ? dx : dy, (int)(imgs * H), W, 2 * W, 2 * W, W, W, 0, 0, 0, 1, stream);
+}
+
+extern "C" long faoctasr_ffl_workspace_floats(int N, int C, int H, int W) {
+    if (N < 1 || C < 1 || H < 2 || W < 2) {
+        fail(FAOCTASR_EINVAL, "ffl_workspace_floats: bad shape N %d C %d H %d W %d (H, W >= 2)", N, C, H, W);
+        return -1;
+    }
+    return ffl_ws(nullptr, N, C, H, W).total;
+}
+
+extern "C" int faoctasr_ffl_fwd(const float* x, const float* y, const float* tabH, const float* tabW, float alpha, int log_matrix,
+                                int batch_matrix, float* loss, float* planes, float* workspace, int N, int C, int H, int W,
+                                faoctasr_stream_t stream) {
+    if (!x || !y || !tabH || !tabW || !loss || !workspace) return fail(FAOCTASR_EINVAL, "ffl_fwd: null pointer");
+    int rc = ffl_check("ffl_fwd", workspace, N, C, H, W, alpha);
+    if (rc) return rc;
+    const FflWs p = ffl_ws(workspace, N, C, H, W);
+    const long imgs = (long)N * C;
+    // row pass [P | Q] = X [C_W | S_W]: x and y as the two batch entries of one launch (the stride is their address difference)
+    const intptr_t diff = (intptr_t)y - (intptr_t)x;
+    if (diff % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "ffl_fwd: x and y are not 4-byte aligned to each other");
+    rc = faoctasr_sgemm_batched(x, tabW, p.pq, (int)(imgs * H), 2 * W, W, W, 2 * W, 2 * W, (long)(diff / (intptr_t)sizeof(float)), 0,
+                                imgs * H * 2 * W, 2, stream);
+    if (rc) return rc;
+    const int form = ffl_form(alpha);
+    const double hw = (double)H * (double)W;
+    dim3 grid((W + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(ffl_col_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float*)p.pq, tabH, planes, p.part, H, W, imgs,
+                       (float)(1.0 / sqrt(hw)), form, 0.5f * alpha, log_matrix ? 1 : 0);
+    rc = check_launch("ffl_fwd (column pass)");
+    if (rc) return rc;
+    // 1 / phi(M) per plane follows the planes in the caller's buffer
+    hipLaunchKernelGGL(ffl_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)p.part, p.stats,
+                       planes ? planes + 2 * imgs * H * W : nullptr, loss, imgs, (long)grid.x * grid.y, (double)imgs * hw, form,
+                       0.5 * (double)alpha, log_matrix ? 1 : 0, batch_matrix ? 1 : 0);
+    return check_launch("ffl_fwd (finish)");
+}
+
+extern "C" int faoctasr_ffl_bwd(const float* g, const float* planes, const float* tabH, const float* tabW, float alpha, int log_matrix,
+                                float* dx, float* dy, float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream) {
+    if (!g || !planes || !tabH || !tabW || !workspace) return fail(FAOCTASR_EINVAL, "ffl_bwd: null pointer");
+    int rc = ffl_check("ffl_bwd", workspace, N, C, H, W, alpha);
+    if (rc) return rc;
+    if (!dx && !dy) return FAOCTASR_OK;
+    const FflWs p = ffl_ws(workspace, N, C, H, W);
+    const long imgs = (long)N * C;
+    const double hw = (double)H * (double)W;
+    // the transform runs once, for the side that is wanted (dx when both are): dL/dy = -dL/dx
+    const double coef = (dx ? 2.0 : -2.0) / ((double)imgs * hw * sqrt(hw));
+    dim3 grid((W + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(ffl_col_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, planes, planes + 2 * imgs * H * W, tabH, g, p.pq, H, W,
+                       (float)coef, ffl_form(alpha), 0.5f * alpha, log_matrix ? 1 : 0);
+    rc = check_launch("ffl_bwd (column pass)");
+    if (rc) return rc;
+    // dX = [T1 | T2] [C_W ; S_W]: the stacked table is the second half of the table buffer
+    float* first = dx ? dx : dy;
+    rc = faoctasr_sgemm_batched(p.pq, tabW + 2L * W * W, first, (int)(imgs * H), W, 2 * W, 2 * W, W, W, 0, 0, 0, 1, stream);
+    if (rc || !(dx && dy)) return rc;
+    const long n = imgs * H * W;
+    const long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(negate_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, (const float*)dx,
+                       dy, n);
+    return check_launch("ffl_bwd (negation)");
 }

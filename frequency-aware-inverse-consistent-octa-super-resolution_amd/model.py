@@ -50,6 +50,26 @@ class phase_consistency_loss(nn.Module):
         return ops.phase_loss(x, y, self.radius)
 
 
+class FocalFrequencyLoss(nn.Module):
+    """The focal frequency loss (Jiang, Dai, Wu, Loy, ICCV 2021; not in the reference): ``loss_weight`` times the mean over the
+    ortho-normalised spectrum of ``w |F(pred) - F(target)|^2``, every bin weighted by how wrong it currently is
+    (``w = |F(pred) - F(target)|^alpha``, ``log_matrix``: ``log(w + 1)``, normalised by its maximum per plane or, with
+    ``batch_matrix``, per batch; a constant for the gradient).  Where ``phase_consistency_loss`` is blind to scale, this one is
+    a distance.  One fused HIP path (``ops.focal_frequency_loss``); ``TrainStep(ffl_weight=...)`` is the opt-in term."""
+
+    def __init__(self, loss_weight=1.0, alpha=1.0, log_matrix=False, batch_matrix=False):
+        super().__init__()
+        self.loss_weight = loss_weight
+        self.alpha = ops.check_ffl_alpha(alpha)
+        self.log_matrix, self.batch_matrix = bool(log_matrix), bool(batch_matrix)
+
+    def forward(self, pred, target):
+        return self.loss_weight * ops.focal_frequency_loss(pred, target, self.alpha, self.log_matrix, self.batch_matrix)
+
+    def extra_repr(self):
+        return "loss_weight=%g, alpha=%g, log_matrix=%s, batch_matrix=%s" % (self.loss_weight, self.alpha, self.log_matrix, self.batch_matrix)
+
+
 class Discriminator(nn.Module):
     """PatchGAN of model.py:86-127: 4x4 convs with bias, five stride-2 stages then two stride-1,
     BatchNorm2d + LeakyReLU(0.2) from the second conv on."""

@@ -2308,6 +2308,71 @@ def phase_loss(x, y, radius=5.0):
 
 
 # ----------------------------------------------------------------------------------------
+# focal frequency loss (Jiang et al., ICCV 2021) on the same DFT GEMMs
+# ----------------------------------------------------------------------------------------
+def check_ffl_alpha(alpha):
+    """``alpha`` of the focal frequency loss as a float; finite and >= 0, or ValueError."""
+    alpha = float(alpha)
+    if not (math.isfinite(alpha) and alpha >= 0.0):
+        raise ValueError("focal frequency loss: alpha must be finite and >= 0, got %r" % alpha)
+    return alpha
+
+
+class _FocalFrequencyLoss(Function):
+    @staticmethod
+    def forward(ctx, x, y, alpha, log_matrix, batch_matrix, save):
+        x, y = _c(x), _c(y)
+        N, C, H, W = x.shape
+        tab_h, tab_w = dft_tables(H, x.device), dft_tables(W, x.device)
+        n = _lib.load().faoctasr_ffl_workspace_floats(N, C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_ffl_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = torch.empty(n, dtype=torch.float32, device=x.device)        # scratch of this call: free again behind it on the stream
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        # Re, -Im of the difference spectrum and 1 / phi(M) per plane: stored only when a backward can follow (``save``)
+        planes = torch.empty(N * C * (2 * H * W + 1), dtype=torch.float32, device=x.device) if save else None
+        call("ffl_fwd", ptr(x), ptr(y), ptr(tab_h), ptr(tab_w), alpha, int(log_matrix), int(batch_matrix), ptr(out), ptr(planes), ptr(ws),
+             N, C, H, W, stream_ptr())
+        if save:
+            ctx.save_for_backward(planes, tab_h, tab_w)
+        ctx.cfg = (alpha, int(log_matrix), N, C, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        planes, tab_h, tab_w = ctx.saved_tensors
+        alpha, log_matrix, N, C, H, W = ctx.cfg
+        g = _c(g)
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=planes.device) if ctx.needs_input_grad[0] else None
+        dy = torch.empty((N, C, H, W), dtype=torch.float32, device=planes.device) if ctx.needs_input_grad[1] else None
+        ws = torch.empty(_lib.load().faoctasr_ffl_workspace_floats(N, C, H, W), dtype=torch.float32, device=planes.device)
+        call("ffl_bwd", ptr(g), ptr(planes), ptr(tab_h), ptr(tab_w), alpha, log_matrix, ptr(dx), ptr(dy), ptr(ws), N, C, H, W, stream_ptr())
+        return dx, dy, None, None, None, None
+
+
+def focal_frequency_loss(x, y, alpha=1.0, log_matrix=False, batch_matrix=False):
+    """The focal frequency loss of Jiang, Dai, Wu and Loy (ICCV 2021) for x, y (N,C,H,W) fp32 on one GPU, as a 0-dim fp32 tensor
+    with gradients to both inputs: with ``D = fft2(x, norm="ortho") - fft2(y, norm="ortho")`` and ``q = |D|^2`` per plane,
+    ``mean(w * q)`` where ``w = sqrt(q)^alpha`` (``log_matrix``: ``log(w + 1)``), divided by its maximum over the plane
+    (``batch_matrix``: over the whole batch), NaN -> 0, and detached.  ``alpha = 0`` is the mean squared error.  One transform of
+    ``x - y`` serves both images and the forward is one pass (csrc/spectral.hip); ``dL/dy`` is the exact negation of ``dL/dx``.
+    The paper's ``patch_factor`` and ``ave_spectrum`` are not offered; no double backward.  Bit-reproducible, always exact fp32
+    (``conv_precision`` does not apply)."""
+    alpha = check_ffl_alpha(alpha)
+    if not (torch.is_tensor(x) and torch.is_tensor(y)) or x.dim() != 4 or x.shape != y.shape:
+        raise _lib.KernelError("focal_frequency_loss operands must be (N,C,H,W) tensors of one shape: %s vs %s"
+                               % (tuple(getattr(x, "shape", ())), tuple(getattr(y, "shape", ()))))
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise _lib.KernelError("focal_frequency_loss operands must be fp32, got %s and %s" % (x.dtype, y.dtype))
+    if not (x.is_cuda and y.is_cuda) or x.device != y.device:
+        raise _lib.KernelError("focal_frequency_loss runs as HIP kernels on one GPU; got devices %s and %s" % (x.device, y.device))
+    if x.shape[2] < 2 or x.shape[3] < 2:
+        raise _lib.KernelError("focal_frequency_loss needs H, W >= 2, got %s" % (tuple(x.shape),))
+    save = torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)         # grad mode is off inside Function.forward
+    return _FocalFrequencyLoss.apply(x, y, alpha, bool(log_matrix), bool(batch_matrix), save)
+
+
+# ----------------------------------------------------------------------------------------
 # total-variation loss (model.py:17-33)
 # ----------------------------------------------------------------------------------------
 class _TVLoss(Function):

@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
-from .model import FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
+from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
 from .ssim import MSSSIM
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
@@ -265,7 +265,8 @@ class TrainStep:
                  reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
-                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None):
+                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
+                 ffl_batch_matrix=False):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -298,7 +299,12 @@ class TrainStep:
         ``msssim_weight`` (default 0: nothing is constructed or launched): adds ``loss_msssim = msssim_weight * ((1 - MS(recovered_A,
         real_A)) + (1 - MS(recovered_B, real_B)))`` to ``loss_G``, MS the multi-scale SSIM ``MSSSIM(levels=msssim_levels,
         weights=msssim_weights)``: the contrast-structure factor at every dyadic scale and the luminance factor at the coarsest, so
-        that a reconstruction with the capillaries right and the large-vessel contrast wrong no longer scores well."""
+        that a reconstruction with the capillaries right and the large-vessel contrast wrong no longer scores well.
+
+        ``ffl_weight`` (default 0: nothing is constructed or launched): adds ``loss_ffl = ffl_weight * (L(recovered_A, real_A) +
+        L(recovered_B, real_B))`` to ``loss_G``, L the focal frequency loss ``FocalFrequencyLoss(alpha=ffl_alpha,
+        log_matrix=ffl_log_matrix, batch_matrix=ffl_batch_matrix)``: a squared distance between the two spectra in which every bin
+        is weighted by how wrong it currently is, where the phase term is blind to scale."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -335,6 +341,12 @@ class TrainStep:
         #: opt-in multi-scale SSIM term on the cycle reconstructions (ssim.MSSSIM; 0 = off, no module is built)
         self.msssim_weight = msssim_weight
         self.msssim = MSSSIM(levels=msssim_levels, weights=msssim_weights).to(dev) if msssim_weight else None
+        #: opt-in focal frequency term on the cycle reconstructions (model.FocalFrequencyLoss; 0 = off, no module is built)
+        if not (isinstance(ffl_weight, (int, float)) and math.isfinite(ffl_weight) and ffl_weight >= 0):
+            raise ValueError("ffl_weight must be a finite number >= 0, got %r" % (ffl_weight,))
+        self.ffl_weight = ffl_weight
+        self.ffl = (FocalFrequencyLoss(alpha=ffl_alpha, log_matrix=ffl_log_matrix, batch_matrix=ffl_batch_matrix)
+                    if ffl_weight else None)
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -624,7 +636,7 @@ class TrainStep:
         return self.dwt_loss(img)[1]
 
     def _extension_terms(self, rec, real):
-        """One image pair's share of the opt-in terms of ``generator_loss`` (SSIM: train.py:234; wavelet-HF L1; spectral phase)."""
+        """One image pair's share of the opt-in terms of ``generator_loss`` (SSIM: train.py:234; wavelet-HF L1; spectral phase; focal frequency)."""
         t = {}
         if self.ssim_weight:
             t["loss_ssim"] = self.ssim_weight * (1 - ops.ssim(rec, real))
@@ -642,6 +654,8 @@ class TrainStep:
             t["loss_cwssim"] = self.cwssim_weight * (1 - self.cwssim(rec, real))
         if self.msssim_weight:
             t["loss_msssim"] = self.msssim_weight * (1 - self.msssim(rec, real))
+        if self.ffl_weight:
+            t["loss_ffl"] = self.ffl_weight * self.ffl(rec, real)
         return t
 
     def generator_loss(self, o, real_A, real_B):
@@ -688,6 +702,9 @@ class TrainStep:
         if self.msssim_weight:
             L["loss_msssim"] = self.msssim_weight * ((1 - self.msssim(o["recovered_A"], real_A)) + (1 - self.msssim(o["recovered_B"], real_B)))
             total = total + L["loss_msssim"]
+        if self.ffl_weight:
+            L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))
+            total = total + L["loss_ffl"]
         if self.tv_weight:
             L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
             total = total + L["loss_tv"]
@@ -752,7 +769,7 @@ class TrainStep:
         # cleared every step, not only on steps without a plan: otherwise the images of other batch shapes and of evaluation calls
         # touched since the last plan-less step would be swept into the rebuilt plan and repacked on every step
         ops.clear_touched()
-        if self.phase_weight:           # the DFT tables are read on both chains' streams: built (once) before the streams fork
+        if self.phase_weight or self.ffl_weight:    # the DFT tables are read on both chains' streams: built (once) before the streams fork
             for n in sorted(set(real_A.shape[-2:]) | set(real_B.shape[-2:])):
                 ops.dft_tables(n, self.device)
         # below ~2 x 256^2 pixels per batch the step is bound by the host's enqueue rate, and the extra events / stream switches

@@ -269,6 +269,27 @@ int faoctasr_phase_loss_fwd(const float* x, const float* y, const float* tabH, c
 int faoctasr_phase_loss_bwd(const float* g, const float* tabH, const float* tabW, float radius, float* dx, float* dy,
                             float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
 
+/* ---- focal frequency loss (Jiang, Dai, Wu, Loy, ICCV 2021; not part of the reference) ----------
+ * D = fft2(x, ortho) - fft2(y, ortho) per (n, c) plane, q = |D|^2, w = phi(q) / phi(M) with phi(q) = q^(alpha/2) or, with
+ * log_matrix, log(q^(alpha/2) + 1), and M the maximum of q over the plane (batch_matrix: over the whole batch); w is a constant
+ * for the gradient and a plane (batch) with M = 0 has w = 0.  L = mean over n, c, u, v of w q.  The DFT is linear, so one
+ * transform of x - y serves both images, and sum w q = (sum phi(q) q) / phi(M) makes the forward one pass (csrc/spectral.hip).
+ * Always exact fp32; no atomics, every sum in a fixed order: bit-reproducible.  tabH, tabW: faoctasr_dft_tables of H and of W.
+ * workspace of one forward or one backward (per-plane sums, per-block partials, the row-pass buffer; free again once the call has
+ * run on its stream); -1 on a bad shape */
+long faoctasr_ffl_workspace_floats(int N, int C, int H, int W);
+/* forward for x, y[N,C,H,W] (H, W >= 2, even or odd), alpha finite and >= 0: loss[1].  Enqueues the row pass of x and y
+ * (faoctasr_sgemm_batched), the fused column pass of their difference + weight + partial sums, and a single-block finish.
+ * planes (may be NULL: no backward will follow and the spectrum is not stored): N*C*(2*H*W + 1) floats that the backward reads --
+ * Re and -Im of D per plane, then 1 / phi(M) per plane.  `workspace` must be 8-byte aligned. */
+int faoctasr_ffl_fwd(const float* x, const float* y, const float* tabH, const float* tabW, float alpha, int log_matrix,
+                     int batch_matrix, float* loss, float* planes, float* workspace, int N, int C, int H, int W,
+                     faoctasr_stream_t stream);
+/* backward: dx, dy[N,C,H,W] (either may be NULL) = g[0] * dL/d(x|y), g a device scalar, from the `planes` a forward with the same
+ * alpha and log_matrix filled.  One column pass and one row pass whichever sides are wanted; dy is the exact negation of dx. */
+int faoctasr_ffl_bwd(const float* g, const float* planes, const float* tabH, const float* tabW, float alpha, int log_matrix,
+                     float* dx, float* dy, float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
+
 /* ---- total-variation loss (model.py:17-33; train.py:98,178) ------------------------------------
  * L = weight * 2 * (S_h / count_h + S_w / count_w) / B for x[B,C,H,W] (H, W >= 2), S_h = sum (x[.,.,i+1,j] - x[.,.,i,j])^2,
  * S_w = sum (x[.,.,i,j+1] - x[.,.,i,j])^2, count_h = C (H-1) W, count_w = C H (W-1)  (csrc/tv.hip).  float4 loads when W % 4 == 0
