@@ -6,7 +6,7 @@ HIP kernels for gfx950 behind the C ABI of ``include/faoctasr.h``.
 """
 from . import _lib, ops
 from ._lib import KernelError
-from .model import (Discriminator, FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A, ResidualBlock, ResnetBlock,
+from .model import (Discriminator, FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A, ResidualBlock, ResnetBlock,
                     ResnetGenerator, TVLoss, UnetGenerator, UnetSkipConnectionBlock, phase_consistency_loss, shallowNet)
 from .evaluate import evaluate_pairs, image_metrics, super_resolve
 from . import ssim                # stays the MODULE: the reference does `import ssim; ssim.SSIM()` (train.py:24,97)

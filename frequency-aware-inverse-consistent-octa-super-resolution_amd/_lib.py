@@ -64,6 +64,9 @@ _SIG = {
     "ffl_workspace_floats": (_L, "iiii"),
     "ffl_fwd": (_I, "pppp f ii ppp iiii p"),
     "ffl_bwd": (_I, "pppp f i ppp iiii p"),
+    "mi_workspace_floats": (_L, "iiii i"),
+    "mi_fwd": (_I, "pp ppp iiii i ffff ii p"),
+    "mi_bwd": (_I, "ppp p pp iiii i fff i p"),
     "tv_loss_workspace_floats": (_L, "iiii"),
     "tv_loss_fwd": (_I, "ppp iiii f p"),
     "tv_loss_bwd": (_I, "ppp iiii f p"),

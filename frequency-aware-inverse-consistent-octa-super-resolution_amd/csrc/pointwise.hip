@@ -517,7 +517,7 @@ using namespace faoctasr;
 
 extern "C" {
 
-int faoctasr_version(void) { return 430; }      // 400: f16x2 (precision 3), absmax slots, two-pass weight-gradient reduction, fused residual; 410: spectral phase loss; 420: total-variation loss; 430: focal frequency loss
+int faoctasr_version(void) { return 440; }      // 400: f16x2 (precision 3), absmax slots, two-pass weight-gradient reduction, fused residual; 410: spectral phase loss; 420: total-variation loss; 430: focal frequency loss; 440: mutual information
 const char* faoctasr_last_error(void) { return err_buf(); }
 int faoctasr_last_route(void) { return faoctasr::get_route(); }
 

@@ -8,6 +8,8 @@ judged against it: BatchNorm2d everywhere (``norm_layer='Instance'`` is ignored,
 8 ResidualBlocks + 3 ResnetBlocks, 5-layer 4x4 PatchGAN with an image and a Haar-DWT branch,
 dead ``unet`` / ``unet_up`` / ``skip`` parameters that exist only as state_dict entries.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -68,6 +70,33 @@ class FocalFrequencyLoss(nn.Module):
 
     def extra_repr(self):
         return "loss_weight=%g, alpha=%g, log_matrix=%s, batch_matrix=%s" % (self.loss_weight, self.alpha, self.log_matrix, self.batch_matrix)
+
+
+class MutualInformationLoss(nn.Module):
+    """The differentiable mutual information of two images (not in the reference, which scores results with a hard-histogram NMI,
+    utils.py:209-212): Gaussian Parzen windows on ``bins`` centres over ``value_range``, a soft joint histogram per (n, c) plane,
+    ``MI = Ha + Hb - Hab`` or with ``normalized`` ``NMI = (Ha + Hb) / Hab``; the mean over the planes, or with ``per_image`` one
+    value per sample.  ``forward`` returns the SCORE (larger = more shared structure); a loss is ``U - score`` with ``U =
+    log(bins)`` (MI) or 2 (NMI), which is what ``TrainStep(mi_weight=...)`` adds for each fake against the image it was made from.
+    Invariant to invertible intensity maps, so it compares images of different domains.  One fused HIP path
+    (``ops.mutual_information``)."""
+
+    def __init__(self, bins=32, value_range=(-1., 1.), sigma_ratio=1.0, eps=1e-6, normalized=False, per_image=False):
+        super().__init__()
+        self.bins, self.value_range, self.sigma_ratio, self.eps = ops.check_mi_params(bins, value_range, sigma_ratio, eps)
+        self.normalized, self.per_image = bool(normalized), bool(per_image)
+
+    @property
+    def upper(self):
+        """The score of two identical images cannot exceed this: log(bins) for MI, 2 for NMI."""
+        return 2.0 if self.normalized else math.log(self.bins)
+
+    def forward(self, x, y):
+        return ops.mutual_information(x, y, self.bins, self.value_range, self.sigma_ratio, self.eps, self.normalized, self.per_image)
+
+    def extra_repr(self):
+        return "bins=%d, value_range=(%g, %g), sigma_ratio=%g, eps=%g, normalized=%s, per_image=%s" % (
+            (self.bins,) + self.value_range + (self.sigma_ratio, self.eps, self.normalized, self.per_image))
 
 
 class Discriminator(nn.Module):

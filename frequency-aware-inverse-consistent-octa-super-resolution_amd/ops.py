@@ -2373,6 +2373,85 @@ def focal_frequency_loss(x, y, alpha=1.0, log_matrix=False, batch_matrix=False):
 
 
 # ----------------------------------------------------------------------------------------
+# differentiable mutual information (Gaussian Parzen windows, soft joint histogram; csrc/mi.hip)
+# ----------------------------------------------------------------------------------------
+MI_MAX_BINS = 64
+
+
+def check_mi_params(bins, value_range, sigma_ratio, eps):
+    """``(bins, (lo, hi), sigma_ratio, eps)`` of the mutual-information op as an int and floats, or ValueError."""
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 2 <= bins <= MI_MAX_BINS:
+        raise ValueError("mutual information: bins must be an int in [2, %d], got %r" % (MI_MAX_BINS, bins))
+    try:
+        lo, hi = (float(v) for v in value_range)
+    except (TypeError, ValueError):
+        raise ValueError("mutual information: value_range must be a (lo, hi) pair, got %r" % (value_range,))
+    if not (math.isfinite(lo) and math.isfinite(hi) and hi > lo):
+        raise ValueError("mutual information: value_range must be finite with hi > lo, got %r" % ((lo, hi),))
+    sigma_ratio, eps = float(sigma_ratio), float(eps)
+    if not (math.isfinite(sigma_ratio) and sigma_ratio > 0.0):
+        raise ValueError("mutual information: sigma_ratio must be finite and > 0, got %r" % sigma_ratio)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError("mutual information: eps must be finite and > 0, got %r" % eps)
+    return bins, (lo, hi), sigma_ratio, eps
+
+
+class _MutualInformation(Function):
+    @staticmethod
+    def forward(ctx, x, y, bins, lo, hi, sigma_ratio, eps, normalized, per_image, save):
+        x, y = _c(x), _c(y)
+        N, C, H, W = x.shape
+        n = _lib.load().faoctasr_mi_workspace_floats(N, C, H, W, bins)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_mi_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = torch.empty(n, dtype=torch.float32, device=x.device)        # scratch of this call: free again behind it on the stream
+        out = torch.empty((N,) if per_image else (), dtype=torch.float32, device=x.device)
+        # dS/dP per plane (bins x bins): all a backward needs besides x and y; stored only when one can follow (``save``)
+        table = torch.empty(N * C * bins * bins, dtype=torch.float32, device=x.device) if save else None
+        call("mi_fwd", ptr(x), ptr(y), ptr(out), ptr(table), ptr(ws), N, C, H, W, bins, lo, hi, sigma_ratio, eps, int(normalized),
+             int(per_image), stream_ptr())
+        if save:
+            ctx.save_for_backward(x, y, table)
+        ctx.cfg = (bins, lo, hi, sigma_ratio, int(per_image), N, C, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, table = ctx.saved_tensors
+        bins, lo, hi, sigma_ratio, per_image, N, C, H, W = ctx.cfg
+        g = _c(g)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        call("mi_bwd", ptr(g), ptr(x), ptr(y), ptr(table), ptr(dx), ptr(dy), N, C, H, W, bins, lo, hi, sigma_ratio, per_image, stream_ptr())
+        return (dx, dy) + (None,) * 8
+
+
+def mutual_information(x, y, bins=32, value_range=(-1., 1.), sigma_ratio=1.0, eps=1e-6, normalized=False, per_image=False):
+    """The differentiable mutual information of x and y (N,C,H,W) fp32 on one GPU, with gradients to both inputs.  Per (n, c)
+    plane, with ``K = bins``, ``d = (hi - lo) / K``, centres ``c_k = lo + (k + 1/2) d`` and ``sigma = sigma_ratio * d``:
+    ``Wa[p, k] = softmax_k(-(x_p - c_k)^2 / (2 sigma^2))`` (Gaussian Parzen windows; any finite value, inside the range or not),
+    ``Wb`` likewise from y, ``P = Wa^T Wb / (H W)``, ``pa`` / ``pb`` its row / column sums, ``H(q) = -sum q log(q + eps)`` and
+    ``MI = Ha + Hb - Hab``, or with ``normalized`` ``NMI = (Ha + Hb) / Hab``.  The result is the mean over all planes as a 0-dim
+    tensor, or with ``per_image`` the ``(N,)`` means over c.  Invariant to any invertible intensity map of either image (up to the
+    binning), which makes it the structure-preservation measure between images of DIFFERENT domains.  Nothing of size pixels x
+    bins is stored (csrc/mi.hip): the weights are contracted on the exact-f32 MFMA as they are formed and recomputed in the
+    backward, which needs x, y and one K x K table per plane.  Bit-reproducible, symmetric in (x, y) bit for bit, always exact
+    fp32 (``conv_precision`` does not apply); no double backward."""
+    bins, (lo, hi), sigma_ratio, eps = check_mi_params(bins, value_range, sigma_ratio, eps)
+    if not (torch.is_tensor(x) and torch.is_tensor(y)) or x.dim() != 4 or x.shape != y.shape:
+        raise _lib.KernelError("mutual_information operands must be (N,C,H,W) tensors of one shape: %s vs %s"
+                               % (tuple(getattr(x, "shape", ())), tuple(getattr(y, "shape", ()))))
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise _lib.KernelError("mutual_information operands must be fp32, got %s and %s" % (x.dtype, y.dtype))
+    if not (x.is_cuda and y.is_cuda) or x.device != y.device:
+        raise _lib.KernelError("mutual_information runs as HIP kernels on one GPU; got devices %s and %s" % (x.device, y.device))
+    if x.numel() == 0 or x.shape[0] * x.shape[1] > 65535:
+        raise _lib.KernelError("mutual_information needs a non-empty batch of at most 65535 planes, got %s" % (tuple(x.shape),))
+    save = torch.is_grad_enabled() and (x.requires_grad or y.requires_grad)         # grad mode is off inside Function.forward
+    return _MutualInformation.apply(x, y, bins, lo, hi, sigma_ratio, eps, bool(normalized), bool(per_image), save)
+
+
+# ----------------------------------------------------------------------------------------
 # total-variation loss (model.py:17-33)
 # ----------------------------------------------------------------------------------------
 class _TVLoss(Function):

@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
-from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, NetworkA2B, NetworkB2A
+from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
 from .ssim import MSSSIM
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
@@ -266,7 +266,7 @@ class TrainStep:
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
                  msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
-                 ffl_batch_matrix=False):
+                 ffl_batch_matrix=False, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -304,7 +304,14 @@ class TrainStep:
         ``ffl_weight`` (default 0: nothing is constructed or launched): adds ``loss_ffl = ffl_weight * (L(recovered_A, real_A) +
         L(recovered_B, real_B))`` to ``loss_G``, L the focal frequency loss ``FocalFrequencyLoss(alpha=ffl_alpha,
         log_matrix=ffl_log_matrix, batch_matrix=ffl_batch_matrix)``: a squared distance between the two spectra in which every bin
-        is weighted by how wrong it currently is, where the phase term is blind to scale."""
+        is weighted by how wrong it currently is, where the phase term is blind to scale.
+
+        ``mi_weight`` (default 0: nothing is constructed or launched): adds ``loss_mi = mi_weight * ((U - S(fake_B, real_A)) +
+        (U - S(fake_A, real_B)))`` to ``loss_G``, S the mutual information ``MutualInformationLoss(bins=mi_bins,
+        sigma_ratio=mi_sigma_ratio, normalized=mi_normalized)`` and ``U = log(mi_bins)`` (with ``mi_normalized``: 2) its upper
+        bound.  Every other opt-in term compares a reconstruction with its own input or looks at a fake alone; this one ties a fake
+        to the image of the OTHER domain it was made from, where pixelwise distances do not apply.  The gradient reaches the fake
+        only."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -347,6 +354,11 @@ class TrainStep:
         self.ffl_weight = ffl_weight
         self.ffl = (FocalFrequencyLoss(alpha=ffl_alpha, log_matrix=ffl_log_matrix, batch_matrix=ffl_batch_matrix)
                     if ffl_weight else None)
+        #: opt-in mutual-information term of each fake against its source (model.MutualInformationLoss; 0 = off, no module is built)
+        if not (isinstance(mi_weight, (int, float)) and math.isfinite(mi_weight) and mi_weight >= 0):
+            raise ValueError("mi_weight must be a finite number >= 0, got %r" % (mi_weight,))
+        self.mi_weight = mi_weight
+        self.mi = MutualInformationLoss(bins=mi_bins, sigma_ratio=mi_sigma_ratio, normalized=mi_normalized) if mi_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -594,6 +606,8 @@ class TrainStep:
             extra_B = self._extension_terms(o["recovered_B"], real_B)       # opt-in SSIM / wavelet-HF terms: one half per chain
             if self.tv_weight:                  # fake_A was made on this stream: its share of the TV term joins chain B's root
                 extra_B["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_A"])
+            if self.mi_weight:                  # likewise fake_A's mutual information with the real_B it was made from
+                extra_B["loss_mi"] = self.mi_weight * (self.mi.upper - self.mi(o["fake_A"], real_B))
             for k, v in extra_B.items():
                 root = root + v
         # ---- chain A, losses and backward
@@ -606,6 +620,8 @@ class TrainStep:
             extra_A = self._extension_terms(o["recovered_A"], real_A)
             if self.tv_weight:                  # ... and fake_B's share joins chain A's, on chain A's stream
                 extra_A["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_B"])
+            if self.mi_weight:
+                extra_A["loss_mi"] = self.mi_weight * (self.mi.upper - self.mi(o["fake_B"], real_A))
             for k, v in extra_A.items():
                 chain_A = chain_A + v
             ops.wgrad_stream = side
@@ -660,7 +676,7 @@ class TrainStep:
 
     def generator_loss(self, o, real_A, real_B):
         """train.py:221-236 (+ the opt-in SSIM term of the commented line train.py:234, a wavelet-HF L1 term, the spectral phase term and
-        the total-variation term of the two fakes).  ``L["_root"]`` is
+        the total-variation term of the two fakes and the mutual information of each fake with its source).  ``L["_root"]`` is
         what remains to be back-propagated (everything, unless ``forward_generators`` already did the identity terms)."""
         w = self.w
         ones, _ = self.targets(real_A.shape[0])
@@ -708,6 +724,9 @@ class TrainStep:
         if self.tv_weight:
             L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
             total = total + L["loss_tv"]
+        if self.mi_weight:
+            L["loss_mi"] = self.mi_weight * ((self.mi.upper - self.mi(o["fake_B"], real_A)) + (self.mi.upper - self.mi(o["fake_A"], real_B)))
+            total = total + L["loss_mi"]
         L["_root"] = total
         L["loss_G"] = total if done is None else total.detach() + done
         return L

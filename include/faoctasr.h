@@ -290,6 +290,28 @@ int faoctasr_ffl_fwd(const float* x, const float* y, const float* tabH, const fl
 int faoctasr_ffl_bwd(const float* g, const float* planes, const float* tabH, const float* tabW, float alpha, int log_matrix,
                      float* dx, float* dy, float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
 
+/* ---- differentiable mutual information (Gaussian Parzen windows; not part of the reference) ----
+ * Per (n, c) plane of n_pix = H*W pixels, with K = bins, d = (hi - lo) / K, centres c_k = lo + (k + 1/2) d, sigma = sigma_ratio d:
+ * Wa[p,k] = softmax_k(-(x_p - c_k)^2 / (2 sigma^2)) (evaluated stably: any finite x, in the range or not), Wb likewise from y,
+ * P = Wa^T Wb / n_pix, pa / pb its row / column sums, H(q) = -sum q log(q + eps); the plane's score is MI = Ha + Hb - Hab or,
+ * with `normalized`, NMI = (Ha + Hb) / Hab.  out[0] = the mean over all planes, or with `per_image` out[n] = the mean over c.
+ * Nothing of size pixels x bins is stored: the weights are formed in registers / LDS, contracted on the exact-f32 MFMA and
+ * recomputed in the backward (csrc/mi.hip).  No atomics, every sum in a fixed order: bit-reproducible, and swapping x and y gives
+ * the same score and the swapped gradients bit for bit.  2 <= bins <= 64, N*C <= 65535, hi > lo, sigma_ratio > 0, eps > 0.
+ * workspace of one forward (per-plane scores in double, one K x K partial per 2048 pixels; free again once the call has run on
+ * its stream; 8-byte aligned); -1 on a bad shape */
+long faoctasr_mi_workspace_floats(int N, int C, int H, int W, int bins);
+/* forward for x, y[N,C,H,W]: out[1] or, with per_image, out[N].  table (may be NULL: no backward will follow and nothing is
+ * saved): N*C*bins*bins floats, dS/dP per plane with the 1 / (planes * n_pix * sigma^2) factor of the mean folded in (per_image:
+ * 1 / (C * n_pix * sigma^2)).  Three launches: histogram partials, per-plane entropies, means. */
+int faoctasr_mi_fwd(const float* x, const float* y, float* out, float* table, float* workspace, int N, int C, int H, int W,
+                    int bins, float lo, float hi, float sigma_ratio, float eps, int normalized, int per_image,
+                    faoctasr_stream_t stream);
+/* backward: dx, dy[N,C,H,W] (either may be NULL) = g * dS/d(x|y) from x, y and the `table` a forward with the same parameters
+ * filled; g a device scalar, or with per_image N device floats, multiplied in last.  One pass over the pixels. */
+int faoctasr_mi_bwd(const float* g, const float* x, const float* y, const float* table, float* dx, float* dy, int N, int C,
+                    int H, int W, int bins, float lo, float hi, float sigma_ratio, int per_image, faoctasr_stream_t stream);
+
 /* ---- total-variation loss (model.py:17-33; train.py:98,178) ------------------------------------
  * L = weight * 2 * (S_h / count_h + S_w / count_w) / B for x[B,C,H,W] (H, W >= 2), S_h = sum (x[.,.,i+1,j] - x[.,.,i,j])^2,
  * S_w = sum (x[.,.,i,j+1] - x[.,.,i,j])^2, count_h = C (H-1) W, count_w = C H (W-1)  (csrc/tv.hip).  float4 loads when W % 4 == 0
