@@ -3,7 +3,9 @@
 //
 // Rows r in [0,R): BatchNorm R = C (each row gathers NI images x HW); InstanceNorm R = N*C with NI = 1.  Element e of row r
 // lives at ((e / HW) * R + r) * HW + e % HW.  Statistics are accumulated around a per-row shift (the row's first element) to
-// avoid the E[x^2]-E[x]^2 cancellation; partials are combined in a fixed order (deterministic).
+// avoid the E[x^2]-E[x]^2 cancellation; partials are combined in a fixed order (deterministic).  The output x * g + b with
+// g = gamma * invstd, b = beta - mean * g cancels as well when |mean| >> std: the forward carries what the roundings of mean
+// and of b lose (offset_tail) and adds it after the cancellation -- without it y is off by 3.5e-4 at mean 100, std 0.01.
 //
 // Three forms, chosen per call:
 //   * streaming (HW % 4 == 0): two kernels per direction (statistics / reduce, then apply / dx).  A block walks a contiguous
@@ -23,6 +25,7 @@ constexpr int BN_MAX_SPLIT = 64;
 
 struct RowStats {
     float mean, invstd, var;
+    float mean_lo;      // shift + dm = mean + mean_lo exactly
 };
 
 // ---- helpers ---------------------------------------------------------------------------------------------------------------
@@ -54,16 +57,29 @@ __device__ __forceinline__ float4 act_mask4(const float4& g, const float4& yv, i
     return make_float4(g.x * act_grad_from_out(yv.x, act, slope), g.y * act_grad_from_out(yv.y, act, slope),
                        g.z * act_grad_from_out(yv.z, act, slope), g.w * act_grad_from_out(yv.w, act, slope));
 }
-// the forward's pre-activation, with the forward's own expression (x * gsc + bsh): only its sign is used
+// the forward's pre-activation before its offset_tail, with the forward's own expression (x * gsc + bsh): only its sign is used
 __device__ __forceinline__ float4 pre4(const float4& xv, float gsc, float bsh) {
     return make_float4(xv.x * gsc + bsh, xv.y * gsc + bsh, xv.z * gsc + bsh, xv.w * gsc + bsh);
 }
+
+// beta - (mean + mean_lo) * gsc = bsh + offset_tail, bsh the rounded offset the kernels use: mean * gsc = p + ep and
+// beta - p = t + et exactly (product and sum with their rounding errors), the rest is small.  No contraction in here: a fused
+// beta - mean * gsc is not the t whose error et is
+__device__ __forceinline__ float offset_tail(float beta, float mean, float mean_lo, float gsc, float bsh) {
+#pragma clang fp contract(off)
+    const float p = mean * gsc, ep = fmaf(mean, gsc, -p);
+    const float t = beta - p, u = t - beta, et = (beta - (t - u)) + (-p - u);
+    return ((t - bsh) + (et - ep)) - mean_lo * gsc;
+}
+__device__ __forceinline__ void add4(float4& o, float v) { o.x += v; o.y += v; o.z += v; o.w += v; }
 
 __device__ __forceinline__ RowStats finish_stats(float a, float q, float shift, long L, float eps) {
     const float invL = 1.0f / (float)L;
     const float dm = a * invL;
     RowStats s;
     s.mean = shift + dm;
+    const float t = s.mean - shift;
+    s.mean_lo = (shift - (s.mean - t)) + (dm - t);
     float var = q * invL - dm * dm;
     s.var = var > 0.f ? var : 0.f;
     s.invstd = 1.0f / sqrtf(s.var + eps);
@@ -143,7 +159,9 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
     if (blockIdx.x == 0 && threadIdx.x == 0) publish_stats(st, r, L, save_mean, save_invstd, rmean, rvar, momentum);
     const int cg = r % Cg;
     const float gsc = (gamma ? gamma[cg] : 1.f) * st.invstd;
-    const float bsh = (beta ? beta[cg] : 0.f) - st.mean * gsc;
+    const float bt = beta ? beta[cg] : 0.f;
+    const float bsh = fmaf(-st.mean, gsc, bt);      // fused, as the backward's contracted beta - mean * gsc
+    const float tail = offset_tail(bt, st.mean, st.mean_lo, gsc, bsh);
     long e0 = (long)blockIdx.x * per, e1 = e0 + per;
     e1 = e1 < L ? e1 : L;
     for_row_pieces(R, HW, r, e0, e1, [&](long base, long lo, long hi) {
@@ -160,6 +178,7 @@ __global__ __launch_bounds__(256) void norm_apply_kernel(const float* __restrict
             for (int u = 0; u < NU; ++u) {
                 if (i + 1024L * u >= hi) continue;
                 float4 o = pre4(v[u], gsc, bsh);
+                add4(o, tail);
                 o.x += rr[u].x; o.y += rr[u].y; o.z += rr[u].z; o.w += rr[u].w;
                 o.x = act_apply(o.x, act, slope); o.y = act_apply(o.y, act, slope);
                 o.z = act_apply(o.z, act, slope); o.w = act_apply(o.w, act, slope);
@@ -338,12 +357,15 @@ __global__ __launch_bounds__(256) void norm_fwd_small_kernel(const float* __rest
     if (threadIdx.x == 0) publish_stats(st, r, L, save_mean, save_invstd, rmean, rvar, momentum);
     const int cg = r % Cg;
     const float gsc = (gamma ? gamma[cg] : 1.f) * st.invstd;
-    const float bsh = (beta ? beta[cg] : 0.f) - st.mean * gsc;
+    const float bt = beta ? beta[cg] : 0.f;
+    const float bsh = fmaf(-st.mean, gsc, bt);      // fused, as the backward's contracted beta - mean * gsc
+    const float tail = offset_tail(bt, st.mean, st.mean_lo, gsc, bsh);
     float mx = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         if (!ok[k]) continue;
         float4 o = pre4(v[k], gsc, bsh);
+        add4(o, tail);
         if (res) { o.x += rr[k].x; o.y += rr[k].y; o.z += rr[k].z; o.w += rr[k].w; }
         o.x = act_apply(o.x, act, slope); o.y = act_apply(o.y, act, slope);
         o.z = act_apply(o.z, act, slope); o.w = act_apply(o.w, act, slope);
@@ -457,13 +479,15 @@ __global__ __launch_bounds__(256) void norm_apply_generic_kernel(const float* __
     if (blockIdx.x == 0 && threadIdx.x == 0) publish_stats(st, r, L, save_mean, save_invstd, rmean, rvar, momentum);
     const int cg = r % Cg;
     const float gsc = (gamma ? gamma[cg] : 1.f) * st.invstd;
-    const float bsh = (beta ? beta[cg] : 0.f) - st.mean * gsc;
+    const float bt = beta ? beta[cg] : 0.f;
+    const float bsh = fmaf(-st.mean, gsc, bt);      // fused, as the backward's contracted beta - mean * gsc
+    const float tail = offset_tail(bt, st.mean, st.mean_lo, gsc, bsh);
     long e0 = (long)blockIdx.x * per, e1 = e0 + per;
     e1 = e1 < L ? e1 : L;
     for (long e = e0 + threadIdx.x; e < e1; e += 256) {
         const long n = e / HW;
         const long off = ((long)n * R + r) * HW + (e - n * HW);
-        float v = x[off] * gsc + bsh;
+        float v = (x[off] * gsc + bsh) + tail;
         if (res) v += res[off];
         y[off] = act_apply(v, act, slope);
     }
