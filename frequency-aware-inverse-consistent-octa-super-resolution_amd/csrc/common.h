@@ -49,19 +49,72 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act, float slope
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
-// block-wide sum for 256-thread blocks; result valid in every thread
-__device__ __forceinline__ float block_sum_256(float v, float* red /* >= 4 floats */) {
+// block-wide sum for 256-thread blocks (float or double); result valid in every thread
+template <class T>
+__device__ __forceinline__ T block_sum_256(T v, T* red /* >= 4 values */) {
     v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
+}
+
+// a block's partial sum: per-thread sum -> 64-lane butterfly -> the four waves, in that order; thread 0 stores
+__device__ __forceinline__ void block_partial_store_256(float v, float* red /* >= 4 floats */, float* part) {
+    v = block_sum_256(v, red);                                          // ((red[0] + red[1]) + red[2]) + red[3]
+    if (threadIdx.x == 0) part[blockIdx.x] = v;
+}
+
+// the single-block finish of those partials, in double: thread t adds p[t], p[t + 256], ... in index order ...
+template <class T>
+__device__ __forceinline__ double strided_sum_256(const T* __restrict__ p, long n) {
+    double a = 0.0;
+    for (long i = threadIdx.x; i < n; i += 256) a += (double)p[i];
+    return a;
+}
+
+// ... and a fixed tree adds the 256 threads' values (red[t] += red[t + o], o = 128 .. 1).  Returns red[0] to every thread; the
+// barrier after it lets a loop reuse red
+__device__ __forceinline__ double block_tree_256(double v, double* red /* 256 doubles */) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+
+// blockIdx.x = (plane * tiles_h + tile row) * tiles_w + tile column of TY x TX tiles: no 65535-plane limit, and a plane's
+// (an image's) blocks are contiguous
+struct PlaneTile { int plane, y0, x0; };
+template <int TY, int TX>
+__device__ __forceinline__ PlaneTile plane_tile(int tiles_h, int tiles_w) {
+    unsigned bi = blockIdx.x;
+    PlaneTile t;
+    t.x0 = (int)(bi % (unsigned)tiles_w) * TX; bi /= (unsigned)tiles_w;
+    t.y0 = (int)(bi % (unsigned)tiles_h) * TY;
+    t.plane = (int)(bi / (unsigned)tiles_h);
+    return t;
+}
+
+// the grid of that decode for `planes` planes of h x w; false when it passes 2^31 - 1 blocks
+inline bool plane_tiles(long planes, int h, int w, int TY, int TX, int* tiles_h, int* tiles_w, long* blocks) {
+    *tiles_h = (h + TY - 1) / TY;
+    *tiles_w = (w + TX - 1) / TX;
+    const long per_plane = (long)*tiles_h * *tiles_w;
+    if (planes > 0x7fffffffL / per_plane) return false;
+    *blocks = planes * per_plane;
+    return true;
 }
 
 }  // namespace faoctasr

@@ -68,17 +68,6 @@ __device__ __forceinline__ void cw_box(float (*in)[CW_PR][CW_PC], float (*mid)[C
     }
 }
 
-struct CwTile { long plane; int i0, j0; };
-
-__device__ __forceinline__ CwTile cw_tile(int tiles_h, int tiles_w) {
-    long bi = blockIdx.x;
-    CwTile t;
-    t.j0 = (int)(bi % tiles_w) * CW_TW; bi /= tiles_w;
-    t.i0 = (int)(bi % tiles_h) * CW_TH;
-    t.plane = bi / tiles_h;
-    return t;
-}
-
 __global__ __launch_bounds__(256) void cwssim_index_kernel(const float2* __restrict__ cx, const float2* __restrict__ cy,
                                                            float2* __restrict__ map_a, float* __restrict__ map_b, float* __restrict__ part,
                                                            int h, int w, int win, float K, int tiles_h, int tiles_w) {
@@ -86,15 +75,16 @@ __global__ __launch_bounds__(256) void cwssim_index_kernel(const float2* __restr
     __shared__ float mid[4][CW_PR][CW_TW];
     __shared__ float red[4];
     const int tid = threadIdx.x;
-    const CwTile t = cw_tile(tiles_h, tiles_w);
+    const PlaneTile t = plane_tile<CW_TH, CW_TW>(tiles_h, tiles_w);
+    const long plane = t.plane;
     const int ph = h - win + 1, pw = w - win + 1;
     const int rows = CW_TH + win - 1, cols = CW_TW + win - 1;
-    const float2* px = cx + t.plane * h * (long)w;
-    const float2* py = cy + t.plane * h * (long)w;
+    const float2* px = cx + plane * h * (long)w;
+    const float2* py = cy + plane * h * (long)w;
     for (int r = tid >> 6; r < rows; r += 4) {
-        const int gi = t.i0 + r;
+        const int gi = t.y0 + r;
         for (int c = tid & 63; c < cols; c += 64) {
-            const int gj = t.j0 + c;
+            const int gj = t.x0 + c;
             float2 a = make_float2(0.f, 0.f), b = a;
             if (gi < h && gj < w) {
                 a = px[(long)gi * w + gj];
@@ -111,10 +101,10 @@ __global__ __launch_bounds__(256) void cwssim_index_kernel(const float2* __restr
     cw_box<4>(in, mid, win, v);
 
     float acc = 0.f;
-    const int pj = t.j0 + (tid & 63);
+    const int pj = t.x0 + (tid & 63);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int pi = t.i0 + 4 * (tid >> 6) + i;
+        const int pi = t.y0 + 4 * (tid >> 6) + i;
         if (pi < ph && pj < pw) {
             const float zr = v[0][i], zi = v[1][i];
             const float m = zi == 0.f ? fabsf(zr) : sqrtf(zr * zr + zi * zi);     // a real z: no rounding, no underflow
@@ -123,18 +113,13 @@ __global__ __launch_bounds__(256) void cwssim_index_kernel(const float2* __restr
             acc += S;
             if (map_a) {
                 const float a = 2.f / d;
-                const long at = (t.plane * ph + pi) * (long)pw + pj;
+                const long at = (plane * ph + pi) * (long)pw + pj;
                 map_a[at] = m > 0.f ? make_float2(a * (zr / m), a * (zi / m)) : make_float2(0.f, 0.f);
                 map_b[at] = (2.f * S) / d;
             }
         }
     }
-    // per-thread sum -> 64-lane butterfly -> the four waves, in that order; thread 0 stores
-    acc = wave_sum(acc);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    block_partial_store_256(acc, red, part);
 }
 
 __global__ __launch_bounds__(256) void cwssim_grad_kernel(const float2* __restrict__ cx, const float2* __restrict__ cy,
@@ -145,15 +130,16 @@ __global__ __launch_bounds__(256) void cwssim_grad_kernel(const float2* __restri
     __shared__ float in[3][CW_PR][CW_PC];
     __shared__ float mid[3][CW_PR][CW_TW];
     const int tid = threadIdx.x;
-    const CwTile t = cw_tile(tiles_h, tiles_w);
+    const PlaneTile t = plane_tile<CW_TH, CW_TW>(tiles_h, tiles_w);
+    const long plane = t.plane;
     const int ph = h - win + 1, pw = w - win + 1;
     const int rows = CW_TH + win - 1, cols = CW_TW + win - 1;
-    const float2* pa = map_a + t.plane * ph * (long)pw;
-    const float* pb = map_b + t.plane * ph * (long)pw;
+    const float2* pa = map_a + plane * ph * (long)pw;
+    const float* pb = map_b + plane * ph * (long)pw;
     for (int r = tid >> 6; r < rows; r += 4) {
-        const int pi = t.i0 - (win - 1) + r;                              // the windows p = q - win + 1 .. q contain q
+        const int pi = t.y0 - (win - 1) + r;                              // the windows p = q - win + 1 .. q contain q
         for (int c = tid & 63; c < cols; c += 64) {
-            const int pj = t.j0 - (win - 1) + c;
+            const int pj = t.x0 - (win - 1) + c;
             float2 a = make_float2(0.f, 0.f);
             float b = 0.f;
             if (pi >= 0 && pi < ph && pj >= 0 && pj < pw) {
@@ -168,13 +154,13 @@ __global__ __launch_bounds__(256) void cwssim_grad_kernel(const float2* __restri
     float v[3][4];
     cw_box<3>(in, mid, win, v);
 
-    const float s = (float)((double)gscale[t.plane / planes_per_image] / count);
-    const int qj = t.j0 + (tid & 63);
+    const float s = (float)((double)gscale[plane / planes_per_image] / count);
+    const int qj = t.x0 + (tid & 63);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int qi = t.i0 + 4 * (tid >> 6) + i;
+        const int qi = t.y0 + 4 * (tid >> 6) + i;
         if (qi < h && qj < w) {
-            const long at = (t.plane * h + qi) * (long)w + qj;
+            const long at = (plane * h + qi) * (long)w + qj;
             const float2 x = cx[at], y = cy[at];
             const float B = v[2][i];
             if (gx) {
@@ -196,20 +182,12 @@ __global__ __launch_bounds__(256) void cwssim_final_kernel(const float* __restri
     __shared__ double red[256];
     double total = 0.0;
     for (long n = 0; n < N; ++n) {
-        double a = 0.0;
-        for (long i = threadIdx.x; i < per_image; i += 256) a += (double)part[n * per_image + i];
-        red[threadIdx.x] = a;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
+        const double s = block_tree_256(strided_sum_256(part + n * per_image, per_image), red);
         if (threadIdx.x == 0) {
-            const double m = red[0] / count;
+            const double m = s / count;
             out_image[n] = (float)m;
             total += m;
         }
-        __syncthreads();
     }
     if (threadIdx.x == 0) out_mean[0] = (float)(total / (double)N);
 }
@@ -220,12 +198,8 @@ static int cw_shape(const char* what, long planes, int h, int w, int win, int ov
     if (planes < 1) return fail(FAOCTASR_EINVAL, "%s: %ld planes", what, planes);
     if (h < win || w < win) return fail(FAOCTASR_EINVAL, "%s: a %d x %d band holds no %d x %d window", what, h, w, win, win);
     const int rh = over_positions ? h - win + 1 : h, rw = over_positions ? w - win + 1 : w;
-    *tiles_h = (rh + CW_TH - 1) / CW_TH;
-    *tiles_w = (rw + CW_TW - 1) / CW_TW;
-    const long per_plane = (long)*tiles_h * *tiles_w;
-    if (planes > 0x7fffffffL / per_plane) return fail(FAOCTASR_EINVAL, "%s: %ld planes of %ld tiles exceed the grid", what, planes, per_plane);
-    *blocks = planes * per_plane;
-    return FAOCTASR_OK;
+    if (plane_tiles(planes, rh, rw, CW_TH, CW_TW, tiles_h, tiles_w, blocks)) return FAOCTASR_OK;
+    return fail(FAOCTASR_EINVAL, "%s: %ld planes of %ld tiles exceed the grid", what, planes, (long)*tiles_h * *tiles_w);
 }
 
 static int cw_images(const char* what, long N, long planes) {

@@ -37,15 +37,6 @@ __device__ __forceinline__ float dl_term(float2 zx, float2 zy, float b2, float s
     return fabsf(d);
 }
 
-// per-thread sum -> 64-lane butterfly -> the four waves, in that order; thread 0 stores
-__device__ __forceinline__ void dl_block_store(float v, float* red, float* part) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // level 1: x, y [H, W] even -> ll of each [H, W] (optional), cotangent bands [H/2, W/2] (optional), one partial per block
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -98,7 +89,7 @@ __global__ __launch_bounds__(256) void dtcwt_loss_fwd_j1(const float* __restrict
             acc += dl_term(zx[o], z[o], b2, scale, gx ? gx + e : nullptr, gy ? gy + e : nullptr);
         }
     }
-    dl_block_store(acc, red, part);
+    block_partial_store_256(acc, red, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -159,7 +150,7 @@ __global__ __launch_bounds__(256) void dtcwt_loss_fwd_j2(const float* __restrict
             acc += dl_term(zx[k], z[k], b2, scale, gx ? gx + e : nullptr, gy ? gy + e : nullptr);
         }
     }
-    dl_block_store(acc, red, part);
+    block_partial_store_256(acc, red, part);
 }
 
 // the levels' partials lie one after the other in `part`.  Per level: thread t adds partials t, t + 256, ... in double, a fixed
@@ -169,16 +160,8 @@ __global__ __launch_bounds__(256) void dtcwt_loss_final_kernel(const float* __re
     double total = 0.0;
     long off = 0;
     for (int j = 0; j < levels; ++j) {
-        double a = 0.0;
-        for (long i = threadIdx.x; i < lv.n[j]; i += 256) a += (double)part[off + i];
-        red[threadIdx.x] = a;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) total += red[0] * lv.s[j];
-        __syncthreads();
+        const double s = block_tree_256(strided_sum_256(part + off, lv.n[j]), red);
+        if (threadIdx.x == 0) total += s * lv.s[j];
         off += lv.n[j];
     }
     if (threadIdx.x == 0) out[0] = (float)total;

@@ -26,63 +26,33 @@
 // taps: the reference defines its backward passes that way (they are the adjoint only for zero padding, and for periodization
 // at even sizes).
 #include <cstdint>
-#include "common.h"
+#include "filterbank_dev.h"
 
 namespace faoctasr {
 
-constexpr int DWT_MAXL = 16;
-constexpr int MODE_ZERO = 0, MODE_SYMMETRIC = 1, MODE_PER = 2, MODE_REFLECT = 4, MODE_PERIODIC = 6;
-
-struct DwtTaps {
-    float w0[DWT_MAXL], w1[DWT_MAXL], h0[DWT_MAXL], h1[DWT_MAXL];
-};
-
 constexpr int DA_TH = 16, DA_TW = 32;                       // analysis: output tile
-constexpr int DA_PR = 2 * DA_TH + DWT_MAXL - 2;             // patch rows
-constexpr int DA_PC = 2 * DA_TW + DWT_MAXL - 2;             // patch columns (even: the W pass reads aligned float2)
+constexpr int DA_PR = 2 * DA_TH + FB_MAXL - 2;             // patch rows
+constexpr int DA_PC = 2 * DA_TW + FB_MAXL - 2;             // patch columns (even: the W pass reads aligned float2)
 constexpr int DS_TH = 32, DS_TW = 64;                       // synthesis: output tile
-constexpr int DS_PR = DS_TH / 2 + DWT_MAXL / 2;             // coefficient patch rows
-constexpr int DS_PC = DS_TW / 2 + DWT_MAXL / 2;             // coefficient patch columns
-
-__device__ __forceinline__ int pmod(int j, int P) {
-    const int m = j % P;
-    return m < 0 ? m + P : m;
-}
-
-// index of the sample that position j of the extended signal reads, -1 for a zero
-__device__ __forceinline__ int dwt_map(int j, int N, int mode, int L2) {
-    switch (mode) {
-        case MODE_SYMMETRIC: { const int m = pmod(j, 2 * N); return m < N ? m : 2 * N - 1 - m; }          // fold about -1/2 and N-1/2
-        case MODE_REFLECT: { if (N == 1) return 0; const int m = pmod(j, 2 * N - 2); return m < N ? m : 2 * N - 2 - m; }   // about 0 and N-1
-        case MODE_PERIODIC: return pmod(j, N);
-        case MODE_PER: {
-            const int Ne = N + (N & 1);
-            if (j < -Ne || j >= Ne) return -1;
-            const int m = ((j < 0 ? j + Ne : j) + L2) % Ne;
-            return m < N ? m : N - 1;
-        }
-        default: return (j >= 0 && j < N) ? j : -1;
-    }
-}
+constexpr int DS_PR = DS_TH / 2 + FB_MAXL / 2;             // coefficient patch rows
+constexpr int DS_PC = DS_TW / 2 + FB_MAXL / 2;             // coefficient patch columns
 
 __global__ __launch_bounds__(256) void dwt_analysis_kernel(const float* __restrict__ x, float* __restrict__ ll, float* __restrict__ hi,
                                                            int H, int W, int OH, int OW, int tiles_h, int tiles_w, int Lh, int Lw,
-                                                           int base_h, int base_w, int mode, DwtTaps taps) {
+                                                           int base_h, int base_w, int mode, FbTaps2 taps) {
     __shared__ __attribute__((aligned(16))) float patch[DA_PR][DA_PC];
     __shared__ float mid_lo[DA_PR][DA_TW], mid_hi[DA_PR][DA_TW];
     const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w; b /= tiles_w;
-    const int th = b % tiles_h;
-    const long plane = b / tiles_h;
-    const int oi0 = th * DA_TH, oj0 = tw * DA_TW;
+    const PlaneTile t = plane_tile<DA_TH, DA_TW>(tiles_h, tiles_w);
+    const long plane = t.plane;
+    const int oi0 = t.y0, oj0 = t.x0;
     const int rows = 2 * DA_TH + Lh - 2, cols = 2 * DA_TW + Lw - 2;      // <= DA_PR, DA_PC
     const float* xp = x + plane * H * (long)W;
 
     for (int r = tid >> 6; r < rows; r += 4) {
-        const int sr = dwt_map(2 * oi0 - base_h + r, H, mode, Lh >> 1);
+        const int sr = fb_map(2 * oi0 - base_h + r, H, mode, Lh >> 1);
         for (int c = tid & 63; c < cols; c += 64) {
-            const int sc = dwt_map(2 * oj0 - base_w + c, W, mode, Lw >> 1);
+            const int sc = fb_map(2 * oj0 - base_w + c, W, mode, Lw >> 1);
             patch[r][c] = (sr >= 0 && sc >= 0) ? xp[(long)sr * W + sc] : 0.f;
         }
     }
@@ -94,10 +64,10 @@ __global__ __launch_bounds__(256) void dwt_analysis_kernel(const float* __restri
             float lo = 0.f, hv = 0.f;
             for (int k = 0; k < Lw; k += 2) {
                 const float2 v = *reinterpret_cast<const float2*>(&patch[r][2 * c + k]);
-                lo = fmaf(taps.w0[k], v.x, lo);
-                hv = fmaf(taps.w1[k], v.x, hv);
-                lo = fmaf(taps.w0[k + 1], v.y, lo);
-                hv = fmaf(taps.w1[k + 1], v.y, hv);
+                lo = fmaf(taps.w.f0[k], v.x, lo);
+                hv = fmaf(taps.w.f1[k], v.x, hv);
+                lo = fmaf(taps.w.f0[k + 1], v.y, lo);
+                hv = fmaf(taps.w.f1[k + 1], v.y, hv);
             }
             mid_lo[r][c] = lo;
             mid_hi[r][c] = hv;
@@ -116,10 +86,10 @@ __global__ __launch_bounds__(256) void dwt_analysis_kernel(const float* __restri
             float a = 0.f, bb = 0.f, cc = 0.f, d = 0.f;
             for (int k = 0; k < Lh; ++k) {
                 const float vl = mid_lo[2 * i + k][c], vh = mid_hi[2 * i + k][c];
-                a = fmaf(taps.h0[k], vl, a);
-                bb = fmaf(taps.h1[k], vl, bb);
-                cc = fmaf(taps.h0[k], vh, cc);
-                d = fmaf(taps.h1[k], vh, d);
+                a = fmaf(taps.h.f0[k], vl, a);
+                bb = fmaf(taps.h.f1[k], vl, bb);
+                cc = fmaf(taps.h.f0[k], vh, cc);
+                d = fmaf(taps.h.f1[k], vh, d);
             }
             if (oi < OH && oj < OW) {
                 const long o = (long)oi * OW + oj;
@@ -134,15 +104,13 @@ __global__ __launch_bounds__(256) void dwt_analysis_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void dwt_synthesis_kernel(const float* __restrict__ ll, const float* __restrict__ hi, float* __restrict__ y,
                                                             int nh, int nw, int out_h, int out_w, int tiles_h, int tiles_w, int Lh,
-                                                            int Lw, int per, DwtTaps taps) {
+                                                            int Lw, int per, FbTaps2 taps) {
     __shared__ float cf[4][DS_PR][DS_PC];
     __shared__ float mid_lo[DS_TH][DS_PC], mid_hi[DS_TH][DS_PC];
     const int tid = threadIdx.x;
-    int b = blockIdx.x;
-    const int tw = b % tiles_w; b /= tiles_w;
-    const int th = b % tiles_h;
-    const long plane = b / tiles_h;
-    const int t0 = th * DS_TH, s0 = tw * DS_TW;
+    const PlaneTile tile = plane_tile<DS_TH, DS_TW>(tiles_h, tiles_w);
+    const long plane = tile.plane;
+    const int t0 = tile.y0, s0 = tile.x0;
     const int off_h = per ? (Lh >> 1) - 1 : Lh - 2, off_w = per ? (Lw >> 1) - 1 : Lw - 2;
     const int ib = (t0 + off_h - Lh + 2) >> 1, jb = (s0 + off_w - Lw + 2) >> 1;     // first virtual coefficient row / column (floor)
     const int prow = DS_TH / 2 + (Lh >> 1), pcol = DS_TW / 2 + (Lw >> 1);
@@ -162,7 +130,8 @@ __global__ __launch_bounds__(256) void dwt_synthesis_kernel(const float* __restr
     }
     __syncthreads();
 
-    // H pass: (ll, lh) -> mid_lo, (hl, hh) -> mid_hi, for every row of the tile and every patch column
+    // H pass: (ll, lh) -> mid_lo, (hl, hh) -> mid_hi, for every row of the tile and every patch column: fb_syn_out's loop, written
+    // out for two outputs that share the taps and the index (two calls cost four VGPRs)
     for (int e = tid; e < DS_TH * pcol; e += 256) {
         const int tt = e / pcol, c = e - tt * pcol;
         const int u = t0 + tt + off_h;
@@ -172,7 +141,7 @@ __global__ __launch_bounds__(256) void dwt_synthesis_kernel(const float* __restr
         for (int q = 0; q < (Lh >> 1); ++q) {
             const int i = (u >> 1) - q;
             if (i < lo_i || i >= hi_i) continue;
-            const float g0 = odd ? taps.h0[2 * q + 1] : taps.h0[2 * q], g1 = odd ? taps.h1[2 * q + 1] : taps.h1[2 * q];
+            const float g0 = odd ? taps.h.f0[2 * q + 1] : taps.h.f0[2 * q], g1 = odd ? taps.h.f1[2 * q + 1] : taps.h.f1[2 * q];
             const int r = i - ib;
             a0 = fmaf(cf[0][r][c], g0, a0);
             a1 = fmaf(cf[1][r][c], g1, a1);
@@ -189,18 +158,7 @@ __global__ __launch_bounds__(256) void dwt_synthesis_kernel(const float* __restr
         const int tt = e / DS_TW, ss = e - tt * DS_TW;
         const int t = t0 + tt, s = s0 + ss;
         if (t >= out_h || s >= out_w) continue;
-        const int v = s + off_w;
-        const int lo_j = (per && v < 2 * nw) ? -nw : 0, hi_j = (per && v >= 2 * nw) ? 2 * nw : nw;
-        const bool odd = v & 1;
-        float a0 = 0.f, a1 = 0.f;
-        for (int q = 0; q < (Lw >> 1); ++q) {
-            const int j = (v >> 1) - q;
-            if (j < lo_j || j >= hi_j) continue;
-            const float g0 = odd ? taps.w0[2 * q + 1] : taps.w0[2 * q], g1 = odd ? taps.w1[2 * q + 1] : taps.w1[2 * q];
-            a0 = fmaf(mid_lo[tt][j - jb], g0, a0);
-            a1 = fmaf(mid_hi[tt][j - jb], g1, a1);
-        }
-        yp[(long)t * out_w + s] = a0 + a1;
+        yp[(long)t * out_w + s] = fb_syn_out(mid_lo[tt], mid_hi[tt], jb, nw, s + off_w, per, Lw, taps.w);
     }
 }
 
@@ -209,19 +167,9 @@ static int mode_ok(int mode) {
 }
 
 static int dwt_check(const char* what, long NC, int L_h, int L_w, int mode, const float* a, const float* b, const float* c, const float* d) {
-    if (!a || !b || !c || !d) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
-    if (NC < 1) return fail(FAOCTASR_EINVAL, "%s: NC %ld", what, NC);
-    if (L_h < 2 || L_h > DWT_MAXL || (L_h & 1) || L_w < 2 || L_w > DWT_MAXL || (L_w & 1))
-        return fail(FAOCTASR_EINVAL, "%s: tap counts L_h %d L_w %d must be even and within 2..%d", what, L_h, L_w, DWT_MAXL);
+    if (int rc = fb_check2(what, NC, L_h, L_w, a, b, c, d)) return rc;
     if (!mode_ok(mode)) return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d (0 zero, 1 symmetric, 2 periodization, 4 reflect, 6 periodic)", what, mode);
     return FAOCTASR_OK;
-}
-
-static DwtTaps dwt_taps(const float* lo_h, const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w) {
-    DwtTaps t = {};
-    for (int k = 0; k < L_h; ++k) { t.h0[k] = lo_h[k]; t.h1[k] = hi_h[k]; }
-    for (int k = 0; k < L_w; ++k) { t.w0[k] = lo_w[k]; t.w1[k] = hi_w[k]; }
-    return t;
 }
 
 }  // namespace faoctasr
@@ -240,13 +188,13 @@ extern "C" int faoctasr_dwt2d_analysis(const float* x, float* ll, float* hi, lon
     if (H < L_h / 2 + 1 || W < L_w / 2 + 1)
         return fail(FAOCTASR_EINVAL, "dwt2d_analysis: H %d W %d below the minimum side L/2 + 1 (L_h %d, L_w %d)", H, W, L_h, L_w);
     const int OH = dwt_out_size(H, L_h, mode), OW = dwt_out_size(W, L_w, mode);
-    const int tiles_h = (OH + DA_TH - 1) / DA_TH, tiles_w = (OW + DA_TW - 1) / DA_TW;
-    const long blocks = NC * tiles_h * (long)tiles_w;
-    if (blocks > 0x7fffffffL) return fail(FAOCTASR_EUNSUPPORTED, "dwt2d_analysis: NC %ld H %d W %d needs more than 2^31 - 1 blocks", NC, H, W);
+    int tiles_h, tiles_w;
+    long blocks;
+    if (!plane_tiles(NC, OH, OW, DA_TH, DA_TW, &tiles_h, &tiles_w, &blocks)) return fail(FAOCTASR_EUNSUPPORTED, "dwt2d_analysis: NC %ld H %d W %d needs more than 2^31 - 1 blocks", NC, H, W);
     const int base_h = mode == MODE_PER ? L_h - 1 : (2 * (OH - 1) - H + L_h) / 2;
     const int base_w = mode == MODE_PER ? L_w - 1 : (2 * (OW - 1) - W + L_w) / 2;
     hipLaunchKernelGGL(dwt_analysis_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, ll, hi, H, W, OH, OW, tiles_h,
-                       tiles_w, L_h, L_w, base_h, base_w, mode, dwt_taps(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
+                       tiles_w, L_h, L_w, base_h, base_w, mode, fb_taps2(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
     return check_launch("dwt2d_analysis");
 }
 
@@ -263,10 +211,10 @@ extern "C" int faoctasr_dwt2d_synthesis(const float* ll, const float* hi, float*
     const int full_h = per ? 2 * nh : 2 * nh - L_h + 2, full_w = per ? 2 * nw : 2 * nw - L_w + 2;
     if (out_h < 1 || out_w < 1 || out_h > full_h || out_w > full_w)
         return fail(FAOCTASR_EINVAL, "dwt2d_synthesis: crop %d x %d outside the %d x %d result", out_h, out_w, full_h, full_w);
-    const int tiles_h = (out_h + DS_TH - 1) / DS_TH, tiles_w = (out_w + DS_TW - 1) / DS_TW;
-    const long blocks = NC * tiles_h * (long)tiles_w;
-    if (blocks > 0x7fffffffL) return fail(FAOCTASR_EUNSUPPORTED, "dwt2d_synthesis: NC %ld, %d x %d needs more than 2^31 - 1 blocks", NC, out_h, out_w);
+    int tiles_h, tiles_w;
+    long blocks;
+    if (!plane_tiles(NC, out_h, out_w, DS_TH, DS_TW, &tiles_h, &tiles_w, &blocks)) return fail(FAOCTASR_EUNSUPPORTED, "dwt2d_synthesis: NC %ld, %d x %d needs more than 2^31 - 1 blocks", NC, out_h, out_w);
     hipLaunchKernelGGL(dwt_synthesis_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ll, hi, y, nh, nw, out_h, out_w,
-                       tiles_h, tiles_w, L_h, L_w, per, dwt_taps(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
+                       tiles_h, tiles_w, L_h, L_w, per, fb_taps2(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
     return check_launch("dwt2d_synthesis");
 }

@@ -18,8 +18,9 @@
 // for u' = t + L/2 - 1 < 2n and in [0, 2n) beyond; the other modes use i' in [0, n) and u' = t + L - 2.  Levels run from the
 // coarsest to the finest; level j's result is cropped to the next level's coefficient count, the finest to out_len.
 //
-// dwt1d_map (the extension's index map), dwt1d_ana_out and dwt1d_syn_out (one output: explicit fmaf, taps k = 0 .. L-1 in
-// order) are shared by every launch shape, so a coefficient has the same bits whatever block, tile or launch computed it.
+// fb_map (the extension's index map) and fb_syn_out of filterbank_dev.h, shared with dwt.hip, and dwt1d_ana_out (one output:
+// explicit fmaf, taps k = 0 .. L-1 in order) serve every launch shape, so a coefficient has the same bits whatever block, tile
+// or launch computed it.
 //
 // Launch shapes.  FUSED: a workgroup of 256 threads owns R rows (R = 1 for a long row, a power of two up to 16 for short
 // ones, 256 / R lanes per row) and runs level after level between two LDS buffers: E, the level's extended input (the index
@@ -49,46 +50,22 @@
 // coefficient (a broadcast), 32 lanes on 16 or 17 consecutive words -- no conflict.  The even / odd lanes pick their taps
 // (g[2 q] or g[2 q + 1]) by a select between two scalars.  All fills and P accesses are consecutive.
 #include <cstdint>
-#include "common.h"
+#include "filterbank_dev.h"
 
 namespace faoctasr {
 
-constexpr int DWT1D_MAXL = 16, DWT1D_MAXJ = 8;
+constexpr int DWT1D_MAXJ = 8;
 constexpr int DWT1D_FUSED_MAX = 8192;
 constexpr int DWT1D_TA = 2048;                  // tiled analysis: outputs per workgroup
 constexpr int DWT1D_TS = 4096;                  // tiled synthesis: outputs per workgroup
-constexpr int D1_ZERO = 0, D1_SYMMETRIC = 1, D1_PER = 2, D1_REFLECT = 4, D1_PERIODIC = 6;
 
-struct Dwt1dTaps { float f0[DWT1D_MAXL], f1[DWT1D_MAXL]; };
 struct Dwt1dPtrs { float* p[DWT1D_MAXJ]; };
 struct Dwt1dLens { int n[DWT1D_MAXJ], src[DWT1D_MAXJ]; };   // analysis: logical / real input length; synthesis: count / crop
 // rows of an operand: row r starts at (r / inner) * outer + (r % inner) * step elements (an (N, C, n) tensor with last stride 1)
 struct Dwt1dRows { long inner, outer, step; };
 
-__device__ __forceinline__ int d1_pmod(int j, int P) {
-    const int m = j % P;
-    return m < 0 ? m + P : m;
-}
-
-// index of the sample that position j of the extended signal reads, -1 for a zero
-__device__ __forceinline__ int dwt1d_map(int j, int N, int mode, int L2) {
-    if (mode != D1_PER && j >= 0 && j < N) return j;
-    switch (mode) {
-        case D1_SYMMETRIC: { const int m = d1_pmod(j, 2 * N); return m < N ? m : 2 * N - 1 - m; }
-        case D1_REFLECT: { if (N == 1) return 0; const int m = d1_pmod(j, 2 * N - 2); return m < N ? m : 2 * N - 2 - m; }
-        case D1_PERIODIC: return d1_pmod(j, N);
-        case D1_PER: {
-            const int Ne = N + (N & 1);
-            if (j < -Ne || j >= Ne) return -1;
-            const int m = ((j < 0 ? j + Ne : j) + L2) % Ne;
-            return m < N ? m : N - 1;
-        }
-        default: return -1;
-    }
-}
-
 // one analysis output from its window w = &E[2 i] (8-byte aligned): taps k = 0 .. L-1 in order
-__device__ __forceinline__ void dwt1d_ana_out(const float* w, int L, const Dwt1dTaps& taps, float& lo, float& hv) {
+__device__ __forceinline__ void dwt1d_ana_out(const float* w, int L, const FbTaps1& taps, float& lo, float& hv) {
     float a = 0.f, b = 0.f;
     for (int k = 0; k < L; k += 2) {
         const float2 v = *reinterpret_cast<const float2*>(w + k);
@@ -101,27 +78,12 @@ __device__ __forceinline__ void dwt1d_ana_out(const float* w, int L, const Dwt1d
     hv = b;
 }
 
-// one synthesis output at the unwrapped position u from the patches A (lo) and H (hi), whose entry 0 is virtual coefficient ib
-__device__ __forceinline__ float dwt1d_syn_out(const float* A, const float* H, int ib, int n, int u, bool per, int L, const Dwt1dTaps& taps) {
-    const int lo_i = (per && u < 2 * n) ? -n : 0, hi_i = (per && u >= 2 * n) ? 2 * n : n;
-    const bool odd = u & 1;
-    float a0 = 0.f, a1 = 0.f;
-    for (int q = 0; q < (L >> 1); ++q) {
-        const int i = (u >> 1) - q;
-        if (i < lo_i || i >= hi_i) continue;
-        const float g0 = odd ? taps.f0[2 * q + 1] : taps.f0[2 * q], g1 = odd ? taps.f1[2 * q + 1] : taps.f1[2 * q];
-        a0 = fmaf(A[i - ib], g0, a0);
-        a1 = fmaf(H[i - ib], g1, a1);
-    }
-    return a0 + a1;
-}
-
 __device__ __forceinline__ int d1_out_size(int n, int L, bool per) { return per ? (n + 1) >> 1 : (n + L - 1) >> 1; }
 
 // shift = log2(R): lanes (tid >> (8 - shift)) ... own row r of the block, 256 >> shift lanes a row
 __global__ __launch_bounds__(256) void dwt1d_analysis_kernel(const float* __restrict__ x, Dwt1dRows xr, float* __restrict__ lo, Dwt1dPtrs hi,
                                                              long NC, int J, int shift, int tiles, int T, int ecap, int pcap, int L,
-                                                             int mode, Dwt1dLens len, Dwt1dTaps taps) {
+                                                             int mode, Dwt1dLens len, FbTaps1 taps) {
     extern __shared__ __attribute__((aligned(16))) float d1_smem[];
     const int R = 1 << shift, tpr = 256 >> shift;
     const int r = threadIdx.x >> (8 - shift), c0 = threadIdx.x & (tpr - 1);
@@ -131,7 +93,7 @@ __global__ __launch_bounds__(256) void dwt1d_analysis_kernel(const float* __rest
     float* E = d1_smem + (size_t)r * ecap;
     float* P = d1_smem + (size_t)R * ecap + (size_t)r * pcap;
     const float* xp = live ? x + (row / xr.inner) * xr.outer + (row % xr.inner) * xr.step : x;
-    const bool per = mode == D1_PER;
+    const bool per = mode == MODE_PER;
 
     for (int j = 0; j < J; ++j) {
         const int n = len.n[j], ns = len.src[j];
@@ -144,12 +106,12 @@ __global__ __launch_bounds__(256) void dwt1d_analysis_kernel(const float* __rest
             const int p0 = 2 * o0 - base;
             if (j == 0) {
                 for (int e = c0; e < elen; e += tpr) {
-                    const int s = dwt1d_map(p0 + e, n, mode, L >> 1);
+                    const int s = fb_map(p0 + e, n, mode, L >> 1);
                     E[e] = (s >= 0 && s < ns) ? xp[s] : 0.f;
                 }
             } else {
                 for (int e = c0; e < elen; e += tpr) {
-                    const int s = dwt1d_map(p0 + e, n, mode, L >> 1);
+                    const int s = fb_map(p0 + e, n, mode, L >> 1);
                     E[e] = (s >= 0 && s < ns) ? P[s] : 0.f;
                 }
             }
@@ -173,7 +135,7 @@ __global__ __launch_bounds__(256) void dwt1d_analysis_kernel(const float* __rest
 // len.n[j]: coefficient count of level j; len.src[j]: the length level j's result is cropped to (src[0] = out_len)
 __global__ __launch_bounds__(256) void dwt1d_synthesis_kernel(const float* __restrict__ lo, Dwt1dRows lr, Dwt1dPtrs hi, float* __restrict__ y,
                                                               long NC, int J, int shift, int tiles, int T, int acap, int pcap, int L,
-                                                              int mode, Dwt1dLens len, Dwt1dTaps taps) {
+                                                              int mode, Dwt1dLens len, FbTaps1 taps) {
     extern __shared__ __attribute__((aligned(16))) float d1_smem[];
     const int R = 1 << shift, tpr = 256 >> shift;
     const int r = threadIdx.x >> (8 - shift), c0 = threadIdx.x & (tpr - 1);
@@ -184,7 +146,7 @@ __global__ __launch_bounds__(256) void dwt1d_synthesis_kernel(const float* __res
     float* H = d1_smem + (size_t)R * acap + (size_t)r * acap;
     float* P = d1_smem + (size_t)2 * R * acap + (size_t)r * pcap;
     const float* lp = live ? lo + (row / lr.inner) * lr.outer + (row % lr.inner) * lr.step : lo;
-    const bool per = mode == D1_PER;
+    const bool per = mode == MODE_PER;
     const int off = per ? (L >> 1) - 1 : L - 2;
 
     for (int j = J - 1; j >= 0; --j) {
@@ -196,17 +158,17 @@ __global__ __launch_bounds__(256) void dwt1d_synthesis_kernel(const float* __res
         if (live) {
             const float* hp = hi.p[j] ? hi.p[j] + row * (long)n : nullptr;
             if (j == J - 1) {
-                for (int e = c0; e < pc; e += tpr) A[e] = lp[d1_pmod(ib + e, n)];
+                for (int e = c0; e < pc; e += tpr) A[e] = lp[pmod(ib + e, n)];
             } else {
-                for (int e = c0; e < pc; e += tpr) A[e] = P[d1_pmod(ib + e, n)];
+                for (int e = c0; e < pc; e += tpr) A[e] = P[pmod(ib + e, n)];
             }
-            for (int e = c0; e < pc; e += tpr) H[e] = hp ? hp[d1_pmod(ib + e, n)] : 0.f;
+            for (int e = c0; e < pc; e += tpr) H[e] = hp ? hp[pmod(ib + e, n)] : 0.f;
         }
         __syncthreads();
         if (live) {
             float* yp = y + row * (long)crop + t0;
             for (int c = c0; c < cnt; c += tpr) {
-                const float v = dwt1d_syn_out(A, H, ib, n, t0 + c + off, per, L, taps);
+                const float v = fb_syn_out(A, H, ib, n, t0 + c + off, per, L, taps);
                 if (j == 0) yp[c] = v; else P[c] = v;
             }
         }
@@ -218,8 +180,8 @@ static int d1_check(const char* what, long NC, int J, int L, int mode, const flo
     if (!a || !b) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
     if (NC < 1) return fail(FAOCTASR_EINVAL, "%s: NC %ld", what, NC);
     if (J < 1 || J > DWT1D_MAXJ) return fail(FAOCTASR_EINVAL, "%s: J %d outside 1..%d", what, J, DWT1D_MAXJ);
-    if (L < 2 || L > DWT1D_MAXL || (L & 1)) return fail(FAOCTASR_EINVAL, "%s: tap count L %d must be even and within 2..%d", what, L, DWT1D_MAXL);
-    if (mode != D1_ZERO && mode != D1_SYMMETRIC && mode != D1_PER && mode != D1_REFLECT && mode != D1_PERIODIC)
+    if (!fb_len_ok(L)) return fail(FAOCTASR_EINVAL, "%s: tap count L %d must be even and within 2..%d", what, L, FB_MAXL);
+    if (mode != MODE_ZERO && mode != MODE_SYMMETRIC && mode != MODE_PER && mode != MODE_REFLECT && mode != MODE_PERIODIC)
         return fail(FAOCTASR_EINVAL, "%s: unknown padding mode %d (0 zero, 1 symmetric, 2 periodization, 4 reflect, 6 periodic)", what, mode);
     return FAOCTASR_OK;
 }
@@ -227,12 +189,6 @@ static int d1_check(const char* what, long NC, int J, int L, int mode, const flo
 static int d1_rows_ok(const char* what, long inner, long outer, long step, long n) {
     if (inner < 1 || step < n || outer < 0) return fail(FAOCTASR_EINVAL, "%s: rows of %ld samples, %ld a group, strides %ld / %ld", what, n, inner, outer, step);
     return FAOCTASR_OK;
-}
-
-static Dwt1dTaps d1_taps(const float* f0, const float* f1, int L) {
-    Dwt1dTaps t = {};
-    for (int k = 0; k < L; ++k) { t.f0[k] = f0[k]; t.f1[k] = f1[k]; }
-    return t;
 }
 
 // log2 of the rows a fused workgroup owns: 256 / R lanes a row, about two level-0 outputs a lane, at least ~512 workgroups
@@ -258,7 +214,7 @@ extern "C" int faoctasr_dwt1d_analysis(const float* x, long x_inner, long x_oute
     if (n < 1) return fail(FAOCTASR_EINVAL, "dwt1d_analysis: n %d", n);
     if ((rc = d1_rows_ok("dwt1d_analysis", x_inner, x_outer_stride, x_row_stride, n))) return rc;
     if (!fused && J != 1) return fail(FAOCTASR_EINVAL, "dwt1d_analysis: the tiled launch runs one level a call, got J %d", J);
-    const bool per = mode == D1_PER;
+    const bool per = mode == MODE_PER;
     Dwt1dLens len = {};
     Dwt1dPtrs hp = {};
     int have = n, nmax = 0, omax = 0;                       // samples the level's source holds
@@ -292,7 +248,7 @@ extern "C" int faoctasr_dwt1d_analysis(const float* x, long x_inner, long x_oute
     if (groups > 0x7fffffffL / tiles) return fail(FAOCTASR_EUNSUPPORTED, "dwt1d_analysis: NC %ld n %d needs more than 2^31 - 1 blocks", NC, n);
     const size_t lds = ((size_t)(ecap + pcap) << shift) * sizeof(float);
     hipLaunchKernelGGL(dwt1d_analysis_kernel, dim3((unsigned)(groups * tiles)), dim3(256), lds, (hipStream_t)stream, x,
-                       Dwt1dRows{x_inner, x_outer_stride, x_row_stride}, lo, hp, NC, J, shift, tiles, T, ecap, pcap, L, mode, len, d1_taps(h0, h1, L));
+                       Dwt1dRows{x_inner, x_outer_stride, x_row_stride}, lo, hp, NC, J, shift, tiles, T, ecap, pcap, L, mode, len, fb_taps1(h0, h1, L));
     return check_launch("dwt1d_analysis");
 }
 
@@ -303,7 +259,7 @@ extern "C" int faoctasr_dwt1d_synthesis(const float* lo, long lo_inner, long lo_
     if (rc) return rc;
     if (!lo || !hi || !y || !counts) return fail(FAOCTASR_EINVAL, "dwt1d_synthesis: null pointer");
     if (!fused && J != 1) return fail(FAOCTASR_EINVAL, "dwt1d_synthesis: the tiled launch runs one level a call, got J %d", J);
-    const bool per = mode == D1_PER;
+    const bool per = mode == MODE_PER;
     Dwt1dLens len = {};
     Dwt1dPtrs hp = {};
     int nmax = 0;
@@ -337,6 +293,6 @@ extern "C" int faoctasr_dwt1d_synthesis(const float* lo, long lo_inner, long lo_
     if (groups > 0x7fffffffL / tiles) return fail(FAOCTASR_EUNSUPPORTED, "dwt1d_synthesis: NC %ld out_len %d needs more than 2^31 - 1 blocks", NC, out_len);
     const size_t lds = ((size_t)(2 * acap + pcap) << shift) * sizeof(float);
     hipLaunchKernelGGL(dwt1d_synthesis_kernel, dim3((unsigned)(groups * tiles)), dim3(256), lds, (hipStream_t)stream, lo,
-                       Dwt1dRows{lo_inner, lo_outer_stride, lo_row_stride}, hp, y, NC, J, shift, tiles, T, acap, pcap, L, mode, len, d1_taps(g0, g1, L));
+                       Dwt1dRows{lo_inner, lo_outer_stride, lo_row_stride}, hp, y, NC, J, shift, tiles, T, acap, pcap, L, mode, len, fb_taps1(g0, g1, L));
     return check_launch("dwt1d_synthesis");
 }

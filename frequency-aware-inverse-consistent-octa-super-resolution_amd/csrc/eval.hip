@@ -15,15 +15,6 @@ namespace faoctasr {
 constexpr int EV_P = 64;                  // partial min/max blocks per image
 constexpr int EV_WIN = 7, EV_PAD = 3;
 
-__device__ __forceinline__ double block_sum_256d(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // partial min / max of both images: mm[n][p][4] = {ymin, ymax, gmin, gmax}
 __global__ __launch_bounds__(256) void eval_minmax_kernel(const float* __restrict__ y, const float* __restrict__ g, float* __restrict__ mm, long HW) {
     __shared__ float red[4][4];
@@ -103,8 +94,8 @@ __global__ __launch_bounds__(256) void eval_sqerr_ssim_kernel(const float* __res
             ss += ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
         }
     }
-    se = block_sum_256d(se, red);
-    ss = block_sum_256d(ss, red);
+    se = block_sum_256(se, red);
+    ss = block_sum_256(ss, red);
     if (threadIdx.x == 0) {
         sums[((long)n * EV_P + p) * 2] = se;
         sums[((long)n * EV_P + p) * 2 + 1] = ss;
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const unsigned* __rest
             atomicAdd(&marg[bins + i % bins], (double)c);
         }
     }
-    hj = block_sum_256d(hj, red);
+    hj = block_sum_256(hj, red);
     __syncthreads();
     double ha = 0.0, hb = 0.0;
     for (int i = threadIdx.x; i < bins; i += 256) {
@@ -178,8 +169,8 @@ __global__ __launch_bounds__(256) void eval_finish_kernel(const unsigned* __rest
         if (a > 0.0) ha -= a * log(a);
         if (b > 0.0) hb -= b * log(b);
     }
-    ha = block_sum_256d(ha, red);
-    hb = block_sum_256d(hb, red);
+    ha = block_sum_256(ha, red);
+    hb = block_sum_256(hb, red);
     if (threadIdx.x == 0) {
         double se = 0.0, ss = 0.0;
         for (int q = 0; q < EV_P; ++q) {                                  // the blocks' partials, in their order

@@ -187,12 +187,7 @@ __global__ __launch_bounds__(256) void mi_final_kernel(const float* __restrict__
         if (i == j) acc += mi_h(P[e], eps);
         else if (i < j) acc += mi_h(P[e], eps) + mi_h(P[j * K + i], eps);
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
+    const double Hab = -block_tree_256(acc, red);
     if (tid < 2) {
         const double* hh = tid ? hb : ha;
         double s = 0.0;
@@ -200,7 +195,7 @@ __global__ __launch_bounds__(256) void mi_final_kernel(const float* __restrict__
         ent[tid] = -s;
     }
     __syncthreads();
-    const double Hm = ent[0] + ent[1], Hab = -red[0];
+    const double Hm = ent[0] + ent[1];
     if (tid == 0) score[plane] = normalized ? Hm / Hab : Hm - Hab;
     if (table) {
         const double cu = normalized ? 1.0 / Hab : 1.0, ca = normalized ? Hm / (Hab * Hab) : 1.0;
@@ -225,15 +220,8 @@ __global__ __launch_bounds__(256) void mi_mean_kernel(const double* __restrict__
         }
         return;
     }
-    double acc = 0.0;
-    for (long p = tid; p < N * C; p += 256) acc += score[p];
-    red[tid] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) out[0] = (float)(red[0] / (double)(N * C));
+    const double s = block_tree_256(strided_sum_256(score, N * C), red);
+    if (tid == 0) out[0] = (float)(s / (double)(N * C));
 }
 
 // one side's derivative for the pixel (lane & 31): sum_k ws_k ((k - k*) - m) sum_j G_kj wo_j, m = sum_k ws_k (k - k*), with

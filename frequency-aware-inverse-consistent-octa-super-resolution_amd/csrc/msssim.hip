@@ -25,11 +25,11 @@
 
 #pragma clang fp contract(off)
 
+#include "ssim_window.h"
+
 namespace faoctasr {
 
-constexpr int MS_R = 5;                            // window radius
 constexpr int MS_MAXLEV = 5;
-struct MsTaps { float g[11]; };
 
 // the five moments -> (cs, l); the same expressions in the forward and in the backward
 struct MsPoint { float m1, m2, A1, B1, A2, B2; };
@@ -43,35 +43,23 @@ __device__ __forceinline__ MsPoint ms_point(const float (&m)[5], float C1, float
     return p;
 }
 
-// blockIdx.x = (plane * tiles_h + tile row) * tiles_w + tile column: no 65535-plane limit, and an image's blocks are contiguous
-struct MsTile { int plane, y0, x0; };
-template <int TY, int TX>
-__device__ __forceinline__ MsTile ms_tile(int tiles_h, int tiles_w) {
-    unsigned bi = blockIdx.x;
-    MsTile t;
-    t.x0 = (int)(bi % (unsigned)tiles_w) * TX; bi /= (unsigned)tiles_w;
-    t.y0 = (int)(bi % (unsigned)tiles_h) * TY;
-    t.plane = (int)(bi / (unsigned)tiles_h);
-    return t;
-}
-
-constexpr int MF_TY = 16, MF_TX = 64, MF_PY = MF_TY + 2 * MS_R, MF_PX = MF_TX + 2 * MS_R;     // 26 x 74 staged values per image
+constexpr int MF_TY = 16, MF_TX = 64, MF_PY = MF_TY + 2 * SSIM_R, MF_PX = MF_TX + 2 * SSIM_R;     // 26 x 74 staged values per image
 
 __global__ __launch_bounds__(256) void msssim_scale_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                float* __restrict__ pa, float* __restrict__ pb, float* __restrict__ part,
                                                                int H, int W, int tiles_h, int tiles_w, int last, float C1, float C2,
-                                                               const MsTaps tp) {
+                                                               const SsimTaps tp) {
     __shared__ float as[MF_PY][MF_PX], bs[MF_PY][MF_PX];
     __shared__ float hz[5][MF_PY][MF_TX];
     __shared__ float red[4];
     const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
-    const MsTile t = ms_tile<MF_TY, MF_TX>(tiles_h, tiles_w);
+    const PlaneTile t = plane_tile<MF_TY, MF_TX>(tiles_h, tiles_w);
     const float* ap = a + (long)t.plane * H * W;
     const float* bp = b + (long)t.plane * H * W;
     for (int r = g; r < MF_PY; r += 4) {
-        const int yy = t.y0 + r - MS_R;
+        const int yy = t.y0 + r - SSIM_R;
         for (int cc = c; cc < MF_PX; cc += 64) {
-            const int xx = t.x0 + cc - MS_R;
+            const int xx = t.x0 + cc - SSIM_R;
             const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
             as[r][cc] = in ? ap[(long)yy * W + xx] : 0.f;
             bs[r][cc] = in ? bp[(long)yy * W + xx] : 0.f;
@@ -84,7 +72,7 @@ __global__ __launch_bounds__(256) void msssim_scale_fwd_kernel(const float* __re
         const int h2 = H >> 1, w2 = W >> 1;
         const int gy = (t.y0 >> 1) + py, gx = (t.x0 >> 1) + px;
         if (gy < h2 && gx < w2) {
-            const int r = MS_R + 2 * py, q = MS_R + 2 * px;
+            const int r = SSIM_R + 2 * py, q = SSIM_R + 2 * px;
             const long at = ((long)t.plane * h2 + gy) * w2 + gx;
             pa[at] = ((as[r][q] + as[r][q + 1]) + (as[r + 1][q] + as[r + 1][q + 1])) * 0.25f;
             pb[at] = ((bs[r][q] + bs[r][q + 1]) + (bs[r + 1][q] + bs[r + 1][q + 1])) * 0.25f;
@@ -129,11 +117,7 @@ __global__ __launch_bounds__(256) void msssim_scale_fwd_kernel(const float* __re
             const float cs = p.A2 / p.B2;
             acc += last ? (p.A1 / p.B1) * cs : cs;
         }
-    // per-thread sum -> 64-lane butterfly -> the four waves, in that order; thread 0 stores
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    block_partial_store_256(acc, red, part);
 }
 
 struct MsFinal {
@@ -158,6 +142,10 @@ __global__ __launch_bounds__(256) void msssim_final_kernel(const float* __restri
     double total = 0.0;
     for (int n = 0; n < N; ++n) {
         for (int j = 0; j < levels; ++j) {
+            // strided_sum_256 and block_tree_256 of common.h, written out: 64 images of 5 scales make 320 rounds a launch, and through
+            // the helpers the kernel traced 4% slower (profiles/shared_helpers_bench.txt).  The helpers differ from this text in two
+            // things, which were not measured apart: they index with long where an int does here, and every thread reads red[0]
+            // before the round's last barrier where only thread 0 does here
             const int cntj = per[j];
             const float* p = ws + off[j] + (long)n * cntj;
             double s = 0.0;
@@ -192,23 +180,23 @@ __global__ __launch_bounds__(256) void msssim_final_kernel(const float* __restri
 }
 
 constexpr int MB_TY = 16, MB_TX = 32;
-constexpr int MB_QY = MB_TY + 2 * MS_R, MB_QX = MB_TX + 2 * MS_R;      // region where the partial-derivative maps are needed
-constexpr int MB_PY = MB_QY + 2 * MS_R, MB_PX = MB_QX + 2 * MS_R;      // input region
+constexpr int MB_QY = MB_TY + 2 * SSIM_R, MB_QX = MB_TX + 2 * SSIM_R;      // region where the partial-derivative maps are needed
+constexpr int MB_PY = MB_QY + 2 * SSIM_R, MB_PX = MB_QX + 2 * SSIM_R;      // input region
 
 __global__ __launch_bounds__(256) void msssim_scale_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                                const float* __restrict__ coef, const float* __restrict__ gout, int gN,
                                                                const float* __restrict__ dca, const float* __restrict__ dcb,
                                                                float* __restrict__ da, float* __restrict__ db, int C, int H, int W,
-                                                               int tiles_h, int tiles_w, int last, float C1, float C2, const MsTaps tp) {
+                                                               int tiles_h, int tiles_w, int last, float C1, float C2, const SsimTaps tp) {
     __shared__ float as[MB_PY * MB_PX], bs[MB_PY * MB_PX];
     __shared__ float hz[5][MB_PY * MB_QX];                              // row-filtered moments; later the row-filtered maps
     __shared__ float pm[4][MB_QY * MB_QX];                              // d / d mu1, mu2, E[a^2] (= E[b^2]), E[ab]
-    const MsTile t = ms_tile<MB_TY, MB_TX>(tiles_h, tiles_w);
+    const PlaneTile t = plane_tile<MB_TY, MB_TX>(tiles_h, tiles_w);
     const float* ap = a + (long)t.plane * H * W;
     const float* bp = b + (long)t.plane * H * W;
     for (int i = threadIdx.x; i < MB_PY * MB_PX; i += 256) {
         const int r = i / MB_PX, c = i - r * MB_PX;
-        const int yy = t.y0 + r - 2 * MS_R, xx = t.x0 + c - 2 * MS_R;
+        const int yy = t.y0 + r - 2 * SSIM_R, xx = t.x0 + c - 2 * SSIM_R;
         const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
         as[i] = in ? ap[(long)yy * W + xx] : 0.f;
         bs[i] = in ? bp[(long)yy * W + xx] : 0.f;
@@ -228,7 +216,7 @@ __global__ __launch_bounds__(256) void msssim_scale_bwd_kernel(const float* __re
     __syncthreads();
     for (int i = threadIdx.x; i < MB_QY * MB_QX; i += 256) {
         const int r = i / MB_QX, c = i - r * MB_QX;
-        const int yy = t.y0 + r - MS_R, xx = t.x0 + c - MS_R;
+        const int yy = t.y0 + r - SSIM_R, xx = t.x0 + c - SSIM_R;
         float f0 = 0.f, f1 = 0.f, f2 = 0.f, f4 = 0.f;
         if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
             float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -282,7 +270,7 @@ __global__ __launch_bounds__(256) void msssim_scale_bwd_kernel(const float* __re
 #pragma unroll
                 for (int q = 0; q < 4; ++q) s[q] += w * hz[q][(r + k) * MB_TX + c];
             }
-            const float av = as[(r + 2 * MS_R) * MB_PX + c + 2 * MS_R], bv = bs[(r + 2 * MS_R) * MB_PX + c + 2 * MS_R];
+            const float av = as[(r + 2 * SSIM_R) * MB_PX + c + 2 * SSIM_R], bv = bs[(r + 2 * SSIM_R) * MB_PX + c + 2 * SSIM_R];
             const long off = (long)t.plane * H * W + (long)yy * W + xx;
             // a dropped odd row or column receives nothing from the coarser scale
             const bool pooled = (yy >> 1) < hc && (xx >> 1) < wc;
@@ -301,18 +289,6 @@ __global__ __launch_bounds__(256) void msssim_scale_bwd_kernel(const float* __re
     }
 }
 
-static MsTaps ms_taps() {
-    // ssim.py:7-9: gauss = Tensor([exp(-(x - 5)^2 / (2 * 1.5^2))]) (fp32) / gauss.sum()
-    MsTaps t;
-    float sum = 0.f;
-    for (int k = 0; k < 11; ++k) {
-        t.g[k] = (float)exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-        sum += t.g[k];
-    }
-    for (int k = 0; k < 11; ++k) t.g[k] /= sum;
-    return t;
-}
-
 // the shape rules of every entry point: scale `scale` (0-based) of a (planes, H, W) input has sides H >> scale, W >> scale
 static int ms_shape(const char* what, long planes, int H, int W, int levels) {
     if (levels < 1 || levels > MS_MAXLEV) return fail(FAOCTASR_EUNSUPPORTED, "%s: %d scales, 1..%d are built", what, levels, MS_MAXLEV);
@@ -324,12 +300,8 @@ static int ms_shape(const char* what, long planes, int H, int W, int levels) {
 
 template <int TY, int TX>
 static int ms_tiles(const char* what, long planes, int h, int w, int* tiles_h, int* tiles_w, long* blocks) {
-    *tiles_h = (h + TY - 1) / TY;
-    *tiles_w = (w + TX - 1) / TX;
-    const long per_plane = (long)*tiles_h * *tiles_w;
-    if (planes > 0x7fffffffL / per_plane) return fail(FAOCTASR_EUNSUPPORTED, "%s: %ld planes of %ld tiles exceed the grid", what, planes, per_plane);
-    *blocks = planes * per_plane;
-    return FAOCTASR_OK;
+    if (plane_tiles(planes, h, w, TY, TX, tiles_h, tiles_w, blocks)) return FAOCTASR_OK;
+    return fail(FAOCTASR_EUNSUPPORTED, "%s: %ld planes of %ld tiles exceed the grid", what, planes, (long)*tiles_h * *tiles_w);
 }
 
 static bool ms_consts_ok(float C1, float C2) { return C1 > 0.f && C2 > 0.f && C1 < INFINITY && C2 < INFINITY; }
@@ -367,7 +339,7 @@ extern "C" int faoctasr_msssim_scale_fwd(const float* a, const float* b, float* 
         if ((rc = ms_tiles<MF_TY, MF_TX>("msssim_scale_fwd", planes, H >> j, W >> j, &th, &tw, &blocks))) return rc;
     }
     hipLaunchKernelGGL(msssim_scale_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, pa, pb, workspace + off,
-                       H >> scale, W >> scale, th, tw, last, C1, C2, ms_taps());
+                       H >> scale, W >> scale, th, tw, last, C1, C2, ssim_taps());
     return check_launch("msssim_scale_fwd");
 }
 
@@ -413,6 +385,6 @@ extern "C" int faoctasr_msssim_scale_bwd(const float* a, const float* b, const f
     long blocks;
     if ((rc = ms_tiles<MB_TY, MB_TX>("msssim_scale_bwd", N * C, H >> scale, W >> scale, &th, &tw, &blocks))) return rc;
     hipLaunchKernelGGL(msssim_scale_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, coef + (long)scale * N, g, gN,
-                       da ? dca : nullptr, db ? dcb : nullptr, da, db, (int)C, H >> scale, W >> scale, th, tw, last, C1, C2, ms_taps());
+                       da ? dca : nullptr, db ? dcb : nullptr, da, db, (int)C, H >> scale, W >> scale, th, tw, last, C1, C2, ssim_taps());
     return check_launch("msssim_scale_bwd");
 }

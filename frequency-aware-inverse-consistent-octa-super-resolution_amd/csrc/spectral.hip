@@ -484,13 +484,8 @@ __global__ __launch_bounds__(256) void ffl_finish_kernel(const float* __restrict
         if (inv_phi) inv_phi[p] = ok ? (float)(1.0 / ph) : 0.f;
         if (ok) acc += stats[2 * p] / ph;
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) *loss = (float)(red[0] / count);
+    acc = block_tree_256(acc, red);
+    if (tid == 0) *loss = (float)(acc / count);
 }
 
 // [T1 | T2] = [C_H dRe + S_H dJ | C_H dJ - S_H dRe] with (dRe, dJ) = g * coef * phi(q) / phi(M) * (Re, J) formed from the saved

@@ -9,12 +9,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "ssim_window.h"
 
 namespace faoctasr {
 
-struct Taps { float g[11]; };
-
-constexpr int R = 5;                 // window radius
 constexpr float C1 = 0.01f * 0.01f;  // ssim.py:29-30
 constexpr float C2 = 0.03f * 0.03f;
 
@@ -30,10 +28,10 @@ __device__ __forceinline__ float ssim_point(float m1, float m2, float e11, float
 // (4 row-pass outputs from 14 staged pairs, 3 column-pass outputs from 13 row-filtered values per thread; 512 threads), which also cuts the
 // LDS reads per pixel from ~90 to ~30.  Tap order per output is unchanged from the plain form.
 typedef float f2 __attribute__((ext_vector_type(2)));
-constexpr int SF_TY = 22, SF_TX = 64, SF_PY = SF_TY + 2 * R, SF_PX = 74;      // 32 staged rows of 74 pairs
+constexpr int SF_TY = 22, SF_TX = 64, SF_PY = SF_TY + 2 * SSIM_R, SF_PX = 74;      // 32 staged rows of 74 pairs
 
 __global__ __launch_bounds__(512) void ssim_fwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
-                                                       float* __restrict__ sums, int C, int H, int W, const Taps tp) {
+                                                       float* __restrict__ sums, int C, int H, int W, const SsimTaps tp) {
     __shared__ __attribute__((aligned(16))) f2 ab[SF_PY * SF_PX];                  // (a, b)
     __shared__ __attribute__((aligned(16))) f2 hz01[SF_PY * SF_TX], hz23[SF_PY * SF_TX];   // (mu_a, mu_b), (E a^2, E b^2) row-filtered
     __shared__ float hz4[SF_PY * SF_TX];                                          // E ab row-filtered
@@ -44,11 +42,11 @@ __global__ __launch_bounds__(512) void ssim_fwd_kernel(const float* __restrict__
     const float* bp = b + (long)plane * H * W;
     {   // 4 rows per pass, 128 threads per row (74 used); 60 KiB of LDS allow two blocks per CU, hence 512 threads each
         const int c = threadIdx.x & 127, rbase = threadIdx.x >> 7;
-        const int xx = x0 + c - R;
+        const int xx = x0 + c - SSIM_R;
         const bool cin = c < SF_PX && (unsigned)xx < (unsigned)W;
 #pragma unroll
         for (int r = rbase; r < SF_PY; r += 4) {
-            const int yy = y0 + r - R;
+            const int yy = y0 + r - SSIM_R;
             const bool in = cin && (unsigned)yy < (unsigned)H;
             if (c < SF_PX) ab[r * SF_PX + c] = in ? f2{ap[(long)yy * W + xx], bp[(long)yy * W + xx]} : f2{0.f, 0.f};
         }
@@ -113,10 +111,10 @@ __global__ __launch_bounds__(512) void ssim_fwd_kernel(const float* __restrict__
 // backward: tile 16 x 32 outputs
 __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                        const float* __restrict__ gout, int gN, float gscale, float* __restrict__ da,
-                                                       float* __restrict__ db, int C, int H, int W, const Taps tp) {
+                                                       float* __restrict__ db, int C, int H, int W, const SsimTaps tp) {
     constexpr int TY = 16, TX = 32;
-    constexpr int QY = TY + 2 * R, QX = TX + 2 * R;       // region where the ssim map's partials are needed
-    constexpr int PY = QY + 2 * R, PX = QX + 2 * R;       // input region
+    constexpr int QY = TY + 2 * SSIM_R, QX = TX + 2 * SSIM_R;       // region where the ssim map's partials are needed
+    constexpr int PY = QY + 2 * SSIM_R, PX = QX + 2 * SSIM_R;       // input region
     __shared__ float as[PY * PX], bs[PY * PX];
     __shared__ float hz[5][PY * QX];                      // row-filtered moments; later reused for row-filtered partials
     __shared__ float pm[5][QY * QX];                      // partial-derivative maps f_m1, f_m2, f_e11, f_e22, f_e12
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
     const float* bp = b + (long)plane * H * W;
     for (int i = threadIdx.x; i < PY * PX; i += 256) {
         const int r = i / PX, c = i - r * PX;
-        const int yy = y0 + r - 2 * R, xx = x0 + c - 2 * R;
+        const int yy = y0 + r - 2 * SSIM_R, xx = x0 + c - 2 * SSIM_R;
         const bool in = (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
         as[i] = in ? ap[(long)yy * W + xx] : 0.f;
         bs[i] = in ? bp[(long)yy * W + xx] : 0.f;
@@ -145,7 +143,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
     __syncthreads();
     for (int i = threadIdx.x; i < QY * QX; i += 256) {
         const int r = i / QX, c = i - r * QX;
-        const int yy = y0 + r - R, xx = x0 + c - R;
+        const int yy = y0 + r - SSIM_R, xx = x0 + c - SSIM_R;
         float f[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
             float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
 #pragma unroll
                 for (int q = 0; q < 5; ++q) s[q] += g * hz[q][(r + k) * TX + c];
             }
-            const float av = as[(r + 2 * R) * PX + c + 2 * R], bv = bs[(r + 2 * R) * PX + c + 2 * R];
+            const float av = as[(r + 2 * SSIM_R) * PX + c + 2 * SSIM_R], bv = bs[(r + 2 * SSIM_R) * PX + c + 2 * SSIM_R];
             const long off = (long)plane * H * W + (long)yy * W + xx;
             if (da) da[off] = gv * (s[0] + 2.f * av * s[2] + bv * s[4]);
             if (db) db[off] = gv * (s[1] + 2.f * bv * s[3] + av * s[4]);
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const float* __restrict__
 // the 12 pairs its two columns need (6 ds_read_b128) and forms the five row-filtered moments; the column pass runs over an
 // 11-row register ring (row loop unrolled 11x, so ring slots are static registers).  LDS traffic 14 B in / 96 B out per lane and
 // row instead of ~135 B per pixel, one global read of each input, and the only synchronisation is the wave's own lgkmcnt.
-constexpr int SL_COLS = 128, SL_PAIRS = SL_COLS + 2 * R + 2;          // pairs per LDS row (index i <-> column x0 - 5 + i)
+constexpr int SL_COLS = 128, SL_PAIRS = SL_COLS + 2 * SSIM_R + 2;          // pairs per LDS row (index i <-> column x0 - 5 + i)
 
 template <int I, int N, class F>
 __device__ __forceinline__ void ss_static_for(F&& f) {
@@ -228,7 +226,7 @@ __device__ __forceinline__ void ss_static_for(F&& f) {
 struct Mom { float ma, mb, mss, mab; };                                  // mu_a, mu_b, E (a^2 + b^2), E ab
 
 // row-filtered moments of the lane's two columns from the 12 staged pairs
-__device__ __forceinline__ void row_moments(const f2 (&v)[12], const Taps& tp, Mom (&out)[2]) {
+__device__ __forceinline__ void row_moments(const f2 (&v)[12], const SsimTaps& tp, Mom (&out)[2]) {
     float ss[12], ab[12];
 #pragma unroll
     for (int q = 0; q < 12; ++q) { ss[q] = __builtin_fmaf(v[q][1], v[q][1], v[q][0] * v[q][0]); ab[q] = v[q][0] * v[q][1]; }
@@ -258,9 +256,9 @@ __device__ __forceinline__ float ssim_point_sum(float m1, float m2, float ess, f
 // stage one input row of the strip in the wave's LDS row and fetch the lane's 12 pairs.  `cur` = this lane's two columns of
 // the row as loaded from global memory ((a0,a1),(b0,b1)), `halo` = the pair of the lane's halo column (lanes 0..9).
 __device__ __forceinline__ void exchange_row(f2* rowbuf, int lane, const f2& a2, const f2& b2, const f2& halo, f2 (&v)[12]) {
-    rowbuf[R + 2 * lane] = f2{a2[0], b2[0]};
-    rowbuf[R + 2 * lane + 1] = f2{a2[1], b2[1]};
-    if (lane < 2 * R) rowbuf[lane < R ? lane : SL_COLS + lane] = halo;
+    rowbuf[SSIM_R + 2 * lane] = f2{a2[0], b2[0]};
+    rowbuf[SSIM_R + 2 * lane + 1] = f2{a2[1], b2[1]};
+    if (lane < 2 * SSIM_R) rowbuf[lane < SSIM_R ? lane : SL_COLS + lane] = halo;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");               // other lanes' stores before this lane's loads: the wave runs
     __builtin_amdgcn_wave_barrier();                                     // in lockstep and its LDS operations retire in order, so this
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");               // only pins the compiler's ordering (no instruction)
@@ -290,7 +288,7 @@ __device__ __forceinline__ SlideItem slide_item(long item, int planes, int nstri
 }
 
 __global__ __launch_bounds__(256) void ssim_fwd_slide_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ sums,
-                                                             int planes, int C, int H, int W, int nstrips, int nseg, int seg_rows, const Taps tp) {
+                                                             int planes, int C, int H, int W, int nstrips, int nseg, int seg_rows, const SsimTaps tp) {
     __shared__ __attribute__((aligned(16))) f2 rows_lds[4][SL_PAIRS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const SlideItem it = slide_item((long)blockIdx.x * 4 + wave, planes, nstrips, nseg, seg_rows, H);
@@ -300,8 +298,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_slide_kernel(const float* __rest
     const float* bp = b + (long)it.plane * H * W;
     const int xc = it.x0 + 2 * lane;                                     // the lane's first column
     const bool cin = xc < W;                                             // W even: both columns in or out
-    const int xh = lane < R ? it.x0 - R + lane : it.x0 + SL_COLS + (lane - R);      // halo column of lanes 0..9
-    const bool hin = lane < 2 * R && (unsigned)xh < (unsigned)W;
+    const int xh = lane < SSIM_R ? it.x0 - SSIM_R + lane : it.x0 + SL_COLS + (lane - SSIM_R);      // halo column of lanes 0..9
+    const bool hin = lane < 2 * SSIM_R && (unsigned)xh < (unsigned)W;
     auto load_row = [&](int y, f2& a2, f2& b2, f2& halo) {
         a2 = f2{0.f, 0.f}; b2 = f2{0.f, 0.f}; halo = f2{0.f, 0.f};
         if ((unsigned)y < (unsigned)H) {                                 // uniform; rows outside the image are zero padding
@@ -322,7 +320,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_slide_kernel(const float* __rest
 #pragma unroll
         for (int j = 0; j < 2; ++j) ring[s][j] = mom_zero();
     float local = 0.f;
-    const int y_first = it.r0 - R, y_last = it.r1 - 1 + R;              // input rows that feed the segment's outputs
+    const int y_first = it.r0 - SSIM_R, y_last = it.r1 - 1 + SSIM_R;              // input rows that feed the segment's outputs
     f2 na2[PF], nb2[PF], nh[PF];                                         // rows yin .. yin + PF - 1, slot = row index mod PF
 #pragma unroll
     for (int p = 0; p < PF; ++p) load_row(y_first + p <= y_last ? y_first + p : -1, na2[p], nb2[p], nh[p]);
@@ -336,7 +334,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_slide_kernel(const float* __rest
                 f2 v[12];
                 exchange_row(rowbuf, lane, a2, b2, hh, v);
                 row_moments(v, tp, ring[j]);
-                const int yo = yin - R;
+                const int yo = yin - SSIM_R;
                 if (yo >= it.r0) {                                       // rows yo-5 .. yo+5 = yin-10 .. yin sit in slots j+2 .. j+12 (mod 12)
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {
@@ -385,7 +383,7 @@ __device__ __forceinline__ void f5_axpy(F5& acc, float g, const F5& h) {
 // to fit, which it does without scratch)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void ssim_bwd_slide_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ gout,
                                                             int gN, float gscale, float* __restrict__ da, float* __restrict__ db, int planes, int C,
-                                                            int H, int W, int nstrips, int nseg, int seg_rows, const Taps tp) {
+                                                            int H, int W, int nstrips, int nseg, int seg_rows, const SsimTaps tp) {
     __shared__ __attribute__((aligned(16))) f2 rowbuf[SL_PAIRS];
     __shared__ __attribute__((aligned(16))) f2 fbuf[(SL_COLS + 12) * 2];    // per column (f0,f1),(f2,f4): 16 bytes; index i <-> column x0 - 6 + i
     const int lane = threadIdx.x;
@@ -406,8 +404,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     const float* bp = b + (long)it.plane * H * W;
     const int xc = it.x0 + 2 * lane;                                     // even (x0 even): the lane's two columns are both in or both out
     const bool cin = (unsigned)xc < (unsigned)W;
-    const int xh = lane < R ? it.x0 - R + lane : it.x0 + SL_COLS + (lane - R);
-    const bool hin = lane < 2 * R && (unsigned)xh < (unsigned)W;
+    const int xh = lane < SSIM_R ? it.x0 - SSIM_R + lane : it.x0 + SL_COLS + (lane - SSIM_R);
+    const bool hin = lane < 2 * SSIM_R && (unsigned)xh < (unsigned)W;
     const bool cout = cin && 2 * lane >= SB_LEFT && 2 * lane < SB_LEFT + SB_OUT;      // this lane writes gradients
     auto load_row = [&](int y, f2& a2, f2& b2, f2& halo) {
         a2 = f2{0.f, 0.f}; b2 = f2{0.f, 0.f}; halo = f2{0.f, 0.f};
@@ -428,7 +426,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         for (int j = 0; j < 2; ++j) { ring1[s][j] = mom_zero(); ring2[s][j] = f5_zero(); }
     // input row yin enters ring 1; the map row yo1 = yin - 5 leaves it as f and enters ring 2 (row-filtered); the gradient row
     // yo2 = yin - 10 leaves ring 2.  Rows outside the image are zero in both stages.
-    const int y_first = it.r0 - 2 * R, y_last = it.r1 - 1 + 2 * R;
+    const int y_first = it.r0 - 2 * SSIM_R, y_last = it.r1 - 1 + 2 * SSIM_R;
     f2 na2, nb2, nh;
     load_row(y_first, na2, nb2, nh);
     for (int ybase = y_first; ybase <= y_last; ybase += 11) {
@@ -439,7 +437,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 const f2 a2 = na2, b2 = nb2, hh = nh;
                 if (yin + 1 <= y_last) load_row(yin + 1, na2, nb2, nh);
                 // the inputs of the gradient row this iteration will finish (L2-resident: read 10 rows ago), issued before the arithmetic
-                const int yo2 = yin - 2 * R;
+                const int yo2 = yin - 2 * SSIM_R;
                 f2 av = {0.f, 0.f}, bv = {0.f, 0.f};
                 if (yo2 >= it.r0 && cout) {
                     av = *reinterpret_cast<const f2*>(ap + (long)yo2 * W + xc);
@@ -449,7 +447,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 exchange_row(rowbuf, lane, a2, b2, hh, v);
                 row_moments(v, tp, ring1[j]);
                 // stage 1 column pass -> partials of map row yo1 on the lane's two columns
-                const int yo1 = yin - R;
+                const int yo1 = yin - SSIM_R;
                 F5 f[2];
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
@@ -510,18 +508,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }
 }
 
-static Taps make_taps() {
-    // ssim.py:7-9: gauss = Tensor([exp(-(x - 5)^2 / (2 * 1.5^2))]) (fp32) / gauss.sum()
-    Taps t;
-    float sum = 0.f;
-    for (int k = 0; k < 11; ++k) {
-        t.g[k] = (float)exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-        sum += t.g[k];
-    }
-    for (int k = 0; k < 11; ++k) t.g[k] /= sum;
-    return t;
-}
-
 }  // namespace faoctasr
 
 using namespace faoctasr;
@@ -542,11 +528,11 @@ int faoctasr_ssim_fwd(const float* a, const float* b, float* sums, int N, int C,
         const int nseg = (H + seg_rows - 1) / seg_rows;
         const long items = (long)planes * nstrips * nseg;
         hipLaunchKernelGGL(ssim_fwd_slide_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, a, b, sums, planes, C, H, W, nstrips, nseg,
-                           seg_rows, make_taps());
+                           seg_rows, ssim_taps());
         return check_launch("ssim_fwd");
     }
     dim3 grid((W + SF_TX - 1) / SF_TX, (H + SF_TY - 1) / SF_TY, N * C);
-    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(512), 0, st, a, b, sums, C, H, W, make_taps());
+    hipLaunchKernelGGL(ssim_fwd_kernel, grid, dim3(512), 0, st, a, b, sums, C, H, W, ssim_taps());
     return check_launch("ssim_fwd");
 }
 
@@ -563,11 +549,11 @@ int faoctasr_ssim_bwd(const float* a, const float* b, const float* g, int gN, fl
         const int nseg = (H + seg_rows - 1) / seg_rows;
         const long items = (long)planes * nstrips * nseg;
         hipLaunchKernelGGL(ssim_bwd_slide_kernel, dim3((unsigned)items), dim3(64), 0, (hipStream_t)stream, a, b, g, gN, gscale, da, db, planes, C, H, W,
-                           nstrips, nseg, seg_rows, make_taps());
+                           nstrips, nseg, seg_rows, ssim_taps());
         return check_launch("ssim_bwd");
     }
     dim3 grid((W + 31) / 32, (H + 15) / 16, N * C);
-    hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, b, g, gN, gscale, da, db, C, H, W, make_taps());
+    hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, b, g, gN, gscale, da, db, C, H, W, ssim_taps());
     return check_launch("ssim_bwd");
 }
 

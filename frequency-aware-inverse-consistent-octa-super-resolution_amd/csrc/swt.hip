@@ -32,40 +32,20 @@
 // The taps travel by value in the kernel arguments: no device allocation, no copy, no state -- the launches can be captured in
 // a graph.  Every output is a fixed-order sum whatever the tile it falls in: bit-reproducible.
 #include <cstdint>
-#include "common.h"
+#include "filterbank_dev.h"
 
 namespace faoctasr {
 
-constexpr int SWT_MAXL = 16, SWT_MAXD = 8;
-constexpr int SWT_ZERO = 0, SWT_SYMMETRIC = 1, SWT_REFLECT = 4, SWT_PERIODIC = 6;
-
-struct SwtTaps {
-    float w0[SWT_MAXL], w1[SWT_MAXL], h0[SWT_MAXL], h1[SWT_MAXL];
-};
+constexpr int SWT_MAXD = 8;
 
 constexpr int SA_TH = 16, SA_TW = 64;                           // analysis: output tile (rows of one residue class, columns)
-constexpr int SA_PR = SA_TH + SWT_MAXL - 1;                     // patch rows
-constexpr int SA_PC = SA_TW + (SWT_MAXL - 1) * SWT_MAXD;        // patch columns
+constexpr int SA_PR = SA_TH + FB_MAXL - 1;                     // patch rows
+constexpr int SA_PC = SA_TW + (FB_MAXL - 1) * SWT_MAXD;        // patch columns
 constexpr int SJ_TH = 16, SJ_TW = 64;                           // adjoint: output tile
-constexpr int SJ_PC = SJ_TW + SWT_MAXL * SWT_MAXD;              // columns of the H pass's half-sums
-
-__device__ __forceinline__ int swt_pmod(int j, int P) {
-    const int m = j % P;
-    return m < 0 ? m + P : m;
-}
-
-// index of the sample that position j of the extended signal reads, -1 for a zero (N >= 2 for reflect: the geometry rule)
-__device__ __forceinline__ int swt_map(int j, int N, int mode) {
-    switch (mode) {
-        case SWT_SYMMETRIC: { const int m = swt_pmod(j, 2 * N); return m < N ? m : 2 * N - 1 - m; }
-        case SWT_REFLECT: { const int m = swt_pmod(j, 2 * N - 2); return m < N ? m : 2 * N - 2 - m; }
-        case SWT_PERIODIC: return swt_pmod(j, N);
-        default: return (j >= 0 && j < N) ? j : -1;
-    }
-}
+constexpr int SJ_PC = SJ_TW + FB_MAXL * SWT_MAXD;              // columns of the H pass's half-sums
 
 __global__ __launch_bounds__(256) void swt_analysis_kernel(const float* __restrict__ x, long xps, float* __restrict__ y, int H, int W, int d,
-                                                           int tiles_h, int tiles_w, int Lh, int Lw, int mode, float scale, SwtTaps taps) {
+                                                           int tiles_h, int tiles_w, int Lh, int Lw, int mode, float scale, FbTaps2 taps) {
     __shared__ float patch[SA_PR][SA_PC];
     __shared__ float mid_lo[SA_PR][SA_TW], mid_hi[SA_PR][SA_TW];
     const int tid = threadIdx.x;
@@ -81,9 +61,9 @@ __global__ __launch_bounds__(256) void swt_analysis_kernel(const float* __restri
 
     // patch row q holds extended row r + d (t0 + q - Lh/2 + 1), patch column c extended column j0 + c - (Lw/2 - 1) d
     for (int c = tid & 63; c < cols; c += 64) {
-        const int sc = swt_map(j0 + c - ((Lw >> 1) - 1) * d, W, mode);
+        const int sc = fb_map(j0 + c - ((Lw >> 1) - 1) * d, W, mode, 0);
         for (int q = tid >> 6; q < rows; q += 4) {
-            const int sr = swt_map(r + d * (t0 + q - (Lh >> 1) + 1), H, mode);
+            const int sr = fb_map(r + d * (t0 + q - (Lh >> 1) + 1), H, mode, 0);
             patch[q][c] = (sr >= 0 && sc >= 0) ? xp[(long)sr * W + sc] : 0.f;
         }
     }
@@ -94,8 +74,8 @@ __global__ __launch_bounds__(256) void swt_analysis_kernel(const float* __restri
         float lo = 0.f, hv = 0.f;
         for (int k = 0; k < Lw; ++k) {
             const float v = patch[q][jj + (Lw - 1 - k) * d];
-            lo = fmaf(taps.w0[k], v, lo);
-            hv = fmaf(taps.w1[k], v, hv);
+            lo = fmaf(taps.w.f0[k], v, lo);
+            hv = fmaf(taps.w.f1[k], v, hv);
         }
         mid_lo[q][jj] = lo;
         mid_hi[q][jj] = hv;
@@ -110,10 +90,10 @@ __global__ __launch_bounds__(256) void swt_analysis_kernel(const float* __restri
         float a = 0.f, bb = 0.f, cc = 0.f, dd = 0.f;
         for (int k = 0; k < Lh; ++k) {
             const float vl = mid_lo[t + Lh - 1 - k][jj], vh = mid_hi[t + Lh - 1 - k][jj];
-            a = fmaf(taps.h0[k], vl, a);
-            bb = fmaf(taps.h1[k], vl, bb);
-            cc = fmaf(taps.h0[k], vh, cc);
-            dd = fmaf(taps.h1[k], vh, dd);
+            a = fmaf(taps.h.f0[k], vl, a);
+            bb = fmaf(taps.h.f1[k], vl, bb);
+            cc = fmaf(taps.h.f0[k], vh, cc);
+            dd = fmaf(taps.h.f1[k], vh, dd);
         }
         if (i < H && j < W) {
             const long o = i * W + j;
@@ -128,18 +108,18 @@ __global__ __launch_bounds__(256) void swt_analysis_kernel(const float* __restri
 // the two half-sums of the adjoint's H pass at row p (any integer) and column sc: taps k = 0 .. Lh-1 over the rows p + (k - Lh/2) d
 // that fall inside the image (wrap: taken mod H).  Band 0 is c's own (own0, NULL when replaced) plus the extra plane x0 (NULL: none)
 __device__ __forceinline__ void swt_adj_rows(const float* __restrict__ cp, const float* __restrict__ own0, const float* __restrict__ x0, long band,
-                                             int W, int H, int p, int sc, int d, int Lh, bool wrap, const SwtTaps& taps, float& lo, float& hv) {
+                                             int W, int H, int p, int sc, int d, int Lh, bool wrap, const FbTaps2& taps, float& lo, float& hv) {
     for (int k = 0; k < Lh; ++k) {
         int e = p + (k - (Lh >> 1)) * d;
-        if (wrap) e = swt_pmod(e, H);
+        if (wrap) e = pmod(e, H);
         if (e < 0 || e >= H) continue;
         const long o = (long)e * W + sc;
         float v = own0 ? own0[o] : 0.f;
         if (x0) v += x0[o];
-        lo = fmaf(taps.h0[k], v, lo);
-        lo = fmaf(taps.h1[k], cp[band + o], lo);
-        hv = fmaf(taps.h0[k], cp[2 * band + o], hv);
-        hv = fmaf(taps.h1[k], cp[3 * band + o], hv);
+        lo = fmaf(taps.h.f0[k], v, lo);
+        lo = fmaf(taps.h.f1[k], cp[band + o], lo);
+        hv = fmaf(taps.h.f0[k], cp[2 * band + o], hv);
+        hv = fmaf(taps.h.f1[k], cp[3 * band + o], hv);
     }
 }
 
@@ -147,19 +127,19 @@ __device__ __forceinline__ void swt_adj_rows(const float* __restrict__ cp, const
 // column 0 is virtual column v0 (the half-sums of a column outside the image are zero in the folding modes, so a mirrored
 // preimage needs no clipping to the image, only to the staged columns)
 __device__ __forceinline__ float swt_adj_cols(const float* __restrict__ lo, const float* __restrict__ hv, int p, int v0, int d, int Lw,
-                                              const SwtTaps& taps, float acc) {
+                                              const FbTaps2& taps, float acc) {
     for (int k = 0; k < Lw; ++k) {
         const int m = p + (k - (Lw >> 1)) * d - v0;
         if (m < 0 || m >= SJ_PC) continue;
-        acc = fmaf(taps.w0[k], lo[m], acc);
-        acc = fmaf(taps.w1[k], hv[m], acc);
+        acc = fmaf(taps.w.f0[k], lo[m], acc);
+        acc = fmaf(taps.w.f1[k], hv[m], acc);
     }
     return acc;
 }
 
 __global__ __launch_bounds__(256) void swt_adjoint_kernel(const float* __restrict__ c, float* __restrict__ dx, long dps,
                                                           const float* __restrict__ band0, long b0ps, int band0_replaces, int H, int W, int d,
-                                                          int tiles_h, int tiles_w, int Lh, int Lw, int mode, float scale, SwtTaps taps) {
+                                                          int tiles_h, int tiles_w, int Lh, int Lw, int mode, float scale, FbTaps2 taps) {
     __shared__ float mid_lo[SJ_TH][SJ_PC], mid_hi[SJ_TH][SJ_PC];
     const int tid = threadIdx.x;
     long b = blockIdx.x;
@@ -173,14 +153,14 @@ __global__ __launch_bounds__(256) void swt_adjoint_kernel(const float* __restric
     const float* cp = c + plane * 4 * band;
     const float* x0 = band0 ? band0 + plane * b0ps : nullptr;          // joins band 0 of c, or stands in for it
     const float* own0 = (band0 && band0_replaces) ? nullptr : cp;
-    const bool wrap = mode == SWT_PERIODIC, fold = mode == SWT_SYMMETRIC || mode == SWT_REFLECT;
-    const int off = mode == SWT_SYMMETRIC ? 1 : 0;                      // mirrors of j: -off - j and 2 N - 2 + off - j
+    const bool wrap = mode == MODE_PERIODIC, fold = mode == MODE_SYMMETRIC || mode == MODE_REFLECT;
+    const int off = mode == MODE_SYMMETRIC ? 1 : 0;                      // mirrors of j: -off - j and 2 N - 2 + off - j
     const int v0 = j0 - (Lw >> 1) * d;                                  // virtual column of half-sum column 0
     const int cols = SJ_TW + Lw * d;                                    // <= SJ_PC
 
     for (int m = tid & 63; m < SJ_PC; m += 64) {                        // H pass (columns past `cols` are cleared, never read)
         const int v = v0 + m;
-        const int sc = m < cols ? (wrap ? swt_pmod(v, W) : (v >= 0 && v < W ? v : -1)) : -1;
+        const int sc = m < cols ? (wrap ? pmod(v, W) : (v >= 0 && v < W ? v : -1)) : -1;
         for (int t = tid >> 6; t < SJ_TH; t += 4) {
             const long jl = r + (long)d * (t0 + t);
             float lo = 0.f, hv = 0.f;
@@ -217,11 +197,8 @@ __global__ __launch_bounds__(256) void swt_adjoint_kernel(const float* __restric
 
 static int swt_check(const char* what, long NC, int H, int W, long plane_stride, int L_h, int L_w, int dilation, int mode, const float* a,
                      const float* b, const float* c, const float* d) {
-    if (!a || !b || !c || !d) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
-    if (NC < 1) return fail(FAOCTASR_EINVAL, "%s: NC %ld", what, NC);
-    if (L_h < 2 || L_h > SWT_MAXL || (L_h & 1) || L_w < 2 || L_w > SWT_MAXL || (L_w & 1))
-        return fail(FAOCTASR_EINVAL, "%s: tap counts L_h %d L_w %d must be even and within 2..%d", what, L_h, L_w, SWT_MAXL);
-    if (mode != SWT_ZERO && mode != SWT_SYMMETRIC && mode != SWT_REFLECT && mode != SWT_PERIODIC)
+    if (int rc = fb_check2(what, NC, L_h, L_w, a, b, c, d)) return rc;
+    if (mode != MODE_ZERO && mode != MODE_SYMMETRIC && mode != MODE_REFLECT && mode != MODE_PERIODIC)
         return fail(FAOCTASR_EINVAL, "%s: unknown extension %d (0 zero, 1 symmetric, 4 reflect, 6 periodic)", what, mode);
     if (dilation != 1 && dilation != 2 && dilation != 4 && dilation != SWT_MAXD)
         return fail(FAOCTASR_EINVAL, "%s: dilation %d is not one of 1, 2, 4, %d", what, dilation, SWT_MAXD);
@@ -230,13 +207,6 @@ static int swt_check(const char* what, long NC, int H, int W, long plane_stride,
                     dilation);
     if (plane_stride < (long)H * W) return fail(FAOCTASR_EINVAL, "%s: plane stride %ld below H W = %ld", what, plane_stride, (long)H * W);
     return FAOCTASR_OK;
-}
-
-static SwtTaps swt_taps(const float* lo_h, const float* hi_h, int L_h, const float* lo_w, const float* hi_w, int L_w) {
-    SwtTaps t = {};
-    for (int k = 0; k < L_h; ++k) { t.h0[k] = lo_h[k]; t.h1[k] = hi_h[k]; }
-    for (int k = 0; k < L_w; ++k) { t.w0[k] = lo_w[k]; t.w1[k] = hi_w[k]; }
-    return t;
 }
 
 // blocks of one launch: planes x residue classes x tiles of the largest class x column tiles; 0 when that passes 2^31 - 1
@@ -262,7 +232,7 @@ extern "C" int faoctasr_swt2d_analysis(const float* x, long x_plane_stride, floa
     const long blocks = swt_blocks(NC, H, W, dilation, SA_TH, SA_TW, &tiles_h, &tiles_w);
     if (!blocks) return fail(FAOCTASR_EUNSUPPORTED, "swt2d_analysis: NC %ld H %d W %d needs more than 2^31 - 1 blocks", NC, H, W);
     hipLaunchKernelGGL(swt_analysis_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, x_plane_stride, y, H, W, dilation,
-                       tiles_h, tiles_w, L_h, L_w, mode, scale, swt_taps(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
+                       tiles_h, tiles_w, L_h, L_w, mode, scale, fb_taps2(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
     return check_launch("swt2d_analysis");
 }
 
@@ -279,6 +249,6 @@ extern "C" int faoctasr_swt2d_adjoint(const float* c, float* dx, long dx_plane_s
     const long blocks = swt_blocks(NC, H, W, dilation, SJ_TH, SJ_TW, &tiles_h, &tiles_w);
     if (!blocks) return fail(FAOCTASR_EUNSUPPORTED, "swt2d_adjoint: NC %ld H %d W %d needs more than 2^31 - 1 blocks", NC, H, W);
     hipLaunchKernelGGL(swt_adjoint_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, c, dx, dx_plane_stride, band0, band0_plane_stride, band0_replaces, H, W, dilation,
-                       tiles_h, tiles_w, L_h, L_w, mode, scale, swt_taps(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
+                       tiles_h, tiles_w, L_h, L_w, mode, scale, fb_taps2(lo_h, hi_h, L_h, lo_w, hi_w, L_w));
     return check_launch("swt2d_adjoint");
 }
