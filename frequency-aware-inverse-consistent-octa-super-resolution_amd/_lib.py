@@ -77,22 +77,14 @@ _SIG = {
     "dwt1d_synthesis": (_I, "p lll pp l p i i pp i i i p"),
     "swt2d_analysis": (_I, "p l p l ii ppi ppi i i f p"),
     "swt2d_adjoint": (_I, "pp l p l i l ii ppi ppi i i f p"),
-    "dtcwt_fwd_j1": (_I, "p lll pp llllll i l iii pi pi i p"),
-    "dtcwt_fwd_j2": (_I, "p lll pp llllll i l iii pppp i p"),
-    "dtcwt_inv_j1": (_I, "p lll p llllll p l iii pi pi i p"),
-    "dtcwt_inv_j2": (_I, "p lll p llllll p l iii pppp i p"),
-    "scat_fwd_j1": (_I, "p lll p ll i p lll p i ff l iii pi pi i p"),
-    "scat_fwd_j2": (_I, "p lll p ll p lll p i ff l iii pppp i p"),
-    "scat_bwd_j1": (_I, "p ll i p lll p p l iii pi pi i p"),
-    "scat_bwd_j2": (_I, "p ll p lll p p l iii pppp i p"),
-    "dtcwt_fwd_j1_bp": (_I, "p lll pp llllll i l iii pi pi pi i p"),
-    "dtcwt_fwd_j2_bp": (_I, "p lll pp llllll i l iii pppppp i p"),
-    "dtcwt_inv_j1_bp": (_I, "p lll p llllll p l iii pi pi pi i p"),
-    "dtcwt_inv_j2_bp": (_I, "p lll p llllll p l iii pppppp i p"),
-    "scat_fwd_j1_bp": (_I, "p lll p ll i p lll p i ff l iii pi pi pi i p"),
-    "scat_fwd_j2_bp": (_I, "p lll p ll p lll p i ff l iii pppppp i p"),
-    "scat_bwd_j1_bp": (_I, "p ll i p lll p p l iii pi pi pi i p"),
-    "scat_bwd_j2_bp": (_I, "p ll p lll p p l iii pppppp i p"),
+    "dtcwt_fwd_j1": (_I, "p lll pp llllll i l iii pi pi pi i p"),
+    "dtcwt_fwd_j2": (_I, "p lll pp llllll i l iii pppppp i p"),
+    "dtcwt_inv_j1": (_I, "p lll p llllll p l iii pi pi pi i p"),
+    "dtcwt_inv_j2": (_I, "p lll p llllll p l iii pppppp i p"),
+    "scat_fwd_j1": (_I, "p lll p ll i p lll p i ff l iii pi pi pi i p"),
+    "scat_fwd_j2": (_I, "p lll p ll p lll p i ff l iii pppppp i p"),
+    "scat_bwd_j1": (_I, "p ll i p lll p p l iii pi pi pi i p"),
+    "scat_bwd_j2": (_I, "p ll p lll p p l iii pppppp i p"),
     "dtcwt_loss_workspace_floats": (_L, "l iii i"),
     "dtcwt_loss_fwd_j1": (_I, "p lll p lll pp pp p ff l iii pi pi i p"),
     "dtcwt_loss_fwd_j2": (_I, "p lll p lll pp pp p ff l iii pppp i p"),

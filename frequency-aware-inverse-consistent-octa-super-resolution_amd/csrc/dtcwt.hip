@@ -21,8 +21,9 @@
 //   depend on the parity of m/2 and on whether the call is a lowpass or a highpass one (lowlevel.py:154-239; the host builds
 //   the table, dtcwt_ifilt_taps below).
 //
-// Three-filter ("_bp", rotationally symmetric) banks: the diagonal band hh has a bandpass filter h2 of its own on both axes
-// (transform_funcs.py fwd_j1_rot, fwd_j2plus_rot, inv_j1_rot, inv_j2plus_rot); every kernel has a compile-time form BP for them.
+// Three-filter (rotationally symmetric) banks, the entry points' optional third filter: the diagonal band hh has a bandpass filter
+// h2 of its own on both axes (transform_funcs.py fwd_j1_rot, fwd_j2plus_rot, inv_j1_rot, inv_j2plus_rot); every kernel has a
+// compile-time form BP for them, which a non-NULL third filter selects.
 //   forward:  ba = row(x, h2),  hh = col(ba, h2);  ll, lh, hl as above.  Level 1: h2 has an odd length of its own (the halo is the
 //     largest half-length of the three).  Level >= 2: (h2b, h2a) is a highpass call, with the index formula of (h1b, h1a).
 //   inverse:  lo = col(lh, g1) + col(ll, g0),  hi = col(hl, g0),  ba = col(hh, g2);   y = (row(hi, g1) + row(lo, g0)) + row(ba, g2),
@@ -160,7 +161,7 @@ __global__ __launch_bounds__(256) void dtcwt_inv_j2(const float* __restrict__ ll
 
 using namespace faoctasr;
 
-// The entry points of a kernel's two forms share everything but the taps: run_* takes them checked and packed.
+// The launches: run_* takes the taps of its form (BP: with the third filter) checked and packed.
 template <bool BP>
 static int run_fwd_j1(const char* what, const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                       long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W, int L0, int L1,
@@ -174,7 +175,7 @@ static int run_fwd_j1(const char* what, const float* x, long x_sn, long x_sc, lo
     const DtLow xs{x_sn, x_sc, x_sr};
     const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
     if constexpr (BP) {
-        if (!hi) return fail(FAOCTASR_EINVAL, "%s: the lowpass alone takes no third filter, call dtcwt_fwd_j1", what);
+        if (!hi) return fail(FAOCTASR_EINVAL, "%s: the lowpass alone takes no third filter, pass a NULL third filter", what);
         hipLaunchKernelGGL((dtcwt_fwd_j1<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C,
                            H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
     } else if (hi) {
@@ -199,7 +200,7 @@ static int run_fwd_j2(const char* what, const float* x, long x_sn, long x_sc, lo
     const DtLow xs{x_sn, x_sc, x_sr};
     const DtStr hs{hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si};
     if constexpr (BP) {
-        if (!hi) return fail(FAOCTASR_EINVAL, "%s: the lowpass alone takes no third filter, call dtcwt_fwd_j2", what);
+        if (!hi) return fail(FAOCTASR_EINVAL, "%s: the lowpass alone takes no third filter, pass a NULL third filter", what);
         hipLaunchKernelGGL((dtcwt_fwd_j2<true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, xs, ll, hi, hs, hi_vec2, C,
                            H, W, tiles_h, tiles_w, m, t);
     } else if (hi) {
@@ -241,93 +242,47 @@ static int run_inv_j2(const char* what, const float* ll, long ll_sn, long ll_sc,
     return check_launch(what);
 }
 
+// The entry points: the tap arguments, checked and packed by dt_with_taps*, pick the form of the launch.
 extern "C" int faoctasr_dtcwt_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                                     const float* h0, int L0, const float* h1, int L1, int mode, faoctasr_stream_t stream) {
-    DtTaps1 t;
-    const int rc = dt_taps1("dtcwt_fwd_j1", h0, L0, h1, L1, &t);
-    if (rc) return rc;
-    return run_fwd_j1<false>("dtcwt_fwd_j1", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, L0, L1, t,
-                             mode, stream);
-}
-
-extern "C" int faoctasr_dtcwt_fwd_j1_bp(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
-                                        long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                                        const float* h0, int L0, const float* h1, int L1, const float* h2, int L2, int mode,
-                                        faoctasr_stream_t stream) {
-    DtTaps1R t;
-    const int rc = dt_taps1r("dtcwt_fwd_j1_bp", h0, L0, h1, L1, h2, L2, &t);
-    if (rc) return rc;
-    return run_fwd_j1<true>("dtcwt_fwd_j1_bp", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, L0, L1,
-                            t, mode, stream);
+                                     const float* h0, int L0, const float* h1, int L1, const float* h2, int L2, int mode,
+                                     faoctasr_stream_t stream) {
+    const char* what = "dtcwt_fwd_j1";
+    return dt_with_taps1(what, h0, L0, h1, L1, h2, L2, [&](auto bp, const auto& t) {
+        return run_fwd_j1<decltype(bp)::value>(what, x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, L0,
+                                               L1, t, mode, stream);
+    });
 }
 
 extern "C" int faoctasr_dtcwt_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                                     const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
-                                     faoctasr_stream_t stream) {
-    const int rc = dt_taps2_check("dtcwt_fwd_j2", h0a, h0b, h1a, h1b, m);
-    if (rc) return rc;
-    DtTaps2 t = {};
-    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, m);
-    return run_fwd_j2<false>("dtcwt_fwd_j2", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, m, t,
-                             stream);
-}
-
-extern "C" int faoctasr_dtcwt_fwd_j2_bp(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
-                                        long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                                        const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
-                                        const float* h2b, int m, faoctasr_stream_t stream) {
-    const int rc = dt_taps2r_check("dtcwt_fwd_j2_bp", h0a, h0b, h1a, h1b, h2a, h2b, m);
-    if (rc) return rc;
-    DtTaps2R t = {};
-    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, h2a, h2b, m);
-    return run_fwd_j2<true>("dtcwt_fwd_j2_bp", x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, m, t,
-                            stream);
+                                     const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                                     const float* h2b, int m, faoctasr_stream_t stream) {
+    const char* what = "dtcwt_fwd_j2";
+    return dt_with_taps2(what, h0a, h0b, h1a, h1b, h2a, h2b, m, [&](auto bp, const auto& t) {
+        return run_fwd_j2<decltype(bp)::value>(what, x, x_sn, x_sc, x_sr, ll, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, hi_vec2, N, C, H, W, m,
+                                               t, stream);
+    });
 }
 
 extern "C" int faoctasr_dtcwt_inv_j1(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                                     const float* g0, int L0, const float* g1, int L1, int mode, faoctasr_stream_t stream) {
-    DtTaps1 t;
-    const int rc = dt_taps1("dtcwt_inv_j1", g0, L0, g1, L1, &t);
-    if (rc) return rc;
-    return run_inv_j1<false>("dtcwt_inv_j1", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, L0, L1, t, mode,
-                             stream);
-}
-
-extern "C" int faoctasr_dtcwt_inv_j1_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
-                                        long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                                        const float* g0, int L0, const float* g1, int L1, const float* g2, int L2, int mode,
-                                        faoctasr_stream_t stream) {
-    DtTaps1R t;
-    const int rc = dt_taps1r("dtcwt_inv_j1_bp", g0, L0, g1, L1, g2, L2, &t);
-    if (rc) return rc;
-    return run_inv_j1<true>("dtcwt_inv_j1_bp", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, L0, L1, t,
-                            mode, stream);
+                                     const float* g0, int L0, const float* g1, int L1, const float* g2, int L2, int mode,
+                                     faoctasr_stream_t stream) {
+    const char* what = "dtcwt_inv_j1";
+    return dt_with_taps1(what, g0, L0, g1, L1, g2, L2, [&](auto bp, const auto& t) {
+        return run_inv_j1<decltype(bp)::value>(what, ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, L0, L1, t,
+                                               mode, stream);
+    });
 }
 
 extern "C" int faoctasr_dtcwt_inv_j2(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
                                      long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                                     const float* g0a, const float* g0b, const float* g1a, const float* g1b, int m,
-                                     faoctasr_stream_t stream) {
-    const int rc = dt_taps2_check("dtcwt_inv_j2", g0a, g0b, g1a, g1b, m);
-    if (rc) return rc;
-    DtTapsI t = {};
-    dtcwt_ifilt_taps(g0b, g0a, m, 0, t.lo, t.dlo);                        // colifilt(X, g0b, g0a, False)
-    dtcwt_ifilt_taps(g1b, g1a, m, 1, t.hi, t.dhi);                        // colifilt(X, g1b, g1a, True)
-    return run_inv_j2<false>("dtcwt_inv_j2", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, m, t, stream);
-}
-
-extern "C" int faoctasr_dtcwt_inv_j2_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
-                                        long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                                        const float* g0a, const float* g0b, const float* g1a, const float* g1b, const float* g2a,
-                                        const float* g2b, int m, faoctasr_stream_t stream) {
-    const int rc = dt_taps2r_check("dtcwt_inv_j2_bp", g0a, g0b, g1a, g1b, g2a, g2b, m);
-    if (rc) return rc;
-    DtTapsIR t = {};
-    dtcwt_ifilt_taps(g0b, g0a, m, 0, t.lo, t.dlo);                        // colifilt(X, g0b, g0a, False)
-    dtcwt_ifilt_taps(g1b, g1a, m, 1, t.hi, t.dhi);                        // colifilt(X, g1b, g1a, True)
-    dtcwt_ifilt_taps(g2b, g2a, m, 1, t.ba, t.dba);                        // colifilt(X, g2b, g2a, True)
-    return run_inv_j2<true>("dtcwt_inv_j2_bp", ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, m, t, stream);
+                                     const float* g0a, const float* g0b, const float* g1a, const float* g1b, const float* g2a,
+                                     const float* g2b, int m, faoctasr_stream_t stream) {
+    const char* what = "dtcwt_inv_j2";
+    return dt_with_tapsi(what, g0a, g0b, g1a, g1b, g2a, g2b, m, [&](auto bp, const auto& t) {
+        return run_inv_j2<decltype(bp)::value>(what, ll, ll_sn, ll_sc, ll_sr, hi, hi_sn, hi_sc, hi_so, hi_sr, hi_sw, hi_si, y, N, C, H, W, m, t,
+                                               stream);
+    });
 }

@@ -17,7 +17,7 @@ struct DtLow { long n, c, r; };                  // lowpass input element stride
 struct DtTaps1 { float f0[DT_MAXL], f1[DT_MAXL]; };                      // level 1: lowpass, highpass
 struct DtTaps2 { float lo0[DT_MAXL], lo1[DT_MAXL], hi0[DT_MAXL], hi1[DT_MAXL]; };   // level >= 2 analysis, by output phase
 struct DtTapsI { float lo[4][DT_MAXL / 2], hi[4][DT_MAXL / 2]; int dlo[4], dhi[4]; };   // level >= 2 synthesis, by output phase q
-// the three-filter (rotationally symmetric, "_bp") banks: the two-filter taps and the bandpass filter of the diagonal band hh
+// the three-filter (rotationally symmetric) banks, an entry point's optional third filter: the two-filter taps and the bandpass filter of the diagonal band hh
 struct DtTaps1R : DtTaps1 { float f2[DT_MAXL]; int L2; };               // level 1: + bandpass, of its own odd length
 struct DtTaps2R : DtTaps2 { float ba0[DT_MAXL], ba1[DT_MAXL]; };        // level >= 2 analysis: + the bandpass pair, phased as hi0, hi1
 struct DtTapsIR : DtTapsI { float ba[4][DT_MAXL / 2]; int dba[4]; };    // level >= 2 synthesis: + a third (highpass-call) table
@@ -427,51 +427,46 @@ inline int dt_blocks(const char* what, long N, int C, int tiles_h, int tiles_w, 
     return FAOCTASR_OK;
 }
 
-inline int dt_taps1(const char* what, const float* f0, int L0, const float* f1, int L1, DtTaps1* t) {
+// The tap arguments of an entry point.  The third filter is optional -- NULL selects the two-filter form --; dt_with_taps* check
+// the arguments, pack them once and hand run(form, taps) the struct of the form: (std::false_type, DtTaps1 / DtTaps2 / DtTapsI) or
+// (std::true_type, DtTaps1R / DtTaps2R / DtTapsIR), the base part of the one packed struct or all of it.  Nothing here calls HIP.
+template <class Run>
+inline int dt_with_taps1(const char* what, const float* f0, int L0, const float* f1, int L1, const float* f2, int L2, Run run) {
     if (!f0 || !f1) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
     if (L0 < 3 || L0 >= DT_MAXL || !(L0 & 1) || L1 < 3 || L1 >= DT_MAXL || !(L1 & 1))
         return fail(FAOCTASR_EINVAL, "%s: level-1 tap counts %d and %d must be odd and within 3..%d", what, L0, L1, DT_MAXL - 1);
-    *t = DtTaps1{};
-    for (int k = 0; k < L0; ++k) t->f0[k] = f0[k];
-    for (int k = 0; k < L1; ++k) t->f1[k] = f1[k];
-    return FAOCTASR_OK;
-}
-
-// the third level-1 filter joins a checked two-filter set
-inline int dt_taps1r(const char* what, const float* f0, int L0, const float* f1, int L1, const float* f2, int L2, DtTaps1R* t) {
-    DtTaps1 two;
-    const int rc = dt_taps1(what, f0, L0, f1, L1, &two);
-    if (rc) return rc;
-    if (!f2) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
-    if (L2 < 3 || L2 >= DT_MAXL || !(L2 & 1))
+    if (!f2 && L2 != 0) return fail(FAOCTASR_EINVAL, "%s: a NULL third filter takes the tap count 0, got %d", what, L2);
+    if (f2 && (L2 < 3 || L2 >= DT_MAXL || !(L2 & 1)))
         return fail(FAOCTASR_EINVAL, "%s: level-1 third-filter tap count %d must be odd and within 3..%d", what, L2, DT_MAXL - 1);
-    *t = DtTaps1R{};
-    static_cast<DtTaps1&>(*t) = two;
-    for (int k = 0; k < L2; ++k) t->f2[k] = f2[k];
-    t->L2 = L2;
-    return FAOCTASR_OK;
+    DtTaps1R t = {};
+    for (int k = 0; k < L0; ++k) t.f0[k] = f0[k];
+    for (int k = 0; k < L1; ++k) t.f1[k] = f1[k];
+    if (!f2) return run(std::false_type{}, static_cast<const DtTaps1&>(t));
+    for (int k = 0; k < L2; ++k) t.f2[k] = f2[k];
+    t.L2 = L2;
+    return run(std::true_type{}, t);
 }
 
-inline int dt_taps2_check(const char* what, const float* a, const float* b, const float* c, const float* d, int m) {
-    if (!a || !b || !c || !d) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
+// the q-shift taps of both level >= 2 kinds: tree a and tree b of the lowpass, the highpass and the optional third pair
+inline int dt_taps2_check(const char* what, const float* a0, const float* b0, const float* a1, const float* b1, const float* a2,
+                          const float* b2, int m) {
+    if (!a0 || !b0 || !a1 || !b1) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
     if (m < 4 || m > DT_MAXL || (m & 1)) return fail(FAOCTASR_EINVAL, "%s: q-shift tap count %d must be even and within 4..%d", what, m, DT_MAXL);
+    if (!a2 != !b2) return fail(FAOCTASR_EINVAL, "%s: the third filter pair (a2, b2) takes both pointers or two NULLs, got one", what);
     return FAOCTASR_OK;
-}
-
-inline int dt_taps2r_check(const char* what, const float* a, const float* b, const float* c, const float* d, const float* e, const float* f,
-                           int m) {
-    if (!e || !f) return fail(FAOCTASR_EINVAL, "%s: null tap pointer", what);
-    return dt_taps2_check(what, a, b, c, d, m);
 }
 
 // analysis taps by output phase: the lowpass call reads (h0b, h0a), the highpass calls (h1a, h1b) and (h2a, h2b)
-inline void dt_taps2_fill(DtTaps2* t, const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m) {
-    for (int k = 0; k < m; ++k) { t->lo0[k] = h0b[k]; t->lo1[k] = h0a[k]; t->hi0[k] = h1a[k]; t->hi1[k] = h1b[k]; }
-}
-inline void dt_taps2_fill(DtTaps2R* t, const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
-                          const float* h2b, int m) {
-    dt_taps2_fill(static_cast<DtTaps2*>(t), h0a, h0b, h1a, h1b, m);
-    for (int k = 0; k < m; ++k) { t->ba0[k] = h2a[k]; t->ba1[k] = h2b[k]; }
+template <class Run>
+inline int dt_with_taps2(const char* what, const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                         const float* h2b, int m, Run run) {
+    const int rc = dt_taps2_check(what, h0a, h0b, h1a, h1b, h2a, h2b, m);
+    if (rc) return rc;
+    DtTaps2R t = {};
+    for (int k = 0; k < m; ++k) { t.lo0[k] = h0b[k]; t.lo1[k] = h0a[k]; t.hi0[k] = h1a[k]; t.hi1[k] = h1b[k]; }
+    if (!h2a) return run(std::false_type{}, static_cast<const DtTaps2&>(t));
+    for (int k = 0; k < m; ++k) { t.ba0[k] = h2a[k]; t.ba1[k] = h2b[k]; }
+    return run(std::true_type{}, t);
 }
 
 // the table of lowlevel.py:154-239: per output phase q the polyphase half and offset of colifilt(X, fa, fb, highpass)
@@ -486,6 +481,20 @@ inline void dtcwt_ifilt_taps(const float* fa, const float* fb, int m, int highpa
         for (int t = 0; t < DT_MAXL / 2; ++t) out[q][t] = t < m2 ? f[2 * t + tab[q][1]] : 0.f;
         d[q] = tab[q][2];
     }
+}
+
+// synthesis tables: colifilt(X, g0b, g0a, False), colifilt(X, g1b, g1a, True) and, for hh, colifilt(X, g2b, g2a, True)
+template <class Run>
+inline int dt_with_tapsi(const char* what, const float* g0a, const float* g0b, const float* g1a, const float* g1b, const float* g2a,
+                         const float* g2b, int m, Run run) {
+    const int rc = dt_taps2_check(what, g0a, g0b, g1a, g1b, g2a, g2b, m);
+    if (rc) return rc;
+    DtTapsIR t = {};
+    dtcwt_ifilt_taps(g0b, g0a, m, 0, t.lo, t.dlo);
+    dtcwt_ifilt_taps(g1b, g1a, m, 1, t.hi, t.dhi);
+    if (!g2a) return run(std::false_type{}, static_cast<const DtTapsI&>(t));
+    dtcwt_ifilt_taps(g2b, g2a, m, 1, t.ba, t.dba);
+    return run(std::true_type{}, t);
 }
 
 }  // namespace faoctasr

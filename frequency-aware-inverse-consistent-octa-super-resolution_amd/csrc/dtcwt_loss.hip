@@ -191,38 +191,35 @@ extern "C" int faoctasr_dtcwt_loss_fwd_j1(const float* x, long x_sn, long x_sc, 
                                           float* llx, float* lly, float* gx, float* gy, float* part, float scale, float bias2, long N,
                                           int C, int H, int W, const float* h0, int L0, const float* h1, int L1, int mode,
                                           faoctasr_stream_t stream) {
-    DtTaps1 t;
-    int rc = dt_taps1("dtcwt_loss_fwd_j1", h0, L0, h1, L1, &t);
-    if (rc) return rc;
-    if ((rc = dl_common("dtcwt_loss_fwd_j1", x, y, part, scale, bias2))) return rc;
-    if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_loss_fwd_j1: unknown padding mode %d", mode);
-    int tiles_h, tiles_w;
-    if ((rc = dt_tiles1("dtcwt_loss_fwd_j1", H, W, &tiles_h, &tiles_w))) return rc;
-    long blocks;
-    if ((rc = dt_blocks("dtcwt_loss_fwd_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
-    hipLaunchKernelGGL(dtcwt_loss_fwd_j1, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, DtLow{x_sn, x_sc, x_sr}, y,
-                       DtLow{y_sn, y_sc, y_sr}, llx, lly, reinterpret_cast<float2*>(gx), reinterpret_cast<float2*>(gy), part, scale, bias2, C,
-                       H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
-    return check_launch("dtcwt_loss_fwd_j1");
+    return dt_with_taps1("dtcwt_loss_fwd_j1", h0, L0, h1, L1, nullptr, 0, [&](auto, const DtTaps1& t) {       // two-filter banks only
+        int rc, tiles_h, tiles_w;
+        if ((rc = dl_common("dtcwt_loss_fwd_j1", x, y, part, scale, bias2))) return rc;
+        if (mode < 0 || mode > 6) return fail(FAOCTASR_EINVAL, "dtcwt_loss_fwd_j1: unknown padding mode %d", mode);
+        if ((rc = dt_tiles1("dtcwt_loss_fwd_j1", H, W, &tiles_h, &tiles_w))) return rc;
+        long blocks;
+        if ((rc = dt_blocks("dtcwt_loss_fwd_j1", N, C, tiles_h, tiles_w, &blocks))) return rc;
+        hipLaunchKernelGGL(dtcwt_loss_fwd_j1, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, DtLow{x_sn, x_sc, x_sr}, y,
+                           DtLow{y_sn, y_sc, y_sr}, llx, lly, reinterpret_cast<float2*>(gx), reinterpret_cast<float2*>(gy), part, scale, bias2,
+                           C, H, W, tiles_h, tiles_w, L0, L1, mode == 1, t);
+        return check_launch("dtcwt_loss_fwd_j1");
+    });
 }
 
 extern "C" int faoctasr_dtcwt_loss_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, const float* y, long y_sn, long y_sc, long y_sr,
                                           float* llx, float* lly, float* gx, float* gy, float* part, float scale, float bias2, long N,
                                           int C, int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b,
                                           int m, faoctasr_stream_t stream) {
-    int rc = dt_taps2_check("dtcwt_loss_fwd_j2", h0a, h0b, h1a, h1b, m);
-    if (rc) return rc;
-    if ((rc = dl_common("dtcwt_loss_fwd_j2", x, y, part, scale, bias2))) return rc;
-    int tiles_h, tiles_w;
-    if ((rc = dt_tiles2f("dtcwt_loss_fwd_j2", H, W, &tiles_h, &tiles_w))) return rc;
-    long blocks;
-    if ((rc = dt_blocks("dtcwt_loss_fwd_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
-    DtTaps2 t = {};
-    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, m);
-    hipLaunchKernelGGL(dtcwt_loss_fwd_j2, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, DtLow{x_sn, x_sc, x_sr}, y,
-                       DtLow{y_sn, y_sc, y_sr}, llx, lly, reinterpret_cast<float2*>(gx), reinterpret_cast<float2*>(gy), part, scale, bias2, C,
-                       H, W, tiles_h, tiles_w, m, t);
-    return check_launch("dtcwt_loss_fwd_j2");
+    return dt_with_taps2("dtcwt_loss_fwd_j2", h0a, h0b, h1a, h1b, nullptr, nullptr, m, [&](auto, const DtTaps2& t) {
+        int rc, tiles_h, tiles_w;
+        if ((rc = dl_common("dtcwt_loss_fwd_j2", x, y, part, scale, bias2))) return rc;
+        if ((rc = dt_tiles2f("dtcwt_loss_fwd_j2", H, W, &tiles_h, &tiles_w))) return rc;
+        long blocks;
+        if ((rc = dt_blocks("dtcwt_loss_fwd_j2", N, C, tiles_h, tiles_w, &blocks))) return rc;
+        hipLaunchKernelGGL(dtcwt_loss_fwd_j2, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, DtLow{x_sn, x_sc, x_sr}, y,
+                           DtLow{y_sn, y_sc, y_sr}, llx, lly, reinterpret_cast<float2*>(gx), reinterpret_cast<float2*>(gy), part, scale, bias2,
+                           C, H, W, tiles_h, tiles_w, m, t);
+        return check_launch("dtcwt_loss_fwd_j2");
+    });
 }
 
 extern "C" int faoctasr_dtcwt_loss_final(const float* workspace, const long* level_floats, const double* level_scale, int levels, float* out,

@@ -15,7 +15,8 @@
 //   c2q applied to the pairs; the two filter passes are the inverse's, on the analysis taps (level 1) or on them with trees a and
 //   b swapped (level 2) -- the exact adjoint.  The colour form is a zero channel stride of dmag.
 //
-// Three-filter ("_bp") banks, ScatLayerj1_rot_f / ScatLayerj2_rot_f: every kernel passes its compile-time form BP on to the tile body --
+// Three-filter banks (an entry point's optional third filter), ScatLayerj1_rot_f / ScatLayerj2_rot_f: every kernel passes its
+// compile-time form BP on to the tile body --
 // forward  ba = row(x, h2), hh = col(ba, h2);  backward  hi = col(hl, h0), ba = col(hh, h2), dx = (row(hi, h1) + row(lo, h0)) + row(ba, h2)
 // -- and the pointwise part is the same for both.  The forwards loop over their channels around the body's barriers, so every thread
 // stays in the loop (`live` guards the quad); the backwards hand the body a stager (sc_stage) and have every input present.
@@ -226,7 +227,7 @@ static int sc_common(const char* what, const void* a, const void* b, const void*
 
 using namespace faoctasr;
 
-// The entry points of a kernel's two forms share everything but the taps: run_* takes them checked and packed.
+// The launches: run_* takes the taps of its form (BP: with the third filter) checked and packed.
 template <bool BP>
 static int run_fwd_j1(const char* what, const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, int pool,
                       float* mag, long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2, long N, int C,
@@ -300,92 +301,45 @@ static int run_bwd_j2(const char* what, const float* dlow, long dlow_sn, long dl
     return check_launch(what);
 }
 
+// The entry points: the tap arguments, checked and packed by dt_with_taps*, pick the form of the launch.
 extern "C" int faoctasr_scat_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, int pool,
                                     float* mag, long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2,
-                                    long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, int mode,
-                                    faoctasr_stream_t stream) {
-    DtTaps1 t;
-    const int rc = dt_taps1("scat_fwd_j1", h0, L0, h1, L1, &t);
-    if (rc) return rc;
-    return run_fwd_j1<false>("scat_fwd_j1", x, x_sn, x_sc, x_sr, low, low_sn, low_sc, pool, mag, mag_sn, mag_so, mag_sc, phase, colour, bias, bias2,
-                             N, C, H, W, L0, L1, t, mode, stream);
-}
-
-extern "C" int faoctasr_scat_fwd_j1_bp(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, int pool,
-                                       float* mag, long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2,
-                                       long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, const float* h2,
-                                       int L2, int mode, faoctasr_stream_t stream) {
-    DtTaps1R t;
-    const int rc = dt_taps1r("scat_fwd_j1_bp", h0, L0, h1, L1, h2, L2, &t);
-    if (rc) return rc;
-    return run_fwd_j1<true>("scat_fwd_j1_bp", x, x_sn, x_sc, x_sr, low, low_sn, low_sc, pool, mag, mag_sn, mag_so, mag_sc, phase, colour, bias,
-                            bias2, N, C, H, W, L0, L1, t, mode, stream);
+                                    long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, const float* h2, int L2,
+                                    int mode, faoctasr_stream_t stream) {
+    const char* what = "scat_fwd_j1";
+    return dt_with_taps1(what, h0, L0, h1, L1, h2, L2, [&](auto bp, const auto& t) {
+        return run_fwd_j1<decltype(bp)::value>(what, x, x_sn, x_sc, x_sr, low, low_sn, low_sc, pool, mag, mag_sn, mag_so, mag_sc, phase, colour, bias,
+                                               bias2, N, C, H, W, L0, L1, t, mode, stream);
+    });
 }
 
 extern "C" int faoctasr_scat_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, float* mag,
                                     long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2, long N, int C,
-                                    int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
-                                    faoctasr_stream_t stream) {
-    const int rc = dt_taps2_check("scat_fwd_j2", h0a, h0b, h1a, h1b, m);
-    if (rc) return rc;
-    DtTaps2 t = {};
-    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, m);
-    return run_fwd_j2<false>("scat_fwd_j2", x, x_sn, x_sc, x_sr, low, low_sn, low_sc, mag, mag_sn, mag_so, mag_sc, phase, colour, bias, bias2, N, C,
-                             H, W, m, t, stream);
-}
-
-extern "C" int faoctasr_scat_fwd_j2_bp(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, float* mag,
-                                       long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2, long N,
-                                       int C, int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b,
-                                       const float* h2a, const float* h2b, int m, faoctasr_stream_t stream) {
-    const int rc = dt_taps2r_check("scat_fwd_j2_bp", h0a, h0b, h1a, h1b, h2a, h2b, m);
-    if (rc) return rc;
-    DtTaps2R t = {};
-    dt_taps2_fill(&t, h0a, h0b, h1a, h1b, h2a, h2b, m);
-    return run_fwd_j2<true>("scat_fwd_j2_bp", x, x_sn, x_sc, x_sr, low, low_sn, low_sc, mag, mag_sn, mag_so, mag_sc, phase, colour, bias, bias2, N,
-                            C, H, W, m, t, stream);
+                                    int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                                    const float* h2b, int m, faoctasr_stream_t stream) {
+    const char* what = "scat_fwd_j2";
+    return dt_with_taps2(what, h0a, h0b, h1a, h1b, h2a, h2b, m, [&](auto bp, const auto& t) {
+        return run_fwd_j2<decltype(bp)::value>(what, x, x_sn, x_sc, x_sr, low, low_sn, low_sc, mag, mag_sn, mag_so, mag_sc, phase, colour, bias, bias2,
+                                               N, C, H, W, m, t, stream);
+    });
 }
 
 extern "C" int faoctasr_scat_bwd_j1(const float* dlow, long dlow_sn, long dlow_sc, int pool, const float* dmag, long dmag_sn, long dmag_so,
                                     long dmag_sc, const float* phase, float* dx, long N, int C, int H, int W, const float* h0, int L0,
-                                    const float* h1, int L1, int mode, faoctasr_stream_t stream) {
-    DtTaps1 t;
-    const int rc = dt_taps1("scat_bwd_j1", h0, L0, h1, L1, &t);
-    if (rc) return rc;
-    return run_bwd_j1<false>("scat_bwd_j1", dlow, dlow_sn, dlow_sc, pool, dmag, dmag_sn, dmag_so, dmag_sc, phase, dx, N, C, H, W, L0, L1, t, mode,
-                             stream);
+                                    const float* h1, int L1, const float* h2, int L2, int mode, faoctasr_stream_t stream) {
+    const char* what = "scat_bwd_j1";
+    return dt_with_taps1(what, h0, L0, h1, L1, h2, L2, [&](auto bp, const auto& t) {
+        return run_bwd_j1<decltype(bp)::value>(what, dlow, dlow_sn, dlow_sc, pool, dmag, dmag_sn, dmag_so, dmag_sc, phase, dx, N, C, H, W, L0, L1, t,
+                                               mode, stream);
+    });
 }
 
-extern "C" int faoctasr_scat_bwd_j1_bp(const float* dlow, long dlow_sn, long dlow_sc, int pool, const float* dmag, long dmag_sn, long dmag_so,
-                                       long dmag_sc, const float* phase, float* dx, long N, int C, int H, int W, const float* h0, int L0,
-                                       const float* h1, int L1, const float* h2, int L2, int mode, faoctasr_stream_t stream) {
-    DtTaps1R t;
-    const int rc = dt_taps1r("scat_bwd_j1_bp", h0, L0, h1, L1, h2, L2, &t);
-    if (rc) return rc;
-    return run_bwd_j1<true>("scat_bwd_j1_bp", dlow, dlow_sn, dlow_sc, pool, dmag, dmag_sn, dmag_so, dmag_sc, phase, dx, N, C, H, W, L0, L1, t, mode,
-                            stream);
-}
-
+// the inverse on the forward's analysis taps with the trees swapped: g0a = h0b, g0b = h0a, and so for the other two pairs
 extern "C" int faoctasr_scat_bwd_j2(const float* dlow, long dlow_sn, long dlow_sc, const float* dmag, long dmag_sn, long dmag_so, long dmag_sc,
                                     const float* phase, float* dx, long N, int C, int H, int W, const float* h0a, const float* h0b,
-                                    const float* h1a, const float* h1b, int m, faoctasr_stream_t stream) {
-    const int rc = dt_taps2_check("scat_bwd_j2", h0a, h0b, h1a, h1b, m);
-    if (rc) return rc;
-    DtTapsI t = {};
-    dtcwt_ifilt_taps(h0a, h0b, m, 0, t.lo, t.dlo);                        // the inverse on g0a = h0b, g0b = h0a: colifilt(X, g0b, g0a, False)
-    dtcwt_ifilt_taps(h1a, h1b, m, 1, t.hi, t.dhi);                        // g1a = h1b, g1b = h1a: colifilt(X, g1b, g1a, True)
-    return run_bwd_j2<false>("scat_bwd_j2", dlow, dlow_sn, dlow_sc, dmag, dmag_sn, dmag_so, dmag_sc, phase, dx, N, C, H, W, m, t, stream);
-}
-
-extern "C" int faoctasr_scat_bwd_j2_bp(const float* dlow, long dlow_sn, long dlow_sc, const float* dmag, long dmag_sn, long dmag_so,
-                                       long dmag_sc, const float* phase, float* dx, long N, int C, int H, int W, const float* h0a,
-                                       const float* h0b, const float* h1a, const float* h1b, const float* h2a, const float* h2b, int m,
-                                       faoctasr_stream_t stream) {
-    const int rc = dt_taps2r_check("scat_bwd_j2_bp", h0a, h0b, h1a, h1b, h2a, h2b, m);
-    if (rc) return rc;
-    DtTapsIR t = {};
-    dtcwt_ifilt_taps(h0a, h0b, m, 0, t.lo, t.dlo);                        // the inverse on g0a = h0b, g0b = h0a: colifilt(X, g0b, g0a, False)
-    dtcwt_ifilt_taps(h1a, h1b, m, 1, t.hi, t.dhi);                        // g1a = h1b, g1b = h1a: colifilt(X, g1b, g1a, True)
-    dtcwt_ifilt_taps(h2a, h2b, m, 1, t.ba, t.dba);                        // g2a = h2b, g2b = h2a: colifilt(X, g2b, g2a, True)
-    return run_bwd_j2<true>("scat_bwd_j2_bp", dlow, dlow_sn, dlow_sc, dmag, dmag_sn, dmag_so, dmag_sc, phase, dx, N, C, H, W, m, t, stream);
+                                    const float* h1a, const float* h1b, const float* h2a, const float* h2b, int m, faoctasr_stream_t stream) {
+    const char* what = "scat_bwd_j2";
+    return dt_with_tapsi(what, h0b, h0a, h1b, h1a, h2b, h2a, m, [&](auto bp, const auto& t) {
+        return run_bwd_j2<decltype(bp)::value>(what, dlow, dlow_sn, dlow_sc, dmag, dmag_sn, dmag_so, dmag_sc, phase, dx, N, C, H, W, m, t, stream);
+    });
 }

@@ -1415,13 +1415,13 @@ def _dtcwt_taps2(fa0, fb0, fa1, fb1, fa2=None, fb2=None):
 
 
 def _taps1_args(taps):
-    """(pointer, length) of every level-1 filter, as the entry points take them."""
-    return tuple(a for t in taps for a in (_tap_array(t), len(t)))
+    """(pointer, length) of the three level-1 filters, as the entry points take them: (NULL, 0) for the third of a two-filter bank."""
+    return tuple(a for t in taps for a in (_tap_array(t), len(t))) + (None, 0) * (3 - len(taps))
 
 
-def _bp(name, taps, level1):
-    """The entry point of a launch: the ``_bp`` twin where the taps carry a third filter."""
-    return name + "_bp" if len(taps) == (3 if level1 else 6) else name
+def _taps2_args(taps):
+    """The six q-shift tap pointers and their length, as the entry points take them: two NULLs for the third pair of a two-filter bank."""
+    return tuple(_tap_array(t) for t in taps) + (None,) * (6 - len(taps)) + (len(taps[0]),)
 
 
 def _dtcwt_dev(t, what):
@@ -1478,14 +1478,12 @@ def _dtcwt_forward(x, taps, level1, mode, names, want_ll=True, want_hi=True):
         size = {"n": N, "c": C, "o": 6, "h": lh // 2, "w": lw // 2, "r": 2}
         hi = torch.empty(tuple(size[k] for k in names), dtype=torch.float32, device=x.device)
         st, vec = _dtcwt_high_strides(hi, names)
-    if not want_hi:                         # the lowpass of a three-filter bank is the two-filter one: the existing entry
+    if not want_hi:                         # the lowpass of a three-filter bank is the two-filter one: no third filter
         taps = taps[:2] if level1 else taps[:4]
     if level1:
-        call(_bp("dtcwt_fwd_j1", taps, True), x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, *_taps1_args(taps), mode,
-             stream_ptr())
+        call("dtcwt_fwd_j1", x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, *_taps1_args(taps), mode, stream_ptr())
     else:
-        call(_bp("dtcwt_fwd_j2", taps, False), x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W,
-             *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+        call("dtcwt_fwd_j2", x.data_ptr(), sn, sc, sr, ptr(ll), ptr(hi), *st, vec, N, C, H, W, *_taps2_args(taps), stream_ptr())
     return ll, hi
 
 
@@ -1516,10 +1514,9 @@ def _dtcwt_inverse(ll, hi, taps, level1, mode, names):
     y = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
     lp, hp = (ll.data_ptr() if ll is not None else None), (hi.data_ptr() if hi is not None else None)
     if level1:
-        call(_bp("dtcwt_inv_j1", taps, True), lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *_taps1_args(taps), mode, stream_ptr())
+        call("dtcwt_inv_j1", lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *_taps1_args(taps), mode, stream_ptr())
     else:
-        call(_bp("dtcwt_inv_j2", taps, False), lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]),
-             stream_ptr())
+        call("dtcwt_inv_j2", lp, sn, sc, sr, hp, *st, ptr(y), N, C, H, W, *_taps2_args(taps), stream_ptr())
     return y
 
 
@@ -2012,11 +2009,11 @@ def _scat_fwd(x, taps, level1, mode, bias, low, pool, mag, phase, colour):
     x, sn, sc, sr = _dtcwt_low(x)
     b = float(bias)
     if level1:
-        call(_bp("scat_fwd_j1", taps, True), x.data_ptr(), sn, sc, sr, *_scat_low(low), int(pool), *_scat_mag(mag, colour), ptr(phase),
+        call("scat_fwd_j1", x.data_ptr(), sn, sc, sr, *_scat_low(low), int(pool), *_scat_mag(mag, colour), ptr(phase),
              int(colour), b, b * b, N, C, H, W, *_taps1_args(taps), mode, stream_ptr())
     else:
-        call(_bp("scat_fwd_j2", taps, False), x.data_ptr(), sn, sc, sr, *_scat_low(low), *_scat_mag(mag, colour), ptr(phase), int(colour), b,
-             b * b, N, C, H, W, *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+        call("scat_fwd_j2", x.data_ptr(), sn, sc, sr, *_scat_low(low), *_scat_mag(mag, colour), ptr(phase), int(colour), b,
+             b * b, N, C, H, W, *_taps2_args(taps), stream_ptr())
 
 
 def _scat_bwd(dlow, pool, dmag, phase, taps, level1, mode, colour, shape):
@@ -2024,11 +2021,10 @@ def _scat_bwd(dlow, pool, dmag, phase, taps, level1, mode, colour, shape):
     N, C, H, W = shape
     dx = torch.empty(shape, dtype=torch.float32, device=phase.device)
     if level1:
-        call(_bp("scat_bwd_j1", taps, True), *_scat_low(dlow), int(pool), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W,
+        call("scat_bwd_j1", *_scat_low(dlow), int(pool), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W,
              *_taps1_args(taps), mode, stream_ptr())
     else:
-        call(_bp("scat_bwd_j2", taps, False), *_scat_low(dlow), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W,
-             *(_tap_array(t) for t in taps), len(taps[0]), stream_ptr())
+        call("scat_bwd_j2", *_scat_low(dlow), *_scat_mag(dmag, colour), ptr(phase), ptr(dx), N, C, H, W, *_taps2_args(taps), stream_ptr())
     return dx
 
 

@@ -577,7 +577,7 @@ class DTCWTForward(_TapModule):
     (h0a, h0b, h1a, h1b) of one even length 4..``ops.DTCWT_MAX_TAPS``.  A 3-tuple (h0o, h1o, h2o) with a 6-tuple (h0a, h0b, h1a, h1b,
     h2a, h2b) is a rotationally symmetric three-filter bank (the reference's near_sym_b_bp / qshift_b_bp, whose names stay refused
     for want of their tables): the diagonal bands take the bandpass filters h2 on both axes, the buffers ``h2o, h2a, h2b`` follow the
-    six, ``bandpass_diag`` is True and the launches are the ``_bp`` entry points of csrc/dtcwt.hip.  ``mode`` acts on level 1 only: 'symmetric', or zero padding
+    six, ``bandpass_diag`` is True and the launches pass the third filter to the entry points of csrc/dtcwt.hip.  ``mode`` acts on level 1 only: 'symmetric', or zero padding
     for any other name; the later levels always extend symmetrically.  An odd side has its last row / column repeated; a lowpass
     side that is no multiple of 4 has its first and last row / column repeated before the next level (torch ops outside the
     kernels -- the sizes 192, 256, 512 never take them up to J = 3).  Otherwise a forward is J launches of csrc/dtcwt.hip."""

@@ -413,44 +413,30 @@ int faoctasr_swt2d_adjoint(const float* c, float* dx, long dx_plane_stride, cons
  * inv_j1: ll [H, W], hi [H/2, W/2] -> y [H, W]; ll or hi may be NULL (zeros; its path is not computed).  Also the backward of
  *   fwd_j1 (on the analysis taps).
  * inv_j2: ll [H/2, W/2], hi [H/4, W/4] -> y [H, W], multiples of 4; ll or hi may be NULL.  Also the backward of fwd_j2 (on the
- *   analysis taps with a and b swapped). */
+ *   analysis taps with a and b swapped).
+ * The optional third filter: the rotationally symmetric three-filter banks (near_sym_b_bp / qshift_b_bp; fwd_j1_rot, fwd_j2plus_rot,
+ * inv_j1_rot, inv_j2plus_rot) filter the diagonal band hh by a bandpass filter of its own on both axes -- forward
+ * hh = col(row(x, h2), h2); inverse y = row(col(hl, g0), g1) + row(col(lh, g1) + col(ll, g0), g0) + row(col(hh, g2), g2).  Level 1:
+ * h2 / g2 of L2 taps, odd and 3..19 like the other two and of its own length; NULL with L2 = 0 is the two-filter bank.  Levels >= 2: a
+ * third pair (h2a, h2b) of the same even length m, used as the highpass pair is (and swapped with the other two in a backward); both
+ * NULL is the two-filter bank, one NULL is FAOCTASR_EINVAL.  Every other argument, rule and error code is the same in both forms; a
+ * forward call with a third filter needs hi (the lowpass alone has none: pass a NULL third filter, else FAOCTASR_EINVAL). */
 int faoctasr_dtcwt_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                           long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                          const float* h0, int L0, const float* h1, int L1, int mode, faoctasr_stream_t stream);
+                          const float* h0, int L0, const float* h1, int L1, const float* h2, int L2, int mode,
+                          faoctasr_stream_t stream);
 int faoctasr_dtcwt_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
                           long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                          const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
-                          faoctasr_stream_t stream);
+                          const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                          const float* h2b, int m, faoctasr_stream_t stream);
 int faoctasr_dtcwt_inv_j1(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
                           long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                          const float* g0, int L0, const float* g1, int L1, int mode, faoctasr_stream_t stream);
+                          const float* g0, int L0, const float* g1, int L1, const float* g2, int L2, int mode,
+                          faoctasr_stream_t stream);
 int faoctasr_dtcwt_inv_j2(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
                           long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                          const float* g0a, const float* g0b, const float* g1a, const float* g1b, int m,
-                          faoctasr_stream_t stream);
-/* The same four calls for the rotationally symmetric three-filter banks (near_sym_b_bp / qshift_b_bp; fwd_j1_rot, fwd_j2plus_rot,
- * inv_j1_rot, inv_j2plus_rot): the diagonal band hh is filtered by a bandpass filter of its own on both axes -- forward
- * hh = col(row(x, h2), h2); inverse y = row(col(hl, g0), g1) + row(col(lh, g1) + col(ll, g0), g0) + row(col(hh, g2), g2).  Level 1: a
- * third filter of L2 taps, odd and 3..19 like the other two and of its own length.  Levels >= 2: a third pair (h2a, h2b) of the same
- * even length m, used as the highpass pair is.  Every other argument, rule and error code is that of the call without the suffix;
- * the forward calls need hi (the lowpass alone has no third filter: FAOCTASR_EINVAL).  Each is the other's backward as above, the
- * pair (h2a, h2b) swapped with the other two at levels >= 2. */
-int faoctasr_dtcwt_fwd_j1_bp(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
-                             long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                             const float* h0, int L0, const float* h1, int L1, const float* h2, int L2, int mode,
-                             faoctasr_stream_t stream);
-int faoctasr_dtcwt_fwd_j2_bp(const float* x, long x_sn, long x_sc, long x_sr, float* ll, float* hi, long hi_sn, long hi_sc,
-                             long hi_so, long hi_sr, long hi_sw, long hi_si, int hi_vec2, long N, int C, int H, int W,
-                             const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
-                             const float* h2b, int m, faoctasr_stream_t stream);
-int faoctasr_dtcwt_inv_j1_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
-                             long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                             const float* g0, int L0, const float* g1, int L1, const float* g2, int L2, int mode,
-                             faoctasr_stream_t stream);
-int faoctasr_dtcwt_inv_j2_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr, const float* hi, long hi_sn, long hi_sc,
-                             long hi_so, long hi_sr, long hi_sw, long hi_si, float* y, long N, int C, int H, int W,
-                             const float* g0a, const float* g0b, const float* g1a, const float* g1b, const float* g2a,
-                             const float* g2b, int m, faoctasr_stream_t stream);
+                          const float* g0a, const float* g0b, const float* g1a, const float* g1b, const float* g2a,
+                          const float* g2b, int m, faoctasr_stream_t stream);
 
 /* ---- DTCWT scattering layers (csrc/scat.hip) ------------------------------------------------------
  * pytorch_wavelets scatternet/lowlevel.py (ScatLayerj1_f, ScatLayerj2_f): one dual-tree level, the smoothed magnitude
@@ -464,38 +450,23 @@ int faoctasr_dtcwt_inv_j2_bp(const float* ll, long ll_sn, long ll_sc, long ll_sr
  * phase == NULL: no phasors are stored (a forward without a backward).  colour = 1 (C must be 3): one magnitude per orientation
  *   over the three channels, sqrt(sum_c (re_c^2 + im_c^2) + bias^2) - bias (mag_sc is not used), phasors per channel.
  * bwd_j1, bwd_j2: the adjoints, on the SAME analysis taps as the forward call (bwd_j2 swaps trees a and b itself): dlow of the
- *   forward's low shape, dmag and phase of its mag and phase shapes -> dx [H, W].  The colour form is dmag_sc = 0. */
+ *   forward's low shape, dmag and phase of its mag and phase shapes -> dx [H, W].  The colour form is dmag_sc = 0.
+ * The optional third filter (ScatLayerj1_rot_f, ScatLayerj2_rot_f) is that of the dtcwt calls above, NULL for a two-filter bank;
+ * bwd_* takes the forward's analysis taps, the third included. */
 int faoctasr_scat_fwd_j1(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, int pool,
                          float* mag, long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2,
-                         long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, int mode,
-                         faoctasr_stream_t stream);
+                         long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, const float* h2, int L2,
+                         int mode, faoctasr_stream_t stream);
 int faoctasr_scat_fwd_j2(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, float* mag,
                          long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2, long N, int C,
-                         int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, int m,
-                         faoctasr_stream_t stream);
+                         int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
+                         const float* h2b, int m, faoctasr_stream_t stream);
 int faoctasr_scat_bwd_j1(const float* dlow, long dlow_sn, long dlow_sc, int pool, const float* dmag, long dmag_sn, long dmag_so,
                          long dmag_sc, const float* phase, float* dx, long N, int C, int H, int W, const float* h0, int L0,
-                         const float* h1, int L1, int mode, faoctasr_stream_t stream);
+                         const float* h1, int L1, const float* h2, int L2, int mode, faoctasr_stream_t stream);
 int faoctasr_scat_bwd_j2(const float* dlow, long dlow_sn, long dlow_sc, const float* dmag, long dmag_sn, long dmag_so, long dmag_sc,
                          const float* phase, float* dx, long N, int C, int H, int W, const float* h0a, const float* h0b,
-                         const float* h1a, const float* h1b, int m, faoctasr_stream_t stream);
-/* The same four calls on the three-filter banks (ScatLayerj1_rot_f, ScatLayerj2_rot_f): the third filter as in the dtcwt *_bp calls
- * above, everything else as the call without the suffix; bwd_*_bp takes the forward's analysis taps, the third included. */
-int faoctasr_scat_fwd_j1_bp(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, int pool,
-                            float* mag, long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2,
-                            long N, int C, int H, int W, const float* h0, int L0, const float* h1, int L1, const float* h2, int L2,
-                            int mode, faoctasr_stream_t stream);
-int faoctasr_scat_fwd_j2_bp(const float* x, long x_sn, long x_sc, long x_sr, float* low, long low_sn, long low_sc, float* mag,
-                            long mag_sn, long mag_so, long mag_sc, float* phase, int colour, float bias, float bias2, long N, int C,
-                            int H, int W, const float* h0a, const float* h0b, const float* h1a, const float* h1b, const float* h2a,
-                            const float* h2b, int m, faoctasr_stream_t stream);
-int faoctasr_scat_bwd_j1_bp(const float* dlow, long dlow_sn, long dlow_sc, int pool, const float* dmag, long dmag_sn, long dmag_so,
-                            long dmag_sc, const float* phase, float* dx, long N, int C, int H, int W, const float* h0, int L0,
-                            const float* h1, int L1, const float* h2, int L2, int mode, faoctasr_stream_t stream);
-int faoctasr_scat_bwd_j2_bp(const float* dlow, long dlow_sn, long dlow_sc, const float* dmag, long dmag_sn, long dmag_so, long dmag_sc,
-                            const float* phase, float* dx, long N, int C, int H, int W, const float* h0a, const float* h0b,
-                            const float* h1a, const float* h1b, const float* h2a, const float* h2b, int m,
-                            faoctasr_stream_t stream);
+                         const float* h1a, const float* h1b, const float* h2a, const float* h2b, int m, faoctasr_stream_t stream);
 
 /* ---- DTCWT magnitude loss (csrc/dtcwt_loss.hip) -----------------------------------------------------
  * L(x, y) = sum_j w_j * mean over (n, c, orientation, row, column) of | r_j(x) - r_j(y) |,  r = sqrt(re^2 + im^2 + bias^2), over the

@@ -27,6 +27,7 @@ import pytest
 import torch
 
 from test_dtcwt_cpu import rel_l2
+from test_rot_cpu import third_filter
 from test_cwssim_cpu import BANKS, CASES, KC, MAX_KAPPA, bufs, case_name, fixture_cases, fixture_inputs, gold, loss_err, restate, restate_case, tuples
 
 pytestmark = pytest.mark.gpu
@@ -270,6 +271,7 @@ def test_launch_counts(fa, monkeypatch, J):
         S = mod(xd, yd)
         assert own(calls) == ["cwssim_index", "cwssim_final"] * J
         assert [n for n, _ in calls if n.startswith("dtcwt")] == ["dtcwt_fwd_j1"] * 2 + ["dtcwt_fwd_j2"] * (2 * (J - 1))
+        assert not any(third_filter(n, a) for n, a in calls if n.startswith("dtcwt"))      # bank "a" has two filters: NULL third
         assert len(calls) == 4 * J
         assert all(a[MAP_A_ARG] and a[MAP_B_ARG] for n, a in calls if n == "cwssim_index")
         del calls[:]

@@ -1,7 +1,8 @@
 """The transform (dtcwt.hip), the scattering layers (scat.hip) and the magnitude loss (dtcwt_loss.hip) run the same tile bodies
 (csrc/dtcwt_dev.h), so where two families compute the same lowpass they compute the same filter sums in the same order: the
 results are equal bit for bit, on an input with a remainder tile in both axes.  The entry points are driven as ops.py drives
-them, on tensors allocated here; the taps are bank "a" of the dual-tree fixtures and the three-filter fixture bank."""
+them (the third filter NULL for a two-filter bank), on tensors allocated here; the taps are bank "a" of the dual-tree fixtures and
+the three-filter fixture bank."""
 import pytest
 import torch
 
@@ -38,9 +39,9 @@ def transform_ll(fa, x, taps, level1, mode=1):
     st, vec = fa.ops._dtcwt_high_strides(hi, "ncohwr")
     head = (x.data_ptr(),) + x.stride()[:3] + (ll.data_ptr(), hi.data_ptr()) + st + (vec, N, C, H, W)
     if level1:
-        fa._lib.call(fa.ops._bp("dtcwt_fwd_j1", taps, True), *head, *fa.ops._taps1_args(taps), mode, fa._lib.stream_ptr())
+        fa._lib.call("dtcwt_fwd_j1", *head, *fa.ops._taps1_args(taps), mode, fa._lib.stream_ptr())
     else:
-        fa._lib.call(fa.ops._bp("dtcwt_fwd_j2", taps, False), *head, *(fa.ops._tap_array(t) for t in taps), len(taps[0]), fa._lib.stream_ptr())
+        fa._lib.call("dtcwt_fwd_j2", *head, *fa.ops._taps2_args(taps), fa._lib.stream_ptr())
     return ll
 
 
@@ -53,7 +54,7 @@ def test_scat_level1_lowpass_is_the_transforms(fa, bank, mode):
     x = image(1, H, W)
     low = torch.full((N, C, H, W), float("nan"), device="cuda")
     mag = torch.empty((N, 6, C, H // 2, W // 2), device="cuda")
-    fa._lib.call(fa.ops._bp("scat_fwd_j1", taps, True), x.data_ptr(), *x.stride()[:3], *fa.ops._scat_low(low), 0, *fa.ops._scat_mag(mag, False),
+    fa._lib.call("scat_fwd_j1", x.data_ptr(), *x.stride()[:3], *fa.ops._scat_low(low), 0, *fa.ops._scat_mag(mag, False),
                  None, 0, 1e-2, 1e-4, N, C, H, W, *fa.ops._taps1_args(taps), MODES[mode], fa._lib.stream_ptr())
     want = transform_ll(fa, x, taps, True, MODES[mode])
     torch.cuda.synchronize()
@@ -76,7 +77,7 @@ def test_loss_lowpasses_are_the_transforms(fa, level1):
     head = (x.data_ptr(),) + x.stride()[:3] + (y.data_ptr(),) + y.stride()[:3] + (llx.data_ptr(), lly.data_ptr(), None, None, part.data_ptr(),
                                                                                   1.0, 1e-4, N, C, H, W)
     if level1:
-        fa._lib.call("dtcwt_loss_fwd_j1", *head, *fa.ops._taps1_args(taps), 1, fa._lib.stream_ptr())
+        fa._lib.call("dtcwt_loss_fwd_j1", *head, *fa.ops._taps1_args(taps)[:4], 1, fa._lib.stream_ptr())       # the loss takes two filters
     else:
         fa._lib.call("dtcwt_loss_fwd_j2", *head, *(fa.ops._tap_array(t) for t in taps), len(taps[0]), fa._lib.stream_ptr())
     wx, wy = transform_ll(fa, x, taps, level1), transform_ll(fa, y, taps, level1)

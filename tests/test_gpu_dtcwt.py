@@ -12,6 +12,7 @@ import torch
 
 from test_dtcwt_cpu import (BANKS, FWD_BUFS, INV_BUFS, bufs, fixture_cases, fixture_inputs, forward_levels, gold, inverse_levels, rel_l2,
                             restate, restate_case, tuples)
+from test_rot_cpu import third_filter
 
 pytestmark = pytest.mark.gpu
 
@@ -223,9 +224,9 @@ def test_reproducible_and_batch_independent(fa):
 
 
 def test_a_forward_is_one_launch_per_level(fa, monkeypatch):
-    calls = []
+    calls, thirds = [], []                                            # the entry points and whether each got a third filter
     real = fa.ops.call
-    monkeypatch.setattr(fa.ops, "call", lambda name, *a: (calls.append(name), real(name, *a))[1])
+    monkeypatch.setattr(fa.ops, "call", lambda name, *a: (calls.append(name), thirds.append(third_filter(name, a)), real(name, *a))[2])
     fwd, inv = modules(fa, "a", "symmetric", 3)
     x = torch.randn(1, 1, 64, 64).cuda().requires_grad_(True)
     yl, yh = fwd(x)
@@ -236,6 +237,7 @@ def test_a_forward_is_one_launch_per_level(fa, monkeypatch):
     del calls[:]
     inv((yl.detach(), [h.detach() for h in yh]))
     assert calls == ["dtcwt_inv_j2", "dtcwt_inv_j2", "dtcwt_inv_j1"]
+    assert len(thirds) == 9 and not any(thirds)                       # a two-filter bank: NULL every time
 
 
 def test_refusals_come_before_any_launch(fa):

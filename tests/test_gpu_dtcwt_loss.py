@@ -25,6 +25,7 @@ import pytest
 import torch
 
 from test_dtcwt_cpu import rel_l2
+from test_rot_cpu import third_filter
 from test_dtcwt_loss_cpu import BANKS, CASES, MIN_GAP, bufs, case_name, fixture_cases, fixture_inputs, gold, loss_err, restate, restate_case, tuples
 
 pytestmark = pytest.mark.gpu
@@ -205,6 +206,7 @@ def test_launch_counts(fa, monkeypatch, J):
         del calls[:]
         loss.backward()
         assert [n for n, _ in calls] == bwd * (int(x_grad) + int(y_grad))
+        assert not any(third_filter(n, a) for n, a in calls)              # the loss is two-filter: a NULL third filter
         assert (xd.grad is not None) == x_grad and (yd.grad is not None) == y_grad
         monkeypatch.undo()
 

@@ -1,4 +1,4 @@
-"""The three-filter (rotationally symmetric, ``_bp``) forms of the dual-tree and scattering kernels on the MI355X: ``ScatLayer`` /
+"""The three-filter (rotationally symmetric) forms of the dual-tree and scattering kernels on the MI355X: ``ScatLayer`` /
 ``ScatLayerj2`` / ``DTCWTForward`` / ``DTCWTInverse`` with 3-tuple / 6-tuple taps against the reference's own CPU results
 (tests/golden/golden_rot_*.npz) and the float64 restatement of tests/test_rot_cpu.py (pinned to those fixtures there), tile seams
 with the fixture bank and with a synthetic one, the launch structure and structural properties.
@@ -13,13 +13,14 @@ import torch.nn.functional as F
 
 from test_dtcwt_cpu import decode, rel_l2
 from test_scat_cpu import tuples as scat_tuples
-from test_rot_cpu import (DT_J, bufs, dt_cases, dt_inputs, forward_levels, gold, inverse_levels, restate_dt, restate_scat, scat_cases,
-                          synthetic_bufs, tuples)
+from test_rot_cpu import (DT_J, bufs, dt_cases, dt_inputs, forward_levels, gold, inverse_levels, restate_dt, restate_scat,
+                          scat_cases, synthetic_bufs, third_filter, tuples)
 
 pytestmark = pytest.mark.gpu
 
 K, FLOOR = 2.0, 2.0 ** -23
-PHASE_ARG = {"scat_fwd_j1_bp": 12, "scat_fwd_j2_bp": 11}     # position of the phasor pointer in the entry points' arguments
+PHASE_ARG = {"scat_fwd_j1": 12, "scat_fwd_j2": 11}           # position of the phasor pointer in the entry points' arguments
+# the third filter's position is THIRD_ARG of test_rot_cpu.py (the CPU tests build calls from it): third_filter(name, args) reads it
 DEFAULT = ("n", "c", "o", "h", "w", "r")
 BANKS = {"fixture": bufs, "synthetic": synthetic_bufs}
 
@@ -176,47 +177,53 @@ def spy(fa, monkeypatch):
     return calls
 
 
+def launches(calls, third=True):
+    """The entry points of the recorded calls, in order, once every one of them has (has not) its third filter."""
+    assert all(third_filter(n, a) == third for n, a in calls), [(n, third_filter(n, a)) for n, a in calls]
+    return [n for n, _ in calls]
+
+
 @pytest.mark.parametrize("colour", [False, True])
 def test_launch_counts_and_names(fa, monkeypatch, colour):
     x = torch.randn(1, 3, 64, 64).cuda().requires_grad_(True)
     one, two = layer(fa, bufs(), 1, "symmetric", colour), layer(fa, bufs(), 2, "symmetric", colour)
     calls = spy(fa, monkeypatch)
     Z = one(x)
-    assert [n for n, _ in calls] == ["scat_fwd_j1_bp"]
+    assert launches(calls) == ["scat_fwd_j1"]
     del calls[:]
     Z.backward(torch.ones_like(Z))
-    assert [n for n, _ in calls] == ["scat_bwd_j1_bp"]
+    assert launches(calls) == ["scat_bwd_j1"]
     del calls[:]
     Z = two(x)
-    assert [n for n, _ in calls] == ["scat_fwd_j1_bp", "scat_fwd_j2_bp", "scat_fwd_j1_bp"]
+    assert launches(calls) == ["scat_fwd_j1", "scat_fwd_j2", "scat_fwd_j1"]
     assert tuple(Z.shape) == (1, 51 if colour else 147, 16, 16) and Z.is_contiguous()
     del calls[:]
     Z.backward(torch.ones_like(Z))
-    assert [n for n, _ in calls] == ["scat_bwd_j1_bp", "scat_bwd_j2_bp", "scat_bwd_j1_bp"]
+    assert launches(calls) == ["scat_bwd_j1", "scat_bwd_j2", "scat_bwd_j1"]
 
 
 def test_transform_launches(fa, monkeypatch):
-    """One launch per level each way on the ``_bp`` entry points; a level that skips its bandpass has no third filter to run and
-    takes the two-filter lowpass entry."""
+    """One launch per level each way, every one with its third filter (at levels >= 2 both pointers of the pair); a level that
+    skips its bandpass has no third filter to run and passes a NULL one: the two-filter lowpass form."""
     x = torch.randn(1, 2, 32, 32, generator=torch.Generator().manual_seed(1)).cuda().requires_grad_(True)
     fwd, inv = modules(fa, bufs(), "symmetric", 3)
     calls = spy(fa, monkeypatch)
     yl, yh = fwd(x)
-    assert [n for n, _ in calls] == ["dtcwt_fwd_j1_bp", "dtcwt_fwd_j2_bp", "dtcwt_fwd_j2_bp"]
+    assert launches(calls) == ["dtcwt_fwd_j1", "dtcwt_fwd_j2", "dtcwt_fwd_j2"]
     del calls[:]
     torch.autograd.backward([yl] + list(yh), [torch.ones_like(t) for t in [yl] + list(yh)])
-    assert [n for n, _ in calls] == ["dtcwt_inv_j2_bp", "dtcwt_inv_j2_bp", "dtcwt_inv_j1_bp"]
+    assert launches(calls) == ["dtcwt_inv_j2", "dtcwt_inv_j2", "dtcwt_inv_j1"]
     del calls[:]
     cl, ch = yl.detach().requires_grad_(True), [h.detach().requires_grad_(True) for h in yh]
     y = inv((cl, ch))
-    assert [n for n, _ in calls] == ["dtcwt_inv_j2_bp", "dtcwt_inv_j2_bp", "dtcwt_inv_j1_bp"]
+    assert launches(calls) == ["dtcwt_inv_j2", "dtcwt_inv_j2", "dtcwt_inv_j1"]
     del calls[:]
     y.backward(torch.ones_like(y))
-    assert [n for n, _ in calls] == ["dtcwt_fwd_j1_bp", "dtcwt_fwd_j2_bp", "dtcwt_fwd_j2_bp"]
+    assert launches(calls) == ["dtcwt_fwd_j1", "dtcwt_fwd_j2", "dtcwt_fwd_j2"]
     del calls[:]
     skip = modules(fa, bufs(), "symmetric", 2, skip_hps=[False, True])[0]
     sl, sh = skip(x.detach())
-    assert [n for n, _ in calls] == ["dtcwt_fwd_j1_bp", "dtcwt_fwd_j2"] and sh[1].dim() == 0
+    assert launches(calls[:1]) == ["dtcwt_fwd_j1"] and launches(calls[1:], third=False) == ["dtcwt_fwd_j2"] and sh[1].dim() == 0
     two = modules(fa, bufs(), "symmetric", 2)[0](x.detach())
     assert torch.equal(sl, two[0]) and torch.equal(sh[0], two[1][0])
 
@@ -325,7 +332,7 @@ def test_the_forwards_backward_is_the_inverse_kernel(fa):
 
 
 def test_the_two_filter_path_is_untouched(fa, monkeypatch):
-    """A two-filter ``ScatLayerj2`` and ``DTCWTForward`` on the two-filter fixture bank a call only the old entry points."""
+    """A two-filter ``ScatLayerj2`` and ``DTCWTForward`` on the two-filter fixture bank pass a NULL third filter to every entry point."""
     fb, fq = scat_tuples("a")
     two = fa.ScatLayerj2(biort=fb, qshift=fq).cuda()
     fwd = fa.DTCWTForward(biort=fb, qshift=fq, J=2).cuda()
@@ -335,5 +342,5 @@ def test_the_two_filter_path_is_untouched(fa, monkeypatch):
     Z.backward(torch.ones_like(Z))
     yl, yh = fwd(x)
     torch.autograd.backward([yl] + list(yh), [torch.ones_like(t) for t in [yl] + list(yh)])
-    assert [n for n, _ in calls] == ["scat_fwd_j1", "scat_fwd_j2", "scat_fwd_j1", "scat_bwd_j1", "scat_bwd_j2", "scat_bwd_j1",
-                                     "dtcwt_fwd_j1", "dtcwt_fwd_j2", "dtcwt_inv_j2", "dtcwt_inv_j1"]
+    assert launches(calls, third=False) == ["scat_fwd_j1", "scat_fwd_j2", "scat_fwd_j1", "scat_bwd_j1", "scat_bwd_j2", "scat_bwd_j1",
+                                            "dtcwt_fwd_j1", "dtcwt_fwd_j2", "dtcwt_inv_j2", "dtcwt_inv_j1"]

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from test_dtcwt_cpu import rel_l2
+from test_rot_cpu import third_filter
 from test_scat_cpu import BANKS, bufs, case_name, fixture_cases, fixture_inputs, gold, restate, restate_case, tuples
 
 pytestmark = pytest.mark.gpu
@@ -82,6 +83,12 @@ def test_tile_seams(fa, bank, order):
     hold_to_bar("seams %s j%d %s %s" % ("x".join(map(str, shape)), order, bank, mode), ref64, ref32, run_hip(layer(fa, bank, order, mode), x, cot))
 
 
+def two_filter(calls):
+    """The entry points of the recorded calls, in order, once every one of them has a NULL third filter."""
+    assert not any(third_filter(n, a) for n, a in calls)
+    return [n for n, _ in calls]
+
+
 def spy(fa, monkeypatch):
     calls = []
     real = fa.ops.call
@@ -112,17 +119,17 @@ def test_launch_counts(fa, monkeypatch, colour):
     one, two = layer(fa, "a", 1, "symmetric", colour), layer(fa, "a", 2, "symmetric", colour)
     calls = spy(fa, monkeypatch)
     Z = one(x)
-    assert [n for n, _ in calls] == ["scat_fwd_j1"]
+    assert two_filter(calls) == ["scat_fwd_j1"]
     del calls[:]
     Z.backward(torch.ones_like(Z))
-    assert [n for n, _ in calls] == ["scat_bwd_j1"]
+    assert two_filter(calls) == ["scat_bwd_j1"]
     del calls[:]
     Z = two(x)
-    assert [n for n, _ in calls] == ["scat_fwd_j1", "scat_fwd_j2", "scat_fwd_j1"]
+    assert two_filter(calls) == ["scat_fwd_j1", "scat_fwd_j2", "scat_fwd_j1"]
     assert tuple(Z.shape) == (1, 51 if colour else 147, 16, 16) and Z.is_contiguous()
     del calls[:]
     Z.backward(torch.ones_like(Z))
-    assert [n for n, _ in calls] == ["scat_bwd_j1", "scat_bwd_j2", "scat_bwd_j1"]
+    assert two_filter(calls) == ["scat_bwd_j1", "scat_bwd_j2", "scat_bwd_j1"]
 
 
 @pytest.mark.parametrize("bank,mode", [("a", "symmetric"), ("b", "zero"), ("c", "symmetric")])

@@ -4,6 +4,7 @@ the two scattering layers over them (scatternet/lowlevel.py ScatLayerj1_rot_f, S
 results in tests/golden/golden_rot_scat.npz and golden_rot_dtcwt.npz (tools/gen_golden_rot.py), and the host logic of the
 3-tuple / 6-tuple tap forms.  The restatement is built on the helpers of test_dtcwt_cpu.py and test_scat_cpu.py; the GPU test
 (test_gpu_rot.py) imports it from here."""
+import ctypes
 import os
 import sys
 import types
@@ -23,7 +24,20 @@ INV_BUFS = ("g0o", "g1o", "g0a", "g0b", "g1a", "g1b", "g2o", "g2a", "g2b")
 DT_MODES = ("symmetric", "zero")
 DT_SHAPES = ((2, 2, 16, 24), (1, 1, 8, 8))
 DT_J = 3
+# position of the third filter in the entry points' arguments: (pointer, length) at level 1, the pair (a2, b2) at levels >= 2
+THIRD_ARG = {"dtcwt_fwd_j1": 21, "dtcwt_fwd_j2": 21, "dtcwt_inv_j1": 20, "dtcwt_inv_j2": 20,
+             "scat_fwd_j1": 24, "scat_fwd_j2": 23, "scat_bwd_j1": 18, "scat_bwd_j2": 17}
 _gold = {}
+
+
+def third_filter(name, args):
+    """Whether a recorded call of entry ``name`` passes a third filter; a half-given one is an error."""
+    p, q = args[THIRD_ARG[name]:THIRD_ARG[name] + 2]
+    if name.endswith("j1"):
+        assert (bool(p) and q >= 3) or (p is None and q == 0), (name, p, q)
+    else:
+        assert bool(p) == bool(q) and (p is None) == (q is None), (name, p, q)
+    return bool(p)
 
 
 def gold(which):
@@ -380,8 +394,67 @@ def fa():
 
 
 def test_entry_points_are_declared(fa):
-    for n in ("dtcwt_fwd_j1", "dtcwt_fwd_j2", "dtcwt_inv_j1", "dtcwt_inv_j2", "scat_fwd_j1", "scat_fwd_j2", "scat_bwd_j1", "scat_bwd_j2"):
-        assert "faoctasr_" + n + "_bp" in fa._lib.declared_symbols()
+    """One entry point per launch, none with a ``_bp`` twin, each binding the argument list with the optional third filter: the
+    pointers and lengths of three level-1 filters, or six q-shift pointers and their one length, then mode or nothing and the stream."""
+    assert len(THIRD_ARG) == 8
+    assert not [s for s in fa._lib.declared_symbols() if s.endswith("_bp")]
+    for n, at in THIRD_ARG.items():
+        assert "faoctasr_" + n in fa._lib.declared_symbols()
+        codes = fa._lib._SIG[n][1].replace(" ", "")
+        assert codes[at - 8:] == ("liii" + "pipipi" + "ip" if n.endswith("j1") else "liii" + "pppppp" + "ip"), (n, codes)
+
+
+def entry_args(fa, name, taps, third_len=None, m=None, **data):
+    """The arguments of entry ``name`` on one 1 x 1 x 8 x 8 plane with NULL data pointers and zero strides, bar ``data`` (position:
+    pointer); ``taps`` are the three (pointer, length) pairs or the six pointers, None for a NULL."""
+    at = THIRD_ARG[name]
+    a = [{"p": None, "i": 0, "l": 0, "f": 0.0}[c] for c in fa._lib._SIG[name][1].replace(" ", "")]
+    a[at - 8:at - 4] = [1, 1, 8, 8]
+    if name.endswith("j1"):
+        a[at - 4:at + 3] = [v for t in taps for v in ((fa.ops._tap_array(t), len(t)) if t is not None else (None, 0))] + [1]
+        if third_len is not None:
+            a[at + 1] = third_len
+    else:
+        a[at - 4:at + 3] = [fa.ops._tap_array(t) if t is not None else None for t in taps] + [len(taps[1]) if m is None else m]
+    for k, v in data.items():
+        a[int(k[1:])] = v
+    return a
+
+
+def test_tap_arguments_choose_the_form_before_any_launch(fa):
+    """The third filter of the eight entry points is optional, and the tap arguments alone decide the form.  No GPU: every call
+    here fails validation.  dt_with_taps1 / dt_with_taps2 / dt_with_tapsi (csrc/dtcwt_dev.h) check and pack the taps without a HIP
+    call and hand them to run_* of the chosen form, whose first statement (sc_common in run_fwd_* of scat.hip) returns "null
+    pointer" for the NULL data pointers passed here; the lowpass-alone refusal of dtcwt_fwd_j* follows only shape and block-count
+    checks and precedes its launch.  So "null pointer" means: taps accepted, form chosen, data check reached."""
+    lib = fa._lib.load()
+    b = {k: tuple(v.float().tolist()) for k, v in bufs().items()}
+    three1, three2 = (b["h0o"], b["h1o"], b["h2o"]), (b["h0a"], b["h0b"], b["h1a"], b["h1b"], b["h2a"], b["h2b"])
+    host = ctypes.cast((ctypes.c_float * 64)(), ctypes.c_void_p)            # a non-null x / ll for the checks that follow the first
+
+    def refused(name, words, *a, **kw):
+        rc, msg = getattr(lib, "faoctasr_" + name)(*entry_args(fa, name, *a, **kw)), lib.faoctasr_last_error().decode()
+        assert rc == -1 and msg.startswith(name + ":") and all(w in msg for w in words), (name, a, kw, rc, msg)
+
+    for name in THIRD_ARG:
+        if name.endswith("j1"):
+            refused(name, ["null pointer"], three1[:2] + (None,))
+            refused(name, ["null pointer"], three1)
+            for L2 in (4, 1, 21):
+                refused(name, ["third-filter tap count %d " % L2], three1, third_len=L2)
+            refused(name, ["NULL third filter", "got 5"], three1[:2] + (None,), third_len=5)
+            refused(name, ["null tap pointer"], (None,) + three1[1:])
+        else:
+            refused(name, ["null pointer"], three2[:4] + (None, None))
+            refused(name, ["null pointer"], three2)
+            refused(name, ["third filter pair (a2, b2)"], three2[:5] + (None,))
+            refused(name, ["third filter pair (a2, b2)"], three2[:4] + (None, three2[5]))
+            refused(name, ["null tap pointer"], (None,) + three2[1:])
+            refused(name, ["q-shift tap count 13"], three2, m=13)
+    for name, taps, two in (("dtcwt_fwd_j1", three1, three1[:2] + (None,)), ("dtcwt_fwd_j2", three2, three2[:4] + (None, None))):
+        refused(name, ["null pointer"], taps, a0=host)                       # x alone: neither output
+        refused(name, ["no third filter", "pass a NULL third filter"], taps, a0=host, a4=host)     # x and ll, no hi: the lowpass alone
+        refused(name, ["H 7 W 8"], two, a0=host, a4=host, **{"a%d" % (THIRD_ARG[name] - 6): 7})     # two filters pass that check: the shape is next
 
 
 def test_modules_register_the_reference_parameters(fa):

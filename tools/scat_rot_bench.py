@@ -1,4 +1,4 @@
-"""Time the three-filter scattering layers (the ``_bp`` kernels of csrc/scat.hip) and what the third filter path costs.
+"""Time the three-filter scattering layers (the entry points of csrc/scat.hip with their third filter) and what the third filter path costs.
 
     python tools/scat_rot_bench.py [--out profiles/scat_rot_bench.txt]
 
