@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("FAOCTASR_LIB") or os.path.join(_HERE, "libfaoctasr.so
 
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 _SIG = {
-    # name: (restype, "argument codes")   p pointer, i int, l long, f float
+    # name: (restype, "argument codes")   p pointer, i int, l long, f float, d double
     "version": (_I, ""),
     "last_error": (ctypes.c_char_p, ""),
     "last_route": (_I, ""),
@@ -97,6 +97,10 @@ _SIG = {
     "msssim_scale_fwd": (_I, "pp pp p l iii i ff p"),
     "msssim_final": (_I, "p ll iii p i ppp p"),
     "msssim_scale_bwd": (_I, "pp p p i pp pp ll iii i ff p"),
+    "haarpsi_workspace_floats": (_L, "l ii"),
+    "haarpsi_index": (_I, "pp p l ii ffff p"),
+    "haarpsi_final": (_I, "p ll ii d i ppp p"),
+    "haarpsi_grad": (_I, "pp p p i pp ll ii ffff p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),
@@ -117,7 +121,7 @@ _SIG = {
     "grad_allreduce": (_I, "p l i p p"),
     "param_broadcast": (_I, "p l i p p"),
 }
-_CODE = {"p": _P, "i": _I, "l": _L, "f": _F}
+_CODE = {"p": _P, "i": _I, "l": _L, "f": _F, "d": ctypes.c_double}
 PACK_JOB_BYTES = 1024          # include/faoctasr.h FAOCTASR_PACK_JOB_BYTES
 
 _lib = None

@@ -46,22 +46,38 @@ def image_metrics(y, gt, data_range=2.0, bins=100, cw_ssim=None):
     return out
 
 
-def evaluate_pairs(model, pairs, cw_ssim=None, ms_ssim=None):
-    """pairs: iterable of (lr (B,1,H,W), hr (B,1,H,W)) device tensors.  Returns mean PSNR / SSIM / MSE / NMI like the print at
-    utils.py:214,242; one host read at the end.  With a ``wavelets.CWSSIM`` module as ``cw_ssim`` also the key "cw_ssim"; with an
-    ``ssim.MSSSIM`` module as ``ms_ssim`` also the key "ms_ssim", the mean of the module's per-image multi-scale index of
-    ``(super_resolve(lr), hr)``."""
-    keys = ("psnr", "ssim", "mse", "nmi") + (("cw_ssim",) if cw_ssim is not None else ()) + (("ms_ssim",) if ms_ssim is not None else ())
+def evaluate_pairs_with(model, pairs, cw_ssim=None, **indices):
+    """``evaluate_pairs`` with any number of further full-reference indices: every keyword names a module with
+    ``index(a, b, per_image)`` (``ssim.MSSSIM``, ``ssim.HaarPSI``) and adds a key of that name, in keyword order, behind the four
+    metrics and "cw_ssim": the mean of the module's per-image index of ``(super_resolve(lr), hr)``.  A keyword given as None adds
+    nothing.  ``evaluate_pairs_with(model, pairs, haarpsi=HaarPSI())`` returns the keys psnr, ssim, mse, nmi, haarpsi.  The keyword is
+    the key: any name is taken, so a value that is no index module (no callable ``index``, or a string or sequence, whose ``index``
+    is something else) and a name that is already a key raise ``TypeError`` / ``ValueError`` before anything runs."""
+    indices = {k: mod for k, mod in indices.items() if mod is not None}
+    for k, mod in indices.items():
+        if isinstance(mod, (str, bytes, list, tuple)) or not callable(getattr(mod, "index", None)):
+            raise TypeError("%s must be a module with index(a, b, per_image), got %r" % (k, mod))
+        if k in ("psnr", "ssim", "mse", "nmi", "cw_ssim"):
+            raise ValueError("%r is a key of the result already" % k)
+    keys = ("psnr", "ssim", "mse", "nmi") + (("cw_ssim",) if cw_ssim is not None else ()) + tuple(indices)
     acc, n = None, 0
     for lr, hr in pairs:
         sr = super_resolve(model, lr)
         m = image_metrics(sr, hr, cw_ssim=cw_ssim).sum(0)
-        if ms_ssim is not None:
+        for mod in indices.values():
             with torch.no_grad():
-                m = torch.cat((m, ms_ssim.index(sr, hr, True).double().sum(0, keepdim=True)))
+                m = torch.cat((m, mod.index(sr, hr, True).double().sum(0, keepdim=True)))
         acc = m if acc is None else acc + m
         n += lr.shape[0]
     if acc is None:
         return dict.fromkeys(keys, 0.0)
     vals = (acc / n).tolist()
     return dict(zip(keys, vals))
+
+
+def evaluate_pairs(model, pairs, cw_ssim=None, ms_ssim=None):
+    """pairs: iterable of (lr (B,1,H,W), hr (B,1,H,W)) device tensors.  Returns mean PSNR / SSIM / MSE / NMI like the print at
+    utils.py:214,242; one host read at the end.  With a ``wavelets.CWSSIM`` module as ``cw_ssim`` also the key "cw_ssim"; with an
+    ``ssim.MSSSIM`` module as ``ms_ssim`` also the key "ms_ssim", the mean of the module's per-image multi-scale index of
+    ``(super_resolve(lr), hr)``.  Further indices (``ssim.HaarPSI``): ``evaluate_pairs_with``."""
+    return evaluate_pairs_with(model, pairs, cw_ssim=cw_ssim, ms_ssim=ms_ssim)

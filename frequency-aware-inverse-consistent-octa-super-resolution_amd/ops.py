@@ -2711,3 +2711,111 @@ def ms_ssim(a, b, levels=5, weights=None, data_range=1.0, per_image=False):
     grad = torch.is_grad_enabled()
     return _MSSSIM.apply(a.contiguous(), b.contiguous(), w, (0.01 * L) ** 2, (0.03 * L) ** 2, bool(per_image), grad and a.requires_grad,
                          grad and b.requires_grad)
+
+
+# ----------------------------------------------------------------------------------------
+# HaarPSI (csrc/haarpsi.hip): Haar coefficients of the half-resolution pair, edge-weighted logistic of the local similarity
+# ----------------------------------------------------------------------------------------
+def _haarpsi_check_scalars(c, alpha, value_range):
+    """The refusals of ``haarpsi`` that concern no tensor; returns ``(c, alpha, lo, hi)`` as floats."""
+    for v, what in ((c, "c"), (alpha, "alpha")):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("%s must be a number, got %r" % (what, v))
+        if not (v > 0 and v < float("inf")):
+            raise ValueError("%s must be positive and finite, got %r" % (what, v))
+    try:
+        lo, hi = value_range
+    except (TypeError, ValueError):
+        raise TypeError("value_range must be a pair (lo, hi), got %r" % (value_range,)) from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("value_range must hold two numbers, got %r" % (value_range,))
+    if not (hi > lo and math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("value_range must be finite with hi > lo, got %r" % (value_range,))
+    return float(c), float(alpha), float(lo), float(hi)
+
+
+def _haarpsi_check(a, b, c, alpha, value_range):
+    """Every refusal of ``haarpsi``, the device check last; returns ``(c, alpha, lo, hi)``."""
+    cfg = _haarpsi_check_scalars(c, alpha, value_range)
+    for t, what in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s" % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor, got %s" % (what, t.dtype))
+        if t.dim() != 4:
+            raise ValueError("%s must be (N, C, H, W), got %s" % (what, tuple(t.shape)))
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("the index takes non-empty images, got %s" % (tuple(a.shape),))
+    if min(a.shape[2], a.shape[3]) < 2:
+        raise ValueError("every side must be at least 2, got %d x %d" % (a.shape[2], a.shape[3]))
+    for t, what in ((a, "a"), (b, "b")):
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    if a.device != b.device:
+        raise ValueError("a and b must be on one device, got %s and %s" % (a.device, b.device))
+    return cfg
+
+
+class _HaarPSI(Function):
+    """``apply(a, b, c, alpha, lo, hi, per_image, want_a, want_b) -> HaarPSI``: ``haarpsi_index`` and ``haarpsi_final`` forward; where
+    an input needs a gradient the two images and the (2, N) factor table are saved, and the backward is one ``haarpsi_grad``, which
+    reads the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, a, b, c, alpha, lo, hi, per_image, want_a, want_b):
+        N, C, H, W = a.shape
+        dev = a.device
+        n = _lib.load().faoctasr_haarpsi_workspace_floats(N * C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_haarpsi_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "haarpsi")                # per stream: consumed by the same call's second launch
+        call("haarpsi_index", ptr(a), ptr(b), ws.data_ptr(), N * C, H, W, lo, hi, c, alpha, stream_ptr())
+        want = want_a or want_b
+        fac = torch.empty((2, N), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = torch.empty((), dtype=torch.float32, device=dev)
+        call("haarpsi_final", ws.data_ptr(), N, C, H, W, alpha, int(not per_image), ptr(out_image), ptr(out_mean), ptr(fac), stream_ptr())
+        ctx.cfg = (c, alpha, lo, hi, want_a, want_b)
+        if want:
+            ctx.save_for_backward(a, b, fac)
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        c, alpha, lo, hi, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 9
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("haarpsi's forward ran without gradients enabled for this input: nothing was saved")
+        a, b, fac = ctx.saved_tensors
+        N, C, H, W = a.shape
+        g = _c(g).reshape(-1)
+        da = torch.empty_like(a) if need_a else None
+        db = torch.empty_like(b) if need_b else None
+        call("haarpsi_grad", ptr(a), ptr(b), ptr(fac), ptr(g), g.numel(), ptr(da), ptr(db), N, C, H, W, lo, hi, c, alpha, stream_ptr())
+        return (da, db) + (None,) * 7
+
+
+def haarpsi(a, b, c=30.0, alpha=4.2, value_range=(-1., 1.), per_image=False):
+    """The Haar wavelet-based perceptual similarity index (Reisenhofer, Bosse, Kutyniok & Wiegand 2018) of two images ``(N, C, H, W)``,
+    every channel an independent grey plane pooled inside its image.  With ``u = (x - lo) 255 / (hi - lo)``, ``u2`` its 2 x 2 mean at
+    every second pixel (samples beyond the image 0, divisor 4), ``g^o_k`` the horizontal and vertical Haar coefficients of ``u2`` at
+    the scales 2, 4, 8 (``2^-k`` times the difference of the two half-window sums, zero outside the map), ``a_k = |g^o_k(a)|`` and
+    ``b_k = |g^o_k(b)|``:
+
+        S_o = 1/2 sum_{k = 1, 2} (2 a_k b_k + c) / (a_k^2 + b_k^2 + c),   W_o = max(a_3, b_3),
+        r[n] = sum sigmoid(alpha S_o) W_o / sum W_o,   HaarPSI[n] = (log(r / (1 - r)) / alpha)^2,
+
+    the mean over n as a 0-d fp32 tensor, or ``(N,)`` with ``per_image``; 1 for identical images, and 1 with zero gradients where
+    neither image has any structure at the coarse scale.  The loss is ``1 - haarpsi``.  Gradients to both images (``d|g|/dg`` is
+    ``sign(g)`` with ``sign(0) = 0``; in ``max`` the gradient goes to the larger side, at equality to ``a``).  Two launches of
+    csrc/haarpsi.hip forward and one backward; under ``no_grad``, or for inputs that need no gradient, nothing is saved, otherwise
+    the two images and a (2, N) table.  ``haarpsi(x, y) == haarpsi(y, x)`` bit for bit with swapped gradients; runs are
+    bit-reproducible.  Every side must be at least 2.  fp32, grey planes only (no YIQ chroma term), no double backward."""
+    c, alpha, lo, hi = _haarpsi_check(a, b, c, alpha, value_range)
+    grad = torch.is_grad_enabled()
+    return _HaarPSI.apply(a.contiguous(), b.contiguous(), c, alpha, lo, hi, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)

@@ -1,5 +1,5 @@
 """SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
-same window behind the same interface (csrc/msssim.hip)."""
+same window behind the same interface (csrc/msssim.hip), and HaarPSI behind the same ``forward`` / ``index`` pair (csrc/haarpsi.hip)."""
 from math import exp
 
 import torch
@@ -75,3 +75,33 @@ class MSSSIM(torch.nn.Module):
 
     def extra_repr(self):
         return "levels={}, weights={}, data_range={}, size_average={}".format(self.levels, self.weights, self.data_range, self.size_average)
+
+
+def haarpsi(img1, img2, c=30.0, alpha=4.2, value_range=(-1., 1.), size_average=True):
+    """HaarPSI with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with ``size_average=False`` (``ops.haarpsi``)."""
+    return ops.haarpsi(img1, img2, c, alpha, value_range, not size_average)
+
+
+class HaarPSI(torch.nn.Module):
+    """forward(img1, img2) -> the Haar wavelet-based perceptual similarity index (Reisenhofer, Bosse, Kutyniok & Wiegand 2018) with
+    ``SSIM``'s interface: the images are mapped from ``value_range`` to 0..255 and halved by a 2 x 2 mean; the similarity of the Haar
+    coefficient magnitudes at the scales 2 and 4, ``1/2 sum_k (2 a_k b_k + c) / (a_k^2 + b_k^2 + c)``, goes through a logistic of
+    slope ``alpha`` and is averaged with the scale-8 edge strength of the stronger image as weight; the score is the squared
+    inverse logistic of that average.  Channels are independent grey planes pooled inside an image (no YIQ chroma term).  The mean
+    over the batch, or ``(N,)`` with ``size_average=False``; the loss is ``1 - HaarPSI``.  Every side must be at least 2; fp32, no
+    double backward (csrc/haarpsi.hip)."""
+
+    def __init__(self, c=30.0, alpha=4.2, value_range=(-1., 1.), size_average=True):
+        super().__init__()
+        self.c, self.alpha, lo, hi = ops._haarpsi_check_scalars(c, alpha, value_range)
+        self.value_range, self.size_average = (lo, hi), size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.haarpsi(img1, img2, self.c, self.alpha, self.value_range, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "c={}, alpha={}, value_range={}, size_average={}".format(self.c, self.alpha, self.value_range, self.size_average)

@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
-from .ssim import MSSSIM
+from .ssim import MSSSIM, HaarPSI
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
@@ -266,7 +266,8 @@ class TrainStep:
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
                  msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
-                 ffl_batch_matrix=False, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False):
+                 ffl_batch_matrix=False, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
+                 haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -311,7 +312,13 @@ class TrainStep:
         sigma_ratio=mi_sigma_ratio, normalized=mi_normalized)`` and ``U = log(mi_bins)`` (with ``mi_normalized``: 2) its upper
         bound.  Every other opt-in term compares a reconstruction with its own input or looks at a fake alone; this one ties a fake
         to the image of the OTHER domain it was made from, where pixelwise distances do not apply.  The gradient reaches the fake
-        only."""
+        only.
+
+        ``haarpsi_weight`` (default 0: nothing is constructed or launched): adds ``loss_haarpsi = haarpsi_weight * ((1 -
+        H(recovered_A, real_A)) + (1 - H(recovered_B, real_B)))`` to ``loss_G``, H the Haar wavelet-based perceptual similarity index
+        ``HaarPSI(c=haarpsi_c, alpha=haarpsi_alpha)`` on the images' range (-1, 1): every position is weighted by the coarse-scale
+        edge strength of the stronger image, so an error on a vessel wall counts and one in the background does not, and the
+        logistic of the local similarity keeps one badly wrong region from dominating."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -359,6 +366,9 @@ class TrainStep:
             raise ValueError("mi_weight must be a finite number >= 0, got %r" % (mi_weight,))
         self.mi_weight = mi_weight
         self.mi = MutualInformationLoss(bins=mi_bins, sigma_ratio=mi_sigma_ratio, normalized=mi_normalized) if mi_weight else None
+        #: opt-in HaarPSI term on the cycle reconstructions (ssim.HaarPSI; 0 = off, no module is built)
+        self.haarpsi_weight = haarpsi_weight
+        self.haarpsi = HaarPSI(c=haarpsi_c, alpha=haarpsi_alpha).to(dev) if haarpsi_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -670,6 +680,8 @@ class TrainStep:
             t["loss_cwssim"] = self.cwssim_weight * (1 - self.cwssim(rec, real))
         if self.msssim_weight:
             t["loss_msssim"] = self.msssim_weight * (1 - self.msssim(rec, real))
+        if self.haarpsi_weight:
+            t["loss_haarpsi"] = self.haarpsi_weight * (1 - self.haarpsi(rec, real))
         if self.ffl_weight:
             t["loss_ffl"] = self.ffl_weight * self.ffl(rec, real)
         return t
@@ -718,6 +730,9 @@ class TrainStep:
         if self.msssim_weight:
             L["loss_msssim"] = self.msssim_weight * ((1 - self.msssim(o["recovered_A"], real_A)) + (1 - self.msssim(o["recovered_B"], real_B)))
             total = total + L["loss_msssim"]
+        if self.haarpsi_weight:
+            L["loss_haarpsi"] = self.haarpsi_weight * ((1 - self.haarpsi(o["recovered_A"], real_A)) + (1 - self.haarpsi(o["recovered_B"], real_B)))
+            total = total + L["loss_haarpsi"]
         if self.ffl_weight:
             L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))
             total = total + L["loss_ffl"]

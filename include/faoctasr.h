@@ -538,6 +538,29 @@ int faoctasr_msssim_scale_bwd(const float* a, const float* b, const float* coef,
                               float* da, float* db, long N, long C, int H, int W, int levels, int scale, float C1, float C2,
                               faoctasr_stream_t stream);
 
+/* ---- HaarPSI (csrc/haarpsi.hip) -----------------------------------------------------------------
+ * x, y: contiguous (planes, H, W), planes = N * C, H, W >= 2; every plane a grey image.  u = (x - lo) 255 / (hi - lo), hi > lo; u2 its 2 x 2
+ * mean at every second pixel (samples beyond the image 0, divisor 4), (H + 1) / 2 by (W + 1) / 2; g^o_k, o in {v, h}, k = 1, 2, 3, the Haar
+ * coefficients of u2 on 2^k x 2^k windows (2^-k times the difference of the two half-window sums; window rows i - 2^(k-1) + 1 ..
+ * i + 2^(k-1), u2 zero outside the map); a_k = |g^o_k(x)|, b_k = |g^o_k(y)|:
+ *   S_o = 1/2 sum_{k = 1, 2} (2 a_k b_k + c) / (a_k^2 + b_k^2 + c),  W_o = max(a_3, b_3),  c > 0, alpha > 0,
+ *   r[n] = sum_{ch, o, p} sigmoid(alpha S_o) W_o / sum W_o,  HaarPSI[n] = (log(r / (1 - r)) / alpha)^2, 1 where sum W_o == 0.
+ * index: one partial of sum (sigmoid(alpha) - sigmoid(alpha S_o)) W_o and one of sum W_o per block into the workspace of
+ *   faoctasr_haarpsi_workspace_floats(planes, H, W) floats (-1 on a bad shape); no atomics.
+ * final: adds an image's partials in double in a fixed order; out_image[n] = HaarPSI[n], out_mean[0] = their mean.  fac (2, N), may be
+ *   NULL: fac[0][n] = dHaarPSI[n]/dr / sum W_o (times 1 / N when average != 0; 0 where sum W_o == 0), fac[1][n] = sigmoid(alpha) - r[n].
+ * grad: dx, dy (either may be NULL, not both) = fac[0][n] g[n or 0] d(r[n] sum W_o)/d(x|y) at fixed sum W_o and r taken from fac[1],
+ *   which is g dHaarPSI/d(x|y); g is a DEVICE array of gN floats (1 = shared, or N).  d|g|/dg = sign(g), sign(0) = 0; in max(a_3, b_3)
+ *   the gradient goes to the larger side, at equality to x.
+ * For x == y HaarPSI is exactly 1 and both gradients exactly 0; swapping x and y leaves it bit for bit and swaps the gradients. */
+long faoctasr_haarpsi_workspace_floats(long planes, int H, int W);
+int faoctasr_haarpsi_index(const float* x, const float* y, float* workspace, long planes, int H, int W, float lo, float hi, float c, float alpha,
+                           faoctasr_stream_t stream);
+int faoctasr_haarpsi_final(const float* workspace, long N, long C, int H, int W, double alpha, int average, float* out_image, float* out_mean,
+                           float* fac, faoctasr_stream_t stream);
+int faoctasr_haarpsi_grad(const float* x, const float* y, const float* fac, const float* g, int gN, float* dx, float* dy, long N, long C, int H,
+                          int W, float lo, float hi, float c, float alpha, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
