@@ -101,6 +101,10 @@ _SIG = {
     "haarpsi_index": (_I, "pp p l ii ffff p"),
     "haarpsi_final": (_I, "p ll ii d i ppp p"),
     "haarpsi_grad": (_I, "pp p p i pp ll ii ffff p"),
+    "lncc_workspace_floats": (_L, "l ii"),
+    "lncc_index": (_I, "pp p l ii i f p"),
+    "lncc_final": (_I, "p ll ii i ppp p"),
+    "lncc_grad": (_I, "pp p p i pp ll ii i f p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -2819,3 +2819,105 @@ def haarpsi(a, b, c=30.0, alpha=4.2, value_range=(-1., 1.), per_image=False):
     c, alpha, lo, hi = _haarpsi_check(a, b, c, alpha, value_range)
     grad = torch.is_grad_enabled()
     return _HaarPSI.apply(a.contiguous(), b.contiguous(), c, alpha, lo, hi, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)
+
+
+# ----------------------------------------------------------------------------------------
+# Local normalised cross-correlation (csrc/lncc.hip): the squared correlation coefficient inside a sliding box window
+# ----------------------------------------------------------------------------------------
+LNCC_MAX_WIN = 15
+
+
+def _lncc_check_scalars(win, eps):
+    """The refusals of ``lncc`` that concern no tensor; returns ``(win, eps)`` as an int and a float."""
+    if isinstance(win, bool) or not isinstance(win, int):
+        raise TypeError("win must be an integer, got %r" % (win,))
+    if not 3 <= win <= LNCC_MAX_WIN or win % 2 == 0:
+        raise ValueError("win must be odd in 3..%d, got %r" % (LNCC_MAX_WIN, win))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)):
+        raise TypeError("eps must be a number, got %r" % (eps,))
+    if not (eps > 0 and eps < float("inf")):
+        raise ValueError("eps must be positive and finite, got %r" % (eps,))
+    return int(win), float(eps)
+
+
+def _lncc_check(a, b, win, eps):
+    """Every refusal of ``lncc``, the device check last; returns ``(win, eps)``."""
+    cfg = _lncc_check_scalars(win, eps)
+    for t, what in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s" % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor, got %s" % (what, t.dtype))
+        if t.dim() != 4:
+            raise ValueError("%s must be (N, C, H, W), got %s" % (what, tuple(t.shape)))
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.numel() == 0:
+        raise ValueError("the index takes non-empty images, got %s" % (tuple(a.shape),))
+    for t, what in ((a, "a"), (b, "b")):
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    if a.device != b.device:
+        raise ValueError("a and b must be on one device, got %s and %s" % (a.device, b.device))
+    return cfg
+
+
+class _LNCC(Function):
+    """``apply(a, b, win, eps, per_image, want_a, want_b) -> LNCC``: ``lncc_index`` and ``lncc_final`` forward; where an input needs a
+    gradient the two images and the (N,) factor table are saved, and the backward is one ``lncc_grad``, which reads the upstream
+    gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, a, b, win, eps, per_image, want_a, want_b):
+        N, C, H, W = a.shape
+        dev = a.device
+        n = _lib.load().faoctasr_lncc_workspace_floats(N * C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_lncc_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "lncc")                   # per stream: consumed by the same call's second launch
+        call("lncc_index", ptr(a), ptr(b), ws.data_ptr(), N * C, H, W, win, eps, stream_ptr())
+        want = want_a or want_b
+        fac = torch.empty((N,), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = torch.empty((), dtype=torch.float32, device=dev)
+        call("lncc_final", ws.data_ptr(), N, C, H, W, int(not per_image), ptr(out_image), ptr(out_mean), ptr(fac), stream_ptr())
+        ctx.cfg = (win, eps, want_a, want_b)
+        if want:
+            ctx.save_for_backward(a, b, fac)
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        win, eps, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 7
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("lncc's forward ran without gradients enabled for this input: nothing was saved")
+        a, b, fac = ctx.saved_tensors
+        N, C, H, W = a.shape
+        g = _c(g).reshape(-1)
+        da = torch.empty_like(a) if need_a else None
+        db = torch.empty_like(b) if need_b else None
+        call("lncc_grad", ptr(a), ptr(b), ptr(fac), ptr(g), g.numel(), ptr(da), ptr(db), N, C, H, W, win, eps, stream_ptr())
+        return (da, db) + (None,) * 5
+
+
+def lncc(a, b, win=9, eps=1e-5, per_image=False):
+    """Local (windowed) normalised cross-correlation of two images ``(N, C, H, W)``: the squared correlation coefficient of the pair
+    inside a sliding ``win x win`` box.  With ``n = win^2`` and ``box(t)_p`` the sum of ``t`` over the window centred on ``p`` (samples
+    beyond the image count as 0 and the divisor is always ``n``: the zero-padded ``conv2d`` form; the window may be larger than the
+    image):
+
+        u = box(a b) - box(a) box(b) / n,   va = box(a a) - box(a)^2 / n,   vb = box(b b) - box(b)^2 / n,
+        cc_p = u^2 / (va vb + eps),   LNCC[n] = mean of cc_p over c, y, x,
+
+    the mean over n as a 0-d fp32 tensor, or ``(N,)`` with ``per_image``.  The index is invariant to an affine intensity map of either
+    image inside the window; the loss is ``1 - lncc``.  Gradients to both images, nothing is clamped.  Two launches of csrc/lncc.hip
+    forward and one backward; under ``no_grad``, or for inputs that need no gradient, nothing is saved, otherwise the two images and
+    an (N,) table.  ``lncc(x, y) == lncc(y, x)`` bit for bit with swapped gradients, halving the upstream gradient halves the
+    gradients bit for bit, and runs are bit-reproducible.  ``win`` is odd in 3..15.  As in the torch form, ``va`` is a difference of
+    two sums: precision falls where the local mean dwarfs the local contrast.  fp32, no double backward."""
+    win, eps = _lncc_check(a, b, win, eps)
+    grad = torch.is_grad_enabled()
+    return _LNCC.apply(a.contiguous(), b.contiguous(), win, eps, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)

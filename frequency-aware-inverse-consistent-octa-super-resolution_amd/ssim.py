@@ -1,5 +1,5 @@
 """SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
-same window behind the same interface (csrc/msssim.hip), and HaarPSI behind the same ``forward`` / ``index`` pair (csrc/haarpsi.hip)."""
+same window behind the same interface (csrc/msssim.hip), and HaarPSI (csrc/haarpsi.hip) and the local normalised cross-correlation (csrc/lncc.hip) behind the same ``forward`` / ``index`` pair."""
 from math import exp
 
 import torch
@@ -105,3 +105,33 @@ class HaarPSI(torch.nn.Module):
 
     def extra_repr(self):
         return "c={}, alpha={}, value_range={}, size_average={}".format(self.c, self.alpha, self.value_range, self.size_average)
+
+
+def lncc(img1, img2, win=9, eps=1e-5, size_average=True):
+    """Local normalised cross-correlation with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with ``size_average=False``
+    (``ops.lncc``)."""
+    return ops.lncc(img1, img2, win, eps, not size_average)
+
+
+class LNCC(torch.nn.Module):
+    """forward(img1, img2) -> the local normalised cross-correlation with ``SSIM``'s interface: the squared correlation coefficient of
+    the two images inside a sliding ``win x win`` box (zero padding, divisor ``win^2``), ``u^2 / (va vb + eps)`` with ``u`` the
+    windowed covariance sum and ``va``, ``vb`` the windowed variance sums, averaged over the positions and channels of an image.  It
+    does not change under an affine intensity map of either image inside the window, which makes it the spatial complement of the
+    mutual information for pairs of different contrast.  The mean over the batch, or ``(N,)`` with ``size_average=False``; the loss
+    is ``1 - LNCC``.  ``win`` odd in 3..15; fp32, no double backward (csrc/lncc.hip)."""
+
+    def __init__(self, win=9, eps=1e-5, size_average=True):
+        super().__init__()
+        self.win, self.eps = ops._lncc_check_scalars(win, eps)
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.lncc(img1, img2, self.win, self.eps, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "win={}, eps={}, size_average={}".format(self.win, self.eps, self.size_average)

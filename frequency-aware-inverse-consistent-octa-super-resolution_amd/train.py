@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
-from .ssim import MSSSIM, HaarPSI
+from .ssim import MSSSIM, HaarPSI, LNCC
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
@@ -267,7 +267,7 @@ class TrainStep:
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
                  msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
                  ffl_batch_matrix=False, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
-                 haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2):
+                 haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2, lncc_weight=0.0, lncc_win=9, lncc_eps=1e-5):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
         cores with hi/lo-split operands (16 significant bits: step-0 losses within ~1e-4 of "f32"); "f16x2" = the same kernels on
         fp16 hi/lo-split operands scaled per tensor by a power of two (22 significant bits; per-layer error against fp64 at or below
@@ -310,15 +310,21 @@ class TrainStep:
         ``mi_weight`` (default 0: nothing is constructed or launched): adds ``loss_mi = mi_weight * ((U - S(fake_B, real_A)) +
         (U - S(fake_A, real_B)))`` to ``loss_G``, S the mutual information ``MutualInformationLoss(bins=mi_bins,
         sigma_ratio=mi_sigma_ratio, normalized=mi_normalized)`` and ``U = log(mi_bins)`` (with ``mi_normalized``: 2) its upper
-        bound.  Every other opt-in term compares a reconstruction with its own input or looks at a fake alone; this one ties a fake
-        to the image of the OTHER domain it was made from, where pixelwise distances do not apply.  The gradient reaches the fake
-        only.
+        bound.  Every other opt-in term but ``lncc_weight``'s compares a reconstruction with its own input or looks at a fake alone;
+        this one ties a fake to the image of the OTHER domain it was made from, where pixelwise distances do not apply.  The
+        gradient reaches the fake only.
 
         ``haarpsi_weight`` (default 0: nothing is constructed or launched): adds ``loss_haarpsi = haarpsi_weight * ((1 -
         H(recovered_A, real_A)) + (1 - H(recovered_B, real_B)))`` to ``loss_G``, H the Haar wavelet-based perceptual similarity index
         ``HaarPSI(c=haarpsi_c, alpha=haarpsi_alpha)`` on the images' range (-1, 1): every position is weighted by the coarse-scale
         edge strength of the stronger image, so an error on a vessel wall counts and one in the background does not, and the
-        logistic of the local similarity keeps one badly wrong region from dominating."""
+        logistic of the local similarity keeps one badly wrong region from dominating.
+
+        ``lncc_weight`` (default 0: nothing is constructed or launched): adds ``loss_lncc = lncc_weight * ((1 - S(fake_B, real_A)) +
+        (1 - S(fake_A, real_B)))`` to ``loss_G``, S the local normalised cross-correlation ``LNCC(win=lncc_win, eps=lncc_eps)``: the
+        squared correlation coefficient of a fake and the image of the other domain it was made from inside a sliding box.  Where
+        the mutual information sees one joint histogram per plane, this term is spatial: a vessel that moved lowers it wherever it
+        moved, whatever the intensity map between the domains.  The gradient reaches the fake only."""
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -369,6 +375,11 @@ class TrainStep:
         #: opt-in HaarPSI term on the cycle reconstructions (ssim.HaarPSI; 0 = off, no module is built)
         self.haarpsi_weight = haarpsi_weight
         self.haarpsi = HaarPSI(c=haarpsi_c, alpha=haarpsi_alpha).to(dev) if haarpsi_weight else None
+        #: opt-in local normalised cross-correlation of each fake against its source (ssim.LNCC; 0 = off, no module is built)
+        if not (isinstance(lncc_weight, (int, float)) and math.isfinite(lncc_weight) and lncc_weight >= 0):
+            raise ValueError("lncc_weight must be a finite number >= 0, got %r" % (lncc_weight,))
+        self.lncc_weight = lncc_weight
+        self.lncc = LNCC(win=lncc_win, eps=lncc_eps).to(dev) if lncc_weight else None
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -618,6 +629,8 @@ class TrainStep:
                 extra_B["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_A"])
             if self.mi_weight:                  # likewise fake_A's mutual information with the real_B it was made from
                 extra_B["loss_mi"] = self.mi_weight * (self.mi.upper - self.mi(o["fake_A"], real_B))
+            if self.lncc_weight:                # ... and its local normalised cross-correlation with it
+                extra_B["loss_lncc"] = self.lncc_weight * (1 - self.lncc(o["fake_A"], real_B))
             for k, v in extra_B.items():
                 root = root + v
         # ---- chain A, losses and backward
@@ -632,6 +645,8 @@ class TrainStep:
                 extra_A["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_B"])
             if self.mi_weight:
                 extra_A["loss_mi"] = self.mi_weight * (self.mi.upper - self.mi(o["fake_B"], real_A))
+            if self.lncc_weight:
+                extra_A["loss_lncc"] = self.lncc_weight * (1 - self.lncc(o["fake_B"], real_A))
             for k, v in extra_A.items():
                 chain_A = chain_A + v
             ops.wgrad_stream = side
@@ -688,7 +703,8 @@ class TrainStep:
 
     def generator_loss(self, o, real_A, real_B):
         """train.py:221-236 (+ the opt-in SSIM term of the commented line train.py:234, a wavelet-HF L1 term, the spectral phase term and
-        the total-variation term of the two fakes and the mutual information of each fake with its source).  ``L["_root"]`` is
+        the total-variation term of the two fakes and the mutual information and local normalised cross-correlation of each fake with
+        its source).  ``L["_root"]`` is
         what remains to be back-propagated (everything, unless ``forward_generators`` already did the identity terms)."""
         w = self.w
         ones, _ = self.targets(real_A.shape[0])
@@ -742,6 +758,9 @@ class TrainStep:
         if self.mi_weight:
             L["loss_mi"] = self.mi_weight * ((self.mi.upper - self.mi(o["fake_B"], real_A)) + (self.mi.upper - self.mi(o["fake_A"], real_B)))
             total = total + L["loss_mi"]
+        if self.lncc_weight:
+            L["loss_lncc"] = self.lncc_weight * ((1 - self.lncc(o["fake_B"], real_A)) + (1 - self.lncc(o["fake_A"], real_B)))
+            total = total + L["loss_lncc"]
         L["_root"] = total
         L["loss_G"] = total if done is None else total.detach() + done
         return L

@@ -561,6 +561,26 @@ int faoctasr_haarpsi_final(const float* workspace, long N, long C, int H, int W,
 int faoctasr_haarpsi_grad(const float* x, const float* y, const float* fac, const float* g, int gN, float* dx, float* dy, long N, long C, int H,
                           int W, float lo, float hi, float c, float alpha, faoctasr_stream_t stream);
 
+/* ---- local normalised cross-correlation (csrc/lncc.hip) -----------------------------------------------
+ * a, b: contiguous (planes, H, W), planes = N * C.  win odd in 3..15, n = win^2, eps > 0; box(t)_p the sum of t over the win x win window
+ * centred on p, samples beyond the image 0 (the window may be larger than the image):
+ *   u = box(a b) - box(a) box(b) / n,  va = box(a a) - box(a)^2 / n,  vb = box(b b) - box(b)^2 / n,
+ *   cc_p = u^2 / (va vb + eps),  LNCC[n] = the mean of cc_p over c, y, x.
+ * index: one partial sum of cc_p per block into the workspace of faoctasr_lncc_workspace_floats(planes, H, W) floats (-1 on a bad
+ *   shape); no atomics.
+ * final: adds an image's partials in double in a fixed order; out_image[n] = LNCC[n], out_mean[0] = their mean.  fac (N), may be NULL:
+ *   fac[n] = 1 / (C H W), times 1 / N when average != 0.
+ * grad: da, db (either may be NULL, not both) = fac[n] g[n or 0] d(sum cc_p)/d(a|b), which is g dLNCC/d(a|b); g is a DEVICE array of
+ *   gN floats (1 = shared, or N).  Nothing is clamped.
+ * Swapping a and b leaves LNCC bit for bit and swaps the gradients; halving g halves them bit for bit. */
+long faoctasr_lncc_workspace_floats(long planes, int H, int W);
+int faoctasr_lncc_index(const float* a, const float* b, float* workspace, long planes, int H, int W, int win, float eps,
+                        faoctasr_stream_t stream);
+int faoctasr_lncc_final(const float* workspace, long N, long C, int H, int W, int average, float* out_image, float* out_mean, float* fac,
+                        faoctasr_stream_t stream);
+int faoctasr_lncc_grad(const float* a, const float* b, const float* fac, const float* g, int gN, float* da, float* db, long N, long C, int H,
+                       int W, int win, float eps, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
