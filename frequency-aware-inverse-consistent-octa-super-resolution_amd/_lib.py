@@ -105,6 +105,10 @@ _SIG = {
     "lncc_index": (_I, "pp p l ii i f p"),
     "lncc_final": (_I, "p ll ii i ppp p"),
     "lncc_grad": (_I, "pp p p i pp ll ii i f p"),
+    "gmsd_workspace_floats": (_L, "l ii ii"),
+    "gmsd_index": (_I, "pp pp p l ii iii fff p"),
+    "gmsd_final": (_I, "p ll ii ii p i ppp p"),
+    "gmsd_grad": (_I, "pp p p i pp pp ll ii iii fff p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -2921,3 +2921,176 @@ def lncc(a, b, win=9, eps=1e-5, per_image=False):
     win, eps = _lncc_check(a, b, win, eps)
     grad = torch.is_grad_enabled()
     return _LNCC.apply(a.contiguous(), b.contiguous(), win, eps, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)
+
+
+# ----------------------------------------------------------------------------------------
+# GMSD and multi-scale GMSD (csrc/gmsd.hip): the deviation of the Prewitt gradient-magnitude similarity map
+# ----------------------------------------------------------------------------------------
+GMSD_MAX_SCALES = 5
+#: Zhang, Shen, Wang & Li 2017
+MSGMSD_WEIGHTS = (0.096, 0.596, 0.289, 0.019)
+
+
+def _gmsd_check_scalars(c, value_range, weights=None):
+    """The refusals of ``gmsd`` and ``ms_gmsd`` that concern no tensor; returns ``(c, lo, hi, weights)``, floats and a tuple of floats
+    (``weights`` None stays None: plain GMSD has none)."""
+    if isinstance(c, bool) or not isinstance(c, (int, float)):
+        raise TypeError("c must be a number, got %r" % (c,))
+    if not (c > 0 and c < float("inf")):
+        raise ValueError("c must be positive and finite, got %r" % (c,))
+    try:
+        lo, hi = value_range
+    except (TypeError, ValueError):
+        raise TypeError("value_range must be a pair (lo, hi), got %r" % (value_range,)) from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise TypeError("value_range must hold two numbers, got %r" % (value_range,))
+    if not (hi > lo and math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("value_range must be finite with hi > lo, got %r" % (value_range,))
+    if weights is not None:
+        try:
+            weights = tuple(weights)
+        except TypeError:
+            raise TypeError("weights must be a sequence of numbers, got %r" % (weights,)) from None
+        for v in weights:
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError("weights must hold numbers, got %r" % (weights,))
+        if not 1 <= len(weights) <= GMSD_MAX_SCALES:
+            raise ValueError("weights lists one weight per scale, 1..%d of them, got %d" % (GMSD_MAX_SCALES, len(weights)))
+        if not all(v >= 0 and v < float("inf") for v in weights):
+            raise ValueError("every weight must be finite and >= 0, got %r" % (weights,))
+        if not any(v > 0 for v in weights):
+            raise ValueError("the weights must not all be zero, got %r" % (weights,))
+        weights = tuple(float(v) for v in weights)
+    return float(c), float(lo), float(hi), weights
+
+
+def _gmsd_check(a, b, c, value_range, weights=None):
+    """Every refusal of ``gmsd`` (``weights`` None) and ``ms_gmsd``, the device check last; returns ``(c, lo, hi, weights)``."""
+    cfg = _gmsd_check_scalars(c, value_range, weights)
+    for t, what in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s" % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor, got %s" % (what, t.dtype))
+        if t.dim() != 4:
+            raise ValueError("%s must be (N, C, H, W), got %s" % (what, tuple(t.shape)))
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.numel() == 0:
+        raise ValueError("the index takes non-empty images, got %s" % (tuple(a.shape),))
+    least = 2 if cfg[3] is None else 2 ** (len(cfg[3]) - 1)
+    if min(a.shape[2], a.shape[3]) < least:
+        raise ValueError("every side must be at least %d, got %d x %d" % (least, a.shape[2], a.shape[3]))
+    for t, what in ((a, "a"), (b, "b")):
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    if a.device != b.device:
+        raise ValueError("a and b must be on one device, got %s and %s" % (a.device, b.device))
+    return cfg
+
+
+class _GMSD(Function):
+    """``apply(a, b, weights, c, lo, hi, per_image, want_a, want_b) -> score``.  ``weights`` None is plain GMSD: one ``gmsd_index`` in the
+    pooled form and ``gmsd_final`` forward, one ``gmsd_grad`` backward; saved where an input needs a gradient: the two images and the
+    table.  Otherwise MS-GMSD over ``M = len(weights)`` scales: one ``gmsd_index`` per scale, which also writes the next scale's pair
+    (a scale of weight 0 takes no workspace and only pools), and ``gmsd_final``; one ``gmsd_grad`` per scale backward, coarsest first;
+    saved: additionally the pooled pairs of scales 2..M.  The backward reads the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, a, b, weights, c, lo, hi, per_image, want_a, want_b):
+        N, C, H, W = a.shape
+        dev = a.device
+        pooled = int(weights is None)
+        w = (1.0,) if pooled else weights
+        M = len(w)
+        n = _lib.load().faoctasr_gmsd_workspace_floats(N * C, H, W, M, pooled)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_gmsd_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "gmsd")                   # per stream: consumed by the same call's last launch
+        pairs = [(a, b)]
+        for j in range(M):
+            pa = pb = None
+            if j < M - 1:
+                pa = torch.empty((N, C, H >> (j + 1), W >> (j + 1)), dtype=torch.float32, device=dev)
+                pb = torch.empty_like(pa)
+                pairs.append((pa, pb))
+            call("gmsd_index", ptr(pairs[j][0]), ptr(pairs[j][1]), ptr(pa), ptr(pb), ws.data_ptr() if w[j] > 0 else None, N * C, H, W, M, j,
+                 pooled, lo, hi, c, stream_ptr())
+        want = want_a or want_b
+        table = torch.empty((2, M, N), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = torch.empty((), dtype=torch.float32, device=dev)
+        call("gmsd_final", ws.data_ptr(), N, C, H, W, M, pooled, ctypes.cast((ctypes.c_double * M)(*w), ctypes.c_void_p), int(not per_image),
+             ptr(out_image), ptr(out_mean), ptr(table), stream_ptr())
+        ctx.cfg = (M, pooled, c, lo, hi, want_a, want_b)
+        if want:
+            ctx.save_for_backward(table, *(t for p in pairs for t in p))
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        M, pooled, c, lo, hi, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 9
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("gmsd's forward ran without gradients enabled for this input: nothing was saved")
+        table, *flat = ctx.saved_tensors
+        N, C, H, W = flat[0].shape
+        g = _c(g).reshape(-1)
+        da = db = None
+        for j in range(M - 1, -1, -1):
+            aj, bj = flat[2 * j], flat[2 * j + 1]
+            dca, dcb = da, db
+            da = torch.empty_like(aj) if need_a else None
+            db = torch.empty_like(bj) if need_b else None
+            call("gmsd_grad", ptr(aj), ptr(bj), ptr(table), ptr(g), g.numel(), ptr(dca), ptr(dcb), ptr(da), ptr(db), N, C, H, W, M, j, pooled,
+                 lo, hi, c, stream_ptr())
+        return (da, db) + (None,) * 7
+
+
+_GMSD_DOC = """With ``u = (x - lo) / (hi - lo)`` for ``value_range = (lo, hi)``, ``pool(t) = avg_pool2d(t, 2)`` (floor pooling: an odd last
+    row or column is dropped) and the Prewitt gradients under zero padding 1,
+
+        gx_p = (1/3) sum_{dy = -1..1} (t[y + dy][x - 1] - t[y + dy][x + 1]),   gy_p the same on the other axis,
+        m_p = sqrt(gx_p^2 + gy_p^2) (no epsilon),   g_p = (2 ma_p mb_p + c) / (ma_p^2 + mb_p^2 + c),
+
+    ``V[n]`` is the population variance of ``g_p`` over the channels and positions of image n: channels are independent grey planes
+    pooled inside an image, there is no chroma term."""
+
+
+def gmsd(a, b, c=0.0026, value_range=(-1., 1.), per_image=False):
+    """The gradient magnitude similarity deviation (Xue, Zhang, Mou & Bovik 2014) of two images ``(N, C, H, W)``.
+    %s
+
+    ``GMSD[n] = sqrt(V[n])`` on the once-pooled pair ``pool(u_a)``, ``pool(u_b)``; ``c`` defaults to 170 / 255^2.  A distortion: 0 for
+    identical images, larger is worse; the value itself is the loss.  The mean over n as a 0-d fp32 tensor, or ``(N,)`` with
+    ``per_image``.  Gradients to both images; where ``m_p == 0`` that image's direction ``(gx, gy) / m`` is taken as ``(0, 0)``, and
+    where an image's score is 0 its gradient is exactly zero.  Two launches of csrc/gmsd.hip forward and one backward, the pooled
+    pair is never stored; under ``no_grad``, or for inputs that need no gradient, nothing is saved, otherwise the two images and a
+    (2, 1, N) table.  ``gmsd(x, y) == gmsd(y, x)`` bit for bit with swapped gradients, halving the upstream gradient halves the
+    gradients bit for bit, and runs are bit-reproducible.  Every side must be at least 2.  fp32, no double backward."""
+    c, lo, hi, _ = _gmsd_check(a, b, c, value_range)
+    grad = torch.is_grad_enabled()
+    return _GMSD.apply(a.contiguous(), b.contiguous(), None, c, lo, hi, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)
+
+
+def ms_gmsd(a, b, weights=None, c=0.0026, value_range=(-1., 1.), per_image=False):
+    """The multi-scale gradient magnitude similarity deviation (Zhang, Shen, Wang & Li 2017) of two images ``(N, C, H, W)``.
+    %s
+
+    ``MS-GMSD[n] = sqrt(sum_j w_j V_j[n])``: scale 1 is the mapped input itself and scale j + 1 is ``pool(scale j)``.  ``weights``
+    defaults to (0.096, 0.596, 0.289, 0.019); 1 <= M <= 5 weights, each finite and >= 0, not all zero; a scale of weight 0 contributes
+    exactly nothing, so ``ms_gmsd(x, y, weights=(0, 1)) == gmsd(x, y)``.  Every side must be at least ``2^(M - 1)``.  A distortion, 0
+    for identical images; the mean over n as a 0-d fp32 tensor, or ``(N,)`` with ``per_image``.  Gradients and singular points as in
+    ``gmsd``.  M + 1 launches of csrc/gmsd.hip forward and M backward; saved where an input needs a gradient: the two images, the
+    pooled pairs of scales 2..M and a (2, M, N) table.  fp32, no double backward."""
+    c, lo, hi, w = _gmsd_check(a, b, c, value_range, MSGMSD_WEIGHTS if weights is None else weights)
+    grad = torch.is_grad_enabled()
+    return _GMSD.apply(a.contiguous(), b.contiguous(), w, c, lo, hi, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)
+
+
+if gmsd.__doc__:                                              # python -OO strips docstrings
+    gmsd.__doc__ %= _GMSD_DOC
+    ms_gmsd.__doc__ %= _GMSD_DOC

@@ -1,5 +1,6 @@
 """SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
-same window behind the same interface (csrc/msssim.hip), and HaarPSI (csrc/haarpsi.hip) and the local normalised cross-correlation (csrc/lncc.hip) behind the same ``forward`` / ``index`` pair."""
+same window behind the same interface (csrc/msssim.hip), and HaarPSI (csrc/haarpsi.hip) and the local normalised cross-correlation (csrc/lncc.hip) behind the same ``forward`` / ``index`` pair,
+and GMSD and multi-scale GMSD (csrc/gmsd.hip) behind it too."""
 from math import exp
 
 import torch
@@ -135,3 +136,64 @@ class LNCC(torch.nn.Module):
 
     def extra_repr(self):
         return "win={}, eps={}, size_average={}".format(self.win, self.eps, self.size_average)
+
+
+def gmsd(img1, img2, c=0.0026, value_range=(-1., 1.), size_average=True):
+    """The gradient magnitude similarity deviation with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with
+    ``size_average=False`` (``ops.gmsd``).  A distortion: 0 for identical images."""
+    return ops.gmsd(img1, img2, c, value_range, not size_average)
+
+
+def ms_gmsd(img1, img2, weights=None, c=0.0026, value_range=(-1., 1.), size_average=True):
+    """The multi-scale gradient magnitude similarity deviation with ``ssim``'s interface (``ops.ms_gmsd``)."""
+    return ops.ms_gmsd(img1, img2, weights, c, value_range, not size_average)
+
+
+class GMSD(torch.nn.Module):
+    """forward(img1, img2) -> the gradient magnitude similarity deviation (Xue, Zhang, Mou & Bovik 2014) with ``SSIM``'s interface.  The
+    images, mapped by ``u = (x - lo) / (hi - lo)`` for ``value_range = (lo, hi)``, are pooled once by ``avg_pool2d(., 2)``; with ``ma``,
+    ``mb`` the Prewitt gradient magnitudes (zero padding 1, no epsilon) of the pooled pair, ``g_p = (2 ma mb + c) / (ma^2 + mb^2 + c)``
+    and ``GMSD[n]`` is the population standard deviation of ``g_p`` over the channels and positions of image n: it measures how
+    unevenly quality is spread over the image, where every mean-pooled index averages a local failure away.  A distortion: 0 for
+    identical images, larger is worse, and the value itself is the loss.  The mean over the batch, or ``(N,)`` with
+    ``size_average=False``.  Every side at least 2; fp32, grey planes only, no double backward (csrc/gmsd.hip)."""
+
+    def __init__(self, c=0.0026, value_range=(-1., 1.), size_average=True):
+        super().__init__()
+        self.c, lo, hi, _ = ops._gmsd_check_scalars(c, value_range)
+        self.value_range = (lo, hi)
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.gmsd(img1, img2, self.c, self.value_range, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "c={}, value_range={}, size_average={}".format(self.c, self.value_range, self.size_average)
+
+
+class MSGMSD(torch.nn.Module):
+    """forward(img1, img2) -> the multi-scale gradient magnitude similarity deviation (Zhang, Shen, Wang & Li 2017) with ``SSIM``'s
+    interface: ``sqrt(sum_j w_j V_j[n])`` with ``V_j`` the population variance of ``GMSD``'s similarity map at scale j, scale 1 the
+    mapped input itself and scale j + 1 = ``avg_pool2d(scale j, 2)``.  ``weights`` defaults to (0.096, 0.596, 0.289, 0.019); 1..5
+    weights, each finite and >= 0, not all zero; every side at least ``2^(M - 1)``.  A distortion: 0 for identical images; the value
+    itself is the loss.  The mean over the batch, or ``(N,)`` with ``size_average=False``.  fp32, no double backward (csrc/gmsd.hip)."""
+
+    def __init__(self, weights=None, c=0.0026, value_range=(-1., 1.), size_average=True):
+        super().__init__()
+        self.c, lo, hi, self.weights = ops._gmsd_check_scalars(c, value_range, ops.MSGMSD_WEIGHTS if weights is None else weights)
+        self.value_range = (lo, hi)
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.ms_gmsd(img1, img2, self.weights, self.c, self.value_range, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "weights={}, c={}, value_range={}, size_average={}".format(self.weights, self.c, self.value_range, self.size_average)

@@ -581,6 +581,35 @@ int faoctasr_lncc_final(const float* workspace, long N, long C, int H, int W, in
 int faoctasr_lncc_grad(const float* a, const float* b, const float* fac, const float* g, int gN, float* da, float* db, long N, long C, int H,
                        int W, int win, float eps, faoctasr_stream_t stream);
 
+/* ---- GMSD and multi-scale GMSD (csrc/gmsd.hip) --------------------------------------------------------
+ * a, b: contiguous (planes, H, W), planes = N * C, independent grey planes pooled inside an image.  u = (x - lo) / (hi - lo), hi > lo;
+ * pool(t) = avg_pool2d(t, 2), floor pooling.  Prewitt gradients, zero padding 1, the size of their input:
+ *   gx_p = (1/3) sum_{dy = -1..1} (t[y + dy][x - 1] - t[y + dy][x + 1]), gy_p the same on the other axis, m_p = sqrt(gx_p^2 + gy_p^2), no epsilon;
+ *   g_p = (2 ma_p mb_p + c) / (ma_p^2 + mb_p^2 + c), c > 0;  V[n] = the population variance of g_p over the channels and positions of image n.
+ * pooled != 0 (scales = 1, sides at least 2): GMSD[n] = sqrt(V[n]) on pool(u_a), pool(u_b), staged straight from a, b.
+ * pooled == 0: MS-GMSD[n] = sqrt(sum_j w_j V_j[n]) over 1 <= scales <= 5; scale 0 is the mapped input, scale j + 1 = pool(scale j), of
+ *   (H >> j) x (W >> j); sides at least 2^(scales - 1).  Both are distortions: 0 for identical images.
+ * index, once per scale: a, b are that scale's pair (the inputs themselves at scale 0 and in the pooled form); writes one partial sum of
+ *   d_p = 1 - g_p and one of d_p^2 per block into the scale's part of the workspace of faoctasr_gmsd_workspace_floats(planes, H, W, scales,
+ *   pooled) floats (-1 on a bad shape); no atomics.  next_a, next_b (both or neither; not in the pooled form, not at the last scale) take
+ *   the pair of scale + 1.  workspace NULL (a scale of weight 0): only pools.
+ * final: weights is a HOST array of `scales` doubles, each finite and >= 0, not all zero (pooled: {1}); adds the partials in double in a
+ *   fixed order, skipping scales of weight 0; out_image[n] the score, out_mean[0] their mean.  table (2, scales, N), may be NULL:
+ *   table[0][j][n] = mean of d_p, table[1][j][n] = w_j / (score[n] P_j), P_j = C h_j w_j, times 1 / N when average != 0, 0 where score[n] == 0.
+ * grad, once per scale, coarsest first: da, db (either may be NULL, not both) of that scale's size (of H x W in the pooled form) =
+ *   g[n or 0] d score[n] / d (a | b) of this scale's term plus 0.25 dca / dcb [y >> 1][x >> 1], the gradient of scale + 1 (NULL at the last
+ *   scale and in the pooled form); g is a DEVICE array of gN floats (1 = shared, or N).  Where m_p == 0 that image's direction is (0, 0);
+ *   where score[n] == 0 the gradient is exactly zero.
+ * Swapping a and b leaves the score bit for bit and swaps the gradients; halving g halves them bit for bit. */
+long faoctasr_gmsd_workspace_floats(long planes, int H, int W, int scales, int pooled);
+int faoctasr_gmsd_index(const float* a, const float* b, float* next_a, float* next_b, float* workspace, long planes, int H, int W, int scales,
+                        int scale, int pooled, float lo, float hi, float c, faoctasr_stream_t stream);
+int faoctasr_gmsd_final(const float* workspace, long N, long C, int H, int W, int scales, int pooled, const double* weights, int average,
+                        float* out_image, float* out_mean, float* table, faoctasr_stream_t stream);
+int faoctasr_gmsd_grad(const float* a, const float* b, const float* table, const float* g, int gN, const float* dca, const float* dcb, float* da,
+                       float* db, long N, long C, int H, int W, int scales, int scale, int pooled, float lo, float hi, float c,
+                       faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
