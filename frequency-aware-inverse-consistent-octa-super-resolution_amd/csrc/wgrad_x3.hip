@@ -13,11 +13,17 @@
 //     address from each lane, so a tap is a constant byte offset, and delivers to each lane its channel's 4 pixels.  Four
 //     consecutive pixels x 32 channels tile the 64 LDS banks exactly: the reads are conflict-free without swizzle, and every
 //     fragment address is one per-lane base plus an immediate.
-// Block = 256 threads, tile 64 rows (m) x 64 channels x 9 taps, pixel tile 2 rows x 32; wave (mh, cb) owns 32 rows x one
-// 32-channel block x 9 taps (144 accumulator registers).  Staging: 4x4 (channel x pixel) register blocks are converted with
-// v_cvt_pk_bf16_f32 across two CHANNELS at a time, so a pixel's four channels are already packed for one ds_write_b64.
-// The epilogue turns the accumulators ([m][channel] per tap) into dW's [m][c][t] order through LDS so that the atomics
-// into the gradient arena are contiguous runs.  LDS is single buffered (59 KiB, two blocks per CU alternate their phases).
+// Block = 512 threads, one per CU: waves 0-3 contract, waves 4-7 stage a tile ahead.  Tile 64 rows (m) x 64 channels x 9 taps,
+// pixel tile 2 rows x 32; consumer wave (mh, cb) owns 32 rows x one 32-channel block x 9 taps (144 accumulator registers).
+// Staging: 4x4 (channel x pixel) register blocks are converted with v_cvt_pk_bf16_f32 across two CHANNELS at a time, so a pixel's
+// four channels are already packed for one ds_write_b64.
+// A block walks its tiles DOWN a 32-pixel column strip (ty fastest, then tx, then n), so consecutive tiles share two of their four
+// input rows.  LDS (116 KiB): dY double buffered (2 x 18 KiB) and X as a ring of 8 patch-row slots [slot][40 px][32 ch] per channel
+// block and plane (80 KiB): a tile below its predecessor stages only its two new rows (y0 + 1, y0 + 2), the first tile of a block,
+// column or image stages all four.  Staged fp32 bytes per tile and 64 channels: 16 KiB dY + 20 KiB X instead of 16 + 40 (X3_ROLL=0
+// builds that form: two whole 4-row images, tx fastest).
+// The epilogue turns the accumulators ([m][channel] per tap) into dW's [m][c][t] order through LDS (the dY buffers, after the last
+// barrier) so that the stores into the slice's partial dW, or the atomics into the gradient arena, are contiguous runs.
 #include <type_traits>
 
 #include "common.h"
@@ -48,6 +54,19 @@ constexpr unsigned X3_CB_BYTES = X3_PPIX * 64;     // one 32-channel block of on
 constexpr unsigned X3_XPLANE = 2 * X3_CB_BYTES;    // hi plane, then lo plane
 constexpr unsigned X3_DPLANE = 64 * X3_DLD * 2;    // dY plane bytes
 constexpr unsigned X3_LDS = 2 * X3_DPLANE + 2 * X3_XPLANE;      // 18432 + 40960 = 59392
+// X3_ROLL=1: the input patch rolls through a ring of row slots, a tile below its predecessor stages only its two new rows, and a
+// block walks its tiles column-major.  X3_ROLL=0: every tile stages its four rows into one of two whole images, row-major walk.
+#ifndef X3_ROLL
+#define X3_ROLL 1
+#endif
+// Ring slots: tile i reads slots p .. p + 3 while tile i + 1 is stored -- at p + 4, p + 5 when it rolls, at p + 4 .. p + 7 when it
+// starts a column: 8 slots, and no slot is written while it is read.
+constexpr int X3_RSLOTS = 8;
+constexpr unsigned X3_RROW = X3_PCOLS * 64;                      // one patch row of one channel block and plane: 2560 B (a multiple of 256: banking unchanged)
+constexpr unsigned X3_RCB = X3_RSLOTS * X3_RROW;                 // a channel block's ring, one plane: 20480
+constexpr unsigned X3_RXPLANE = 2 * X3_RCB;                      // hi plane, then lo plane
+constexpr unsigned X3_RXBASE = 4 * X3_DPLANE;                    // behind the two dY buffers (hi, lo each)
+static_assert(X3_RXBASE + 2 * X3_RXPLANE == 2 * X3_LDS, "the ring form takes the LDS of the two-image form: one block per CU either way");
 
 template <int I, int N, class F>
 __device__ __forceinline__ void x3_static_for(F&& f) {
@@ -68,7 +87,8 @@ __device__ __forceinline__ void x3_wait_set(bf16x8& ah, bf16x8& al, bf16x4 (&bh)
 }
 
 // Wave-specialised (round 3): a 512-thread block, one per CU.  Waves 0-3 contract (wave (mh, cb): 32 rows x 32 channels x 9 taps, as
-// before), waves 4-7 stage: the LDS image is double buffered, tile i + 1 is split and stored while tile i is contracted, and the
+// before), waves 4-7 stage: the LDS image is double buffered (X3_ROLL: dY is, and X rolls through a ring of row slots with room for
+// the next tile's rows), tile i + 1 is split and stored while tile i is contracted, and the
 // loads of tile i + 2 are issued right behind that store -- a whole tile before their use.  Rounds 2's form (256 threads, two blocks
 // per CU alternating) issued a tile's loads and waited for them at once: the ~2.4 us until a burst of loads from every CU has arrived
 // (igemm_bf16x3.hip) were paid per tile and covered only by the other block's MFMAs.
@@ -127,6 +147,100 @@ __global__ __launch_bounds__(512) void wgrad_x3_kernel(const float* __restrict__
         // with the chunks on consecutive lanes; a wave's global loads still cover 8 rows x 128 contiguous bytes per instruction.
         unsigned xg_off[3], xl_off[3];
         int x_row[3], x_ck[3];
+#if X3_ROLL
+        // Ring form: item 0 = the two NEW rows (patch rows 2, 3) chunks 0..7, item 1 = chunks 8, 9 of all four rows (threads 0..127,
+        // the new rows on wave 5), item 2 = patch rows 0, 1 chunks 0..7.  A rolling tile takes item 0 and wave 5's item 1 (4 dY + 8 X
+        // loads of 16 bytes per thread at most), a column start all three; xl_off is the address in slot 0, the slot is added per tile.
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int q8 = stid & 7;
+            int cbs, row, ck;
+            if (i == 1) { ck = 8 + ((stid >> 3) & 1); cbs = (stid >> 4) & 1; row = (stid >> 5) & 3; }
+            else { ck = (stid >> 3) & 7; cbs = (stid >> 6) & 1; row = (stid >> 7) + (i == 0 ? 2 : 0); }
+            const bool use = i != 1 || stid < 128;
+            x_row[i] = use ? row : -1;
+            x_ck[i] = ck;
+            xg_off[i] = 4u * (unsigned)((cbs * 8 + q8) * 4 * (int)hw + row * g.W + 4 * ck);
+            xl_off[i] = lds0 + X3_RXBASE + (unsigned)cbs * X3_RCB + (unsigned)(4 * ck) * 64u + (unsigned)q8 * 8u;
+        }
+        int tn, ty, tx;                                                  // load cursor: ty fastest, then tx, then n
+        {
+            const long per_img = (long)g.tiles_y * g.tiles_x;
+            tn = (int)(tile0 / per_img);
+            const int r = (int)(tile0 - (long)tn * per_img);
+            tx = r / g.tiles_y;
+            ty = r - tx * g.tiles_y;
+        }
+        bool full = true;                                                // the tile in the registers stages all four rows / only rows 2, 3
+        unsigned ring = 4;                                               // slot of patch row 0 of the tile stored last (tile 0: (4 + 4) & 7 = 0)
+        f32x4 dv[2][2], xv[3][4];
+        auto load_tile = [&](bool first) {                               // the cursor's tile -> registers; cursor + 1
+            const int y0 = ty * 2, x0 = tx * 32;
+            const float* dsrc = dy + ((long)tn * g.M + m0) * hw + (long)y0 * g.W + x0;
+            const float* xsrc = x + ((long)tn * g.C + c0) * hw + (long)(y0 - 1) * g.W + (x0 - 4);
+            full = first || ty == 0;                                     // no tile directly above it in this block's walk
+            if (++ty == g.tiles_y) { ty = 0; if (++tx == g.tiles_x) { tx = 0; ++tn; } }
+            const int row_lo = full ? 0 : 2;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const char* p = reinterpret_cast<const char*>(dsrc) + dg_off[i];
+                dv[i][0] = *reinterpret_cast<const f32x4*>(p);
+                dv[i][1] = *reinterpret_cast<const f32x4*>(p + 16);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const int iy = y0 - 1 + x_row[i], gx0 = x0 - 4 + 4 * x_ck[i];
+                const bool ok = x_row[i] >= row_lo && (unsigned)iy < (unsigned)g.H && (unsigned)gx0 < (unsigned)g.W;   // zero padding: row / chunk outside
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    xv[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (ok) xv[i][c] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(xsrc + (long)c * hw) + xg_off[i]);
+                }
+            }
+        };
+        auto store_tile = [&](int buf) {                                 // registers -> (hi, lo) bf16 -> dY buffer buf, the ring's next slots
+            const unsigned bo = (unsigned)buf * (2 * X3_DPLANE);
+            ring = (ring + (full ? 4u : 2u)) & 7u;
+            const int row_lo = full ? 0 : 2;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                unsigned h0, h1, h2, h3, l0, l1, l2, l3;
+                split_pair_scaled<F16>(dv[i][0][0], dv[i][0][1], sd, h0, l0);
+                split_pair_scaled<F16>(dv[i][0][2], dv[i][0][3], sd, h1, l1);
+                split_pair_scaled<F16>(dv[i][1][0], dv[i][1][1], sd, h2, l2);
+                split_pair_scaled<F16>(dv[i][1][2], dv[i][1][3], sd, h3, l3);
+                const u32x4 hi = {h0, h1, h2, h3}, lo = {l0, l1, l2, l3};
+                const unsigned da = dl_off[i] + bo;
+                asm volatile("ds_write_b128 %0, %1" ::"v"(da), "v"(hi) : "memory");
+                asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(da), "v"(lo), "n"(X3_DPLANE) : "memory");
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                if (x_row[i] < row_lo) continue;
+                const unsigned xa = xl_off[i] + ((ring + (unsigned)x_row[i]) & 7u) * X3_RROW;
+#pragma unroll
+                for (int px = 0; px < 4; ++px) {                         // one pixel's four channels -> 8 bytes per plane
+                    unsigned h0, h1, l0, l1;
+                    split_pair_scaled<F16>(xv[i][0][px], xv[i][1][px], sx, h0, l0);
+                    split_pair_scaled<F16>(xv[i][2][px], xv[i][3][px], sx, h1, l1);
+                    const u32x2 hi = {h0, h1}, lo = {l0, l1};
+                    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(xa), "v"(hi), "n"(64 * px) : "memory");
+                    asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(xa), "v"(lo), "n"(64 * px + X3_RXPLANE) : "memory");
+                }
+            }
+        };
+        auto barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+        load_tile(true);                                                 // tile 0
+        store_tile(0);
+        if (ntl > 1) load_tile(false);                                   // tile 1
+        barrier();
+        for (int i = 0; i < ntl; ++i) {                                  // the consumers contract tile i out of dY buffer i & 1 and its four slots
+            if (i + 1 < ntl) store_tile((i + 1) & 1);                    // loaded a whole tile ago
+            if (i + 2 < ntl) load_tile(false);
+            barrier();
+        }
+        return;
+#else
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int it = stid + 256 * i;
@@ -211,6 +325,7 @@ __global__ __launch_bounds__(512) void wgrad_x3_kernel(const float* __restrict__
             barrier();
         }
         return;
+#endif
     }
 
     // ==================================================== CONSUMER ====================================================
@@ -219,7 +334,13 @@ __global__ __launch_bounds__(512) void wgrad_x3_kernel(const float* __restrict__
     const unsigned a_addr0 = lds0 + 2u * (unsigned)((mh * 32 + l31) * X3_DLD + 8 * lh);
     // B (transpose read): 16-lane group: channel half (lane >> 4) & 1, lane-in-group = 4 q + p supplies pixel row q, channels 4 p..+3
     const int gi = lane & 15, q4 = gi >> 2, p4 = gi & 3, chh = (lane >> 4) & 1;
+#if X3_ROLL
+    const unsigned b_addr0 = lds0 + X3_RXBASE + (unsigned)cb * X3_RCB + (unsigned)(8 * lh + q4) * 64u + (unsigned)(chh * 4 + p4) * 8u;   // in ring slot 0
+    int cty = (int)(tile0 % g.tiles_y);                                  // the producers' walk, followed: tile row, slot of patch row 0
+    unsigned ring = 4;
+#else
     const unsigned b_addr0 = lds0 + 2 * X3_DPLANE + (unsigned)cb * X3_CB_BYTES + (unsigned)(8 * lh + q4) * 64u + (unsigned)(chh * 4 + p4) * 8u;
+#endif
 
     f32x16 acc[9];
 #pragma unroll
@@ -229,7 +350,20 @@ __global__ __launch_bounds__(512) void wgrad_x3_kernel(const float* __restrict__
 
     asm volatile("s_barrier" ::: "memory");                             // tile 0 staged
     for (int it = 0; it < ntl; ++it) {
+#if X3_ROLL
+        const unsigned a_addr = a_addr0 + (unsigned)(it & 1) * (2 * X3_DPLANE);
+        // patch row r of this tile lives in slot (ring + r) & 7: four row bases, so that a fragment address stays base + immediate
+        ring = (ring + ((it == 0 || cty == 0) ? 4u : 2u)) & 7u;
+        if (++cty == g.tiles_y) cty = 0;
+        unsigned b_row[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            b_row[r] = b_addr0 + ((ring + (unsigned)r) & 7u) * X3_RROW;
+            asm volatile("" : "+v"(b_row[r]));                           // kept as four registers, not re-added in front of every read
+        }
+#else
         const unsigned a_addr = a_addr0 + (unsigned)(it & 1) * X3_LDS, b_addr = b_addr0 + (unsigned)(it & 1) * X3_LDS;
+#endif
         // ---- contraction: 4 k-blocks of 16 pixels x 9 taps x 3 split products ----
         // Twelve sub-steps (k-block kb, kernel row kh), each 9 MFMAs on fragment set s & 1 with the 12 transpose reads (+ the two dY
         // reads of a new k-block) of sub-step s + 1 issued two per MFMA gap into the other set (round 3; before, a sub-step's reads were
@@ -243,11 +377,16 @@ __global__ __launch_bounds__(512) void wgrad_x3_kernel(const float* __restrict__
                 if constexpr (j < 12) {
                     constexpr int kw = j >> 2, which = j & 3;
                     // pixel of k index j: row (kb >> 1) + kh, column 16 (kb & 1) + j + kw + 3 (patch column 0 = image column x0 - 4, pad 1)
-                    constexpr unsigned imm = (unsigned)(((kb >> 1) + kh) * X3_PCOLS + 16 * (kb & 1) + kw + 3) * 64u;
+#if X3_ROLL
+                    constexpr unsigned imm = (unsigned)(16 * (kb & 1) + kw + 3) * 64u, lo_plane = X3_RXPLANE;
+                    const unsigned b_addr = b_row[(kb >> 1) + kh];
+#else
+                    constexpr unsigned imm = (unsigned)(((kb >> 1) + kh) * X3_PCOLS + 16 * (kb & 1) + kw + 3) * 64u, lo_plane = X3_XPLANE;
+#endif
                     if constexpr (which == 0) x3_read_tr<imm>(bh[set][kw][0], b_addr);
                     else if constexpr (which == 1) x3_read_tr<imm + 4 * 64>(bh[set][kw][1], b_addr);
-                    else if constexpr (which == 2) x3_read_tr<imm + X3_XPLANE>(bl[set][kw][0], b_addr);
-                    else x3_read_tr<imm + 4 * 64 + X3_XPLANE>(bl[set][kw][1], b_addr);
+                    else if constexpr (which == 2) x3_read_tr<imm + lo_plane>(bl[set][kw][0], b_addr);
+                    else x3_read_tr<imm + 4 * 64 + lo_plane>(bl[set][kw][1], b_addr);
                 } else if constexpr (kh == 0) {                          // a new k-block: its dY fragments
                     constexpr unsigned a_imm = 2u * (unsigned)((kb >> 1) * 32 + 16 * (kb & 1));
                     if constexpr (j == 12) x3_read_128<a_imm>(a_hi[kb & 1], a_addr);
