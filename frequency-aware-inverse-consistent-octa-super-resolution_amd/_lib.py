@@ -109,6 +109,10 @@ _SIG = {
     "gmsd_index": (_I, "pp pp p l ii iii fff p"),
     "gmsd_final": (_I, "p ll ii ii p i ppp p"),
     "gmsd_grad": (_I, "pp p p i pp pp ll ii iii fff p"),
+    "vessel_workspace_floats": (_L, "ll ii"),
+    "vessel_index": (_I, "pp pp p ll ii pp i ffff i p"),
+    "vessel_final": (_I, "p ll ii d i ppp p"),
+    "vessel_grad": (_I, "pp pp p p i pp ll ii pp i ffff i p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

@@ -3094,3 +3094,221 @@ def ms_gmsd(a, b, weights=None, c=0.0026, value_range=(-1., 1.), per_image=False
 if gmsd.__doc__:                                              # python -OO strips docstrings
     gmsd.__doc__ %= _GMSD_DOC
     ms_gmsd.__doc__ %= _GMSD_DOC
+
+
+# ----------------------------------------------------------------------------------------
+# Hessian vesselness and the vessel Dice index (csrc/vessel.hip)
+# ----------------------------------------------------------------------------------------
+VESSEL_MAX_SCALES = 3
+VESSEL_SIGMA_RANGE = (0.5, 3.0)
+VESSEL_SIGMAS = (1., 2., 3.)
+
+
+def _vessel_number(v, what):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError("%s must be a number, got %r" % (what, v))
+    return float(v)
+
+
+def _vessel_check_scalars(sigmas, weights, beta, c, value_range, eps=0.0):
+    """The refusals of ``vesselness`` and ``vessel_dice`` that concern no tensor; returns ``(sigmas, weights, beta, c, eps, lo, hi)`` with
+    the scales of weight 0 dropped and the remaining weights normalised to sum 1."""
+    beta, c, eps = _vessel_number(beta, "beta"), _vessel_number(c, "c"), _vessel_number(eps, "eps")
+    if not (beta > 0 and beta < float("inf")):
+        raise ValueError("beta must be positive and finite, got %r" % (beta,))
+    if not (c > 0 and c < float("inf")):
+        raise ValueError("c must be positive and finite, got %r" % (c,))
+    if not (eps >= 0 and eps < float("inf")):
+        raise ValueError("eps must be finite and >= 0, got %r" % (eps,))
+    try:
+        lo, hi = value_range
+    except (TypeError, ValueError):
+        raise TypeError("value_range must be a pair (lo, hi), got %r" % (value_range,)) from None
+    lo, hi = _vessel_number(lo, "value_range's lo"), _vessel_number(hi, "value_range's hi")
+    if not (hi > lo and math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("value_range must be finite with hi > lo, got %r" % (value_range,))
+    try:
+        sigmas = tuple(sigmas)
+    except TypeError:
+        raise TypeError("sigmas must be a sequence of numbers, got %r" % (sigmas,)) from None
+    sigmas = tuple(_vessel_number(v, "every sigma") for v in sigmas)
+    if not 1 <= len(sigmas) <= VESSEL_MAX_SCALES:
+        raise ValueError("sigmas lists 1..%d scales, got %d" % (VESSEL_MAX_SCALES, len(sigmas)))
+    if not all(VESSEL_SIGMA_RANGE[0] <= v <= VESSEL_SIGMA_RANGE[1] for v in sigmas):
+        raise ValueError("every sigma must lie in [%g, %g], got %r" % (VESSEL_SIGMA_RANGE + (sigmas,)))
+    if weights is None:
+        weights = (1.0,) * len(sigmas)
+    else:
+        try:
+            weights = tuple(weights)
+        except TypeError:
+            raise TypeError("weights must be a sequence of numbers, got %r" % (weights,)) from None
+        weights = tuple(_vessel_number(v, "every weight") for v in weights)
+        if len(weights) != len(sigmas):
+            raise ValueError("weights lists one weight per scale, %d of them, got %d" % (len(sigmas), len(weights)))
+        if not all(v >= 0 and v < float("inf") for v in weights):
+            raise ValueError("every weight must be finite and >= 0, got %r" % (weights,))
+        if not any(v > 0 for v in weights):
+            raise ValueError("the weights must not all be zero, got %r" % (weights,))
+    total = math.fsum(weights)
+    kept = [(s, w / total) for s, w in zip(sigmas, weights) if w > 0]
+    return tuple(s for s, _ in kept), tuple(w for _, w in kept), beta, c, eps, lo, hi
+
+
+def _vessel_check_tensors(tensors):
+    for t, what in tensors:
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s" % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor, got %s" % (what, t.dtype))
+        if t.dim() != 4:
+            raise ValueError("%s must be (N, C, H, W), got %s" % (what, tuple(t.shape)))
+    first = tensors[0][0]
+    for t, what in tensors[1:]:
+        if t.shape != first.shape:
+            raise ValueError("%s and %s must have the same shape, got %s and %s" % (tensors[0][1], what, tuple(first.shape), tuple(t.shape)))
+    if first.numel() == 0:
+        raise ValueError("the filter takes non-empty images, got %s" % (tuple(first.shape),))
+    for t, what in tensors:
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    for t, what in tensors[1:]:
+        if t.device != first.device:
+            raise ValueError("%s and %s must be on one device, got %s and %s" % (tensors[0][1], what, first.device, t.device))
+
+
+def _vessel_arrays(sigmas, weights):
+    M = len(sigmas)
+    return (ctypes.cast((ctypes.c_double * M)(*sigmas), ctypes.c_void_p), ctypes.cast((ctypes.c_double * M)(*weights), ctypes.c_void_p), M)
+
+
+class _Vesselness(Function):
+    """``apply(x, cfg, want) -> response map``, ``cfg = (sigmas, weights, beta, c, lo, hi, bright)``.  One ``vessel_index`` in its
+    one-image form forward, one ``vessel_grad`` in its map form backward; saved where the input needs a gradient: the image."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, want):
+        sigmas, weights, beta, c, lo, hi, bright = cfg
+        N, C, H, W = x.shape
+        out = torch.empty_like(x)
+        sg, wt, M = _vessel_arrays(sigmas, weights)
+        call("vessel_index", ptr(x), None, ptr(out), None, None, N, C, H, W, sg, wt, M, beta, c, lo, hi, int(bright), stream_ptr())
+        ctx.cfg, ctx.want = cfg, want
+        if want:
+            ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        if not ctx.want:
+            raise _lib.KernelError("vesselness's forward ran without gradients enabled for this input: nothing was saved")
+        sigmas, weights, beta, c, lo, hi, bright = ctx.cfg
+        x, = ctx.saved_tensors
+        N, C, H, W = x.shape
+        g = _c(g)
+        dx = torch.empty_like(x)
+        sg, wt, M = _vessel_arrays(sigmas, weights)
+        call("vessel_grad", ptr(x), None, None, None, None, ptr(g), 0, ptr(dx), None, N, C, H, W, sg, wt, M, beta, c, lo, hi,
+             int(bright), stream_ptr())
+        return dx, None, None
+
+
+class _VesselDice(Function):
+    """``apply(a, b, cfg, eps, per_image, want_a, want_b) -> score``.  ``vessel_index`` and ``vessel_final`` forward, one ``vessel_grad``
+    backward.  Saved where an input needs a gradient: the two images, their two response maps, which ``vessel_index`` then also writes,
+    and the (2, N) table; otherwise nothing.  The backward reads the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, a, b, cfg, eps, per_image, want_a, want_b):
+        sigmas, weights, beta, c, lo, hi, bright = cfg
+        N, C, H, W = a.shape
+        dev = a.device
+        n = _lib.load().faoctasr_vessel_workspace_floats(N, C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_vessel_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "vessel")                 # per stream: consumed by the same call's last launch
+        want = want_a or want_b
+        ma = torch.empty_like(a) if want else None
+        mb = torch.empty_like(b) if want else None
+        table = torch.empty((2, N), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = None if per_image else torch.empty((), dtype=torch.float32, device=dev)
+        sg, wt, M = _vessel_arrays(sigmas, weights)
+        call("vessel_index", ptr(a), ptr(b), ptr(ma), ptr(mb), ws.data_ptr(), N, C, H, W, sg, wt, M, beta, c, lo, hi, int(bright), stream_ptr())
+        call("vessel_final", ws.data_ptr(), N, C, H, W, eps, int(not per_image), ptr(out_image), ptr(out_mean), ptr(table), stream_ptr())
+        ctx.cfg = (cfg, want_a, want_b)
+        if want:
+            ctx.save_for_backward(a, b, ma, mb, table)
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        cfg, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 7
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("vessel_dice's forward ran without gradients enabled for this input: nothing was saved")
+        sigmas, weights, beta, c, lo, hi, bright = cfg
+        a, b, ma, mb, table = ctx.saved_tensors
+        N, C, H, W = a.shape
+        g = _c(g).reshape(-1)
+        da = torch.empty_like(a) if need_a else None
+        db = torch.empty_like(b) if need_b else None
+        sg, wt, M = _vessel_arrays(sigmas, weights)
+        call("vessel_grad", ptr(a), ptr(b), ptr(ma), ptr(mb), ptr(table), ptr(g), g.numel(), ptr(da), ptr(db), N, C, H, W, sg, wt, M, beta, c,
+             lo, hi, int(bright), stream_ptr())
+        return (da, db) + (None,) * 5
+
+
+_VESSEL_DOC = """With ``u = (x - lo) / (hi - lo)`` for ``value_range = (lo, hi)`` and, per scale ``sigma``, ``R = int(3 sigma + 0.5)``, ``t = -R..R``,
+    ``g = exp(-t^2 / (2 sigma^2))`` normalised to sum 1, ``g1 = -t / sigma^2 g``, ``g2 = (t^2 / sigma^4 - 1 / sigma^2) g`` (scipy's sampled
+    kernels, nothing renormalised), the scale-normalised Hessian under zero padding is
+
+        a = sigma^2 (g2 along W, g along H) * u,   b = sigma^2 (g1, g1) * u,   d = sigma^2 (g along W, g2 along H) * u,
+
+    negated with ``bright=False`` (dark ridges).  ``m = (a + d) / 2``, ``h = (a - d) / 2``, ``r = sqrt(h^2 + b^2)``, ``kappa = r - m`` (minus
+    the most negative eigenvalue, the ridge strength), ``mu = m + r``, ``E1 = mu^2 / (2 beta^2 kappa^2)``, ``E2 = (mu^2 + kappa^2) / (2 c^2)`` and
+
+        V = exp(-E1) (1 - exp(-E2)) where kappa > 0 and E1 < 87, exactly 0 with zero gradient elsewhere;   Rsp = sum_s w_s V_s.
+
+    This is Frangi's 2-D measure wherever ``m < 0``; ordering the eigenvalues by value instead of magnitude replaces Frangi's jump to 0
+    at ``m >= 0`` by the measure's continuous extension.  The scales are summed with weights, not maximised: the gradient of a maximum
+    jumps wherever the arg-max changes.  ``sigmas``: 1 to 3 values in [0.5, 3]; ``weights`` default to equal, each finite and >= 0, not
+    all zero, normalised to sum 1; a scale of weight 0 is dropped before anything is launched.  At ``r == 0`` the direction
+    ``(h, b) / r`` is taken as ``(0, 0)``.  Channels are independent grey planes; any sides >= 1; fp32, no double backward."""
+
+
+def vesselness(x, sigmas=VESSEL_SIGMAS, weights=None, beta=0.5, c=0.1, value_range=(-1., 1.), bright=True):
+    """The multi-scale Hessian vesselness (Frangi et al. 1998, made continuous) of ``x`` ``(N, C, H, W)``: the response ``Rsp``, the shape of ``x``.
+    %s
+
+    One launch of csrc/vessel.hip forward and one backward; saved where ``x`` needs a gradient: ``x``."""
+    sigmas, weights, beta, c, _, lo, hi = _vessel_check_scalars(sigmas, weights, beta, c, value_range)
+    _vessel_check_tensors([(x, "x")])
+    want = torch.is_grad_enabled() and x.requires_grad
+    return _Vesselness.apply(x.contiguous(), (sigmas, weights, beta, c, lo, hi, bool(bright)), want)
+
+
+def vessel_dice(a, b, sigmas=VESSEL_SIGMAS, weights=None, beta=0.5, c=0.1, eps=1e-6, value_range=(-1., 1.), bright=True, per_image=False):
+    """The continuous Dice overlap of the vessel maps of two images ``(N, C, H, W)``.
+    %s
+
+    ``S[n] = (2 mean(A B) + eps) / (mean(A^2) + mean(B^2) + eps)`` with ``A = Rsp(a)``, ``B = Rsp(b)`` and the means over the channels and
+    positions of image n: ``0 < S <= 1``, 1 for identical images and for two vessel-free images; the loss is ``1 - S``.  The mean over n
+    as a 0-d fp32 tensor, or ``(N,)`` with ``per_image``.  Gradients to both images.  Two calls into csrc/vessel.hip forward
+    (``vessel_index``, ``vessel_final``) and one backward (``vessel_grad``); under ``no_grad``, or for inputs that need no gradient,
+    nothing is saved, otherwise the two images, their two response maps and a (2, N) table.  ``vessel_dice(x, y) == vessel_dice(y, x)``
+    bit for bit with swapped gradients, halving the upstream gradient halves the gradients bit for bit, and runs are bit-reproducible."""
+    sigmas, weights, beta, c, eps, lo, hi = _vessel_check_scalars(sigmas, weights, beta, c, value_range, eps)
+    _vessel_check_tensors([(a, "a"), (b, "b")])
+    grad = torch.is_grad_enabled()
+    return _VesselDice.apply(a.contiguous(), b.contiguous(), (sigmas, weights, beta, c, lo, hi, bool(bright)), eps, bool(per_image),
+                             grad and a.requires_grad, grad and b.requires_grad)
+
+
+if vesselness.__doc__:                                        # python -OO strips docstrings
+    vesselness.__doc__ %= _VESSEL_DOC
+    vessel_dice.__doc__ %= _VESSEL_DOC

@@ -1,6 +1,7 @@
 """SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
 same window behind the same interface (csrc/msssim.hip), and HaarPSI (csrc/haarpsi.hip) and the local normalised cross-correlation (csrc/lncc.hip) behind the same ``forward`` / ``index`` pair,
-and GMSD and multi-scale GMSD (csrc/gmsd.hip) behind it too."""
+and GMSD and multi-scale GMSD (csrc/gmsd.hip) behind it too, and the Hessian vesselness
+filter with its Dice index (csrc/vessel.hip)."""
 from math import exp
 
 import torch
@@ -197,3 +198,60 @@ class MSGMSD(torch.nn.Module):
 
     def extra_repr(self):
         return "weights={}, c={}, value_range={}, size_average={}".format(self.weights, self.c, self.value_range, self.size_average)
+
+
+def vessel_dice(img1, img2, sigmas=ops.VESSEL_SIGMAS, weights=None, beta=0.5, c=0.1, eps=1e-6, value_range=(-1., 1.), bright=True, size_average=True):
+    """The vessel Dice index with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with ``size_average=False``
+    (``ops.vessel_dice``).  An index: 1 for identical images."""
+    return ops.vessel_dice(img1, img2, sigmas, weights, beta, c, eps, value_range, bright, not size_average)
+
+
+class Vesselness(torch.nn.Module):
+    """forward(x) -> the multi-scale Hessian vesselness of ``x`` ``(N, C, H, W)``, the shape of ``x`` (``ops.vesselness``): Frangi's 2-D
+    ridge measure with the eigenvalues ordered by value, which extends it continuously over Frangi's cut at a non-negative trace, summed
+    over 1 to 3 scales with weights instead of maximised.  Differentiable; fp32, grey planes, zero padding (csrc/vessel.hip)."""
+
+    def __init__(self, sigmas=ops.VESSEL_SIGMAS, weights=None, beta=0.5, c=0.1, value_range=(-1., 1.), bright=True):
+        super().__init__()
+        ops._vessel_check_scalars(sigmas, weights, beta, c, value_range)
+        self.sigmas = tuple(float(v) for v in sigmas)
+        self.weights = None if weights is None else tuple(float(v) for v in weights)
+        self.beta, self.c = float(beta), float(c)
+        self.value_range = (float(value_range[0]), float(value_range[1]))
+        self.bright = bool(bright)
+
+    def forward(self, x):
+        return ops.vesselness(x, self.sigmas, self.weights, self.beta, self.c, self.value_range, self.bright)
+
+    def extra_repr(self):
+        return "sigmas={}, weights={}, beta={}, c={}, value_range={}, bright={}".format(self.sigmas, self.weights, self.beta, self.c, self.value_range,
+                                                                                       self.bright)
+
+
+class VesselDice(torch.nn.Module):
+    """forward(img1, img2) -> the continuous Dice overlap of the two images' vessel maps with ``SSIM``'s interface:
+    ``S[n] = (2 mean(A B) + eps) / (mean(A^2) + mean(B^2) + eps)`` with ``A``, ``B`` the ``Vesselness`` responses and the means over the
+    channels and positions of image n.  An index: 1 for identical images and for two vessel-free images, so the loss is
+    ``1 - VesselDice()(a, b)``.  The mean over the batch, or ``(N,)`` with ``size_average=False``.  fp32, grey planes, zero padding, no
+    double backward (csrc/vessel.hip)."""
+
+    def __init__(self, sigmas=ops.VESSEL_SIGMAS, weights=None, beta=0.5, c=0.1, eps=1e-6, value_range=(-1., 1.), bright=True, size_average=True):
+        super().__init__()
+        ops._vessel_check_scalars(sigmas, weights, beta, c, value_range, eps)
+        self.sigmas = tuple(float(v) for v in sigmas)
+        self.weights = None if weights is None else tuple(float(v) for v in weights)
+        self.beta, self.c, self.eps = float(beta), float(c), float(eps)
+        self.value_range = (float(value_range[0]), float(value_range[1]))
+        self.bright = bool(bright)
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.vessel_dice(img1, img2, self.sigmas, self.weights, self.beta, self.c, self.eps, self.value_range, self.bright, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "sigmas={}, weights={}, beta={}, c={}, eps={}, value_range={}, bright={}, size_average={}".format(
+            self.sigmas, self.weights, self.beta, self.c, self.eps, self.value_range, self.bright, self.size_average)

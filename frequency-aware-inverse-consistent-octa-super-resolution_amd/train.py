@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
-from .ssim import GMSD, MSGMSD, MSSSIM, HaarPSI, LNCC
+from .ssim import GMSD, MSGMSD, MSSSIM, HaarPSI, LNCC, VesselDice
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
@@ -267,6 +267,7 @@ class TrainStep:
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
                  msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
                  ffl_batch_matrix=False, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
+                 vessel_weight=0.0, vessel_sigmas=(1., 2., 3.), vessel_c=0.1,
                  haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2, gmsd_weight=0.0, gmsd_multiscale=False, gmsd_c=0.0026,
                  lncc_weight=0.0, lncc_win=9, lncc_eps=1e-5):
         """``precision``: "f32" = exact fp32 MFMA contraction (default); "bf16x3" = the convolutions' three GEMMs on the bf16 matrix
@@ -326,6 +327,11 @@ class TrainStep:
         ``gmsd_multiscale`` its four-scale form ``MSGMSD(c=gmsd_c)``, on the images' range (-1, 1).  G is a distortion, so the value
         itself is the term.  Every other index here ends in a mean over positions; this one is the standard deviation of the
         gradient-magnitude similarity map, so one badly reconstructed vessel junction in an otherwise good image counts.
+
+        ``vessel_weight`` (default 0: nothing is constructed or launched): adds ``loss_vessel = vessel_weight * ((1 - S(recovered_A, real_A))
+        + (1 - S(recovered_B, real_B)))`` to ``loss_G``, S the vessel Dice index ``VesselDice(sigmas=vessel_sigmas, c=vessel_c)`` on the
+        images' range (-1, 1): the overlap of the two images' Hessian ridge maps.  Every other term here pools over all pixels alike;
+        this one looks only at where the tubes are, so a capillary the generator drops or breaks counts.
 
         ``lncc_weight`` (default 0: nothing is constructed or launched): adds ``loss_lncc = lncc_weight * ((1 - S(fake_B, real_A)) +
         (1 - S(fake_A, real_B)))`` to ``loss_G``, S the local normalised cross-correlation ``LNCC(win=lncc_win, eps=lncc_eps)``: the
@@ -387,6 +393,11 @@ class TrainStep:
             raise ValueError("gmsd_weight must be a finite number >= 0, got %r" % (gmsd_weight,))
         self.gmsd_weight = gmsd_weight
         self.gmsd = ((MSGMSD(c=gmsd_c) if gmsd_multiscale else GMSD(c=gmsd_c)).to(dev)) if gmsd_weight else None
+        #: opt-in vessel Dice term on the cycle reconstructions (ssim.VesselDice; 0 = off, no module is built)
+        if not (isinstance(vessel_weight, (int, float)) and math.isfinite(vessel_weight) and vessel_weight >= 0):
+            raise ValueError("vessel_weight must be a finite number >= 0, got %r" % (vessel_weight,))
+        self.vessel_weight = vessel_weight
+        self.vessel = VesselDice(sigmas=vessel_sigmas, c=vessel_c).to(dev) if vessel_weight else None
         #: opt-in local normalised cross-correlation of each fake against its source (ssim.LNCC; 0 = off, no module is built)
         if not (isinstance(lncc_weight, (int, float)) and math.isfinite(lncc_weight) and lncc_weight >= 0):
             raise ValueError("lncc_weight must be a finite number >= 0, got %r" % (lncc_weight,))
@@ -711,6 +722,8 @@ class TrainStep:
             t["loss_haarpsi"] = self.haarpsi_weight * (1 - self.haarpsi(rec, real))
         if self.gmsd_weight:
             t["loss_gmsd"] = self.gmsd_weight * self.gmsd(rec, real)
+        if self.vessel_weight:
+            t["loss_vessel"] = self.vessel_weight * (1 - self.vessel(rec, real))
         if self.ffl_weight:
             t["loss_ffl"] = self.ffl_weight * self.ffl(rec, real)
         return t
@@ -766,6 +779,9 @@ class TrainStep:
         if self.gmsd_weight:
             L["loss_gmsd"] = self.gmsd_weight * (self.gmsd(o["recovered_A"], real_A) + self.gmsd(o["recovered_B"], real_B))
             total = total + L["loss_gmsd"]
+        if self.vessel_weight:
+            L["loss_vessel"] = self.vessel_weight * ((1 - self.vessel(o["recovered_A"], real_A)) + (1 - self.vessel(o["recovered_B"], real_B)))
+            total = total + L["loss_vessel"]
         if self.ffl_weight:
             L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))
             total = total + L["loss_ffl"]

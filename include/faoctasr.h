@@ -610,6 +610,34 @@ int faoctasr_gmsd_grad(const float* a, const float* b, const float* table, const
                        float* db, long N, long C, int H, int W, int scales, int scale, int pooled, float lo, float hi, float c,
                        faoctasr_stream_t stream);
 
+/* ---- Hessian vesselness and the vessel Dice index (csrc/vessel.hip) --------------------------------------
+ * x, y: contiguous (N, C, H, W), channels independent grey planes pooled inside an image, any sides >= 1.  u = (x - lo) / (hi - lo), hi > lo.
+ * sigmas, weights: HOST arrays of `scales` doubles (1..3), read during the call; the taps are computed from them in double and passed to
+ *   the kernel by value (nothing is allocated or copied: the launch is capturable).  Every sigma in [0.5, 3], every weight positive and
+ *   finite; the caller drops scales of weight 0 and normalises the rest to sum 1.  Per scale R = int(3 sigma + 0.5), t = -R..R,
+ *   g = exp(-t^2 / (2 sigma^2)) / sum, g1 = -t / sigma^2 g, g2 = (t^2 / sigma^4 - 1 / sigma^2) g;
+ *   a = sigma^2 (g2 along W, g along H) * u, b = sigma^2 (g1, g1) * u, d = sigma^2 (g along W, g2 along H) * u: true convolutions, zero padding;
+ *   bright == 0 negates a, b, d.  m = (a + d) / 2, h = (a - d) / 2, r = sqrt(h^2 + b^2), kappa = r - m, mu = m + r,
+ *   E1 = mu^2 / (2 beta^2 kappa^2), E2 = (mu^2 + kappa^2) / (2 c^2), V = exp(-E1) (1 - exp(-E2)) where kappa > 0 and E1 < 87, else exactly 0;
+ *   Rsp = sum_s w_s V_s;  S[n] = (2 mean(A B) + eps) / (mean(A^2) + mean(B^2) + eps) with A = Rsp(x), B = Rsp(y).
+ * index: with y, writes one partial each of A B, A^2, B^2 per block into the workspace of faoctasr_vessel_workspace_floats(N, C, H, W)
+ *   floats (-1 on a bad shape; 8-byte aligned) and, given map_x and map_y (both or neither), the two response maps the backward reads.
+ *   With y NULL (and no workspace, no map_y) it writes the response map of x into map_x: the vesselness filter.
+ * final: adds the partials in double in a fixed order, a wave per image; out_image[N]; out_mean (may be NULL) the batch mean; table (may
+ *   be NULL) [2][N]: S and 1 / (P D), P = C H W, D the denominator (times 1 / N with `average`).
+ * grad: with a table, the index's gradient: g is a DEVICE array of gN floats (1 = shared, or N); a NULL dx or dy skips that side.  With
+ *   table NULL (and y, the maps and dy NULL) the filter's: g is the upstream map, the size of x.
+ * Swapping x and y leaves the score bit for bit and swaps the gradients; halving g halves them bit for bit.  No atomics. */
+long faoctasr_vessel_workspace_floats(long N, long C, int H, int W);
+int faoctasr_vessel_index(const float* x, const float* y, float* map_x, float* map_y, float* workspace, long N, long C, int H, int W,
+                          const double* sigmas, const double* weights, int scales, float beta, float c, float lo, float hi, int bright,
+                          faoctasr_stream_t stream);
+int faoctasr_vessel_final(float* workspace, long N, long C, int H, int W, double eps, int average, float* out_image, float* out_mean,
+                          float* table, faoctasr_stream_t stream);
+int faoctasr_vessel_grad(const float* x, const float* y, const float* map_x, const float* map_y, const float* table, const float* g, int gN,
+                         float* dx, float* dy, long N, long C, int H, int W, const double* sigmas, const double* weights, int scales,
+                         float beta, float c, float lo, float hi, int bright, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
