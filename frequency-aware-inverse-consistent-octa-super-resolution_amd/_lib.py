@@ -113,6 +113,10 @@ _SIG = {
     "vessel_index": (_I, "pp pp p ll ii pp i ffff i p"),
     "vessel_final": (_I, "p ll ii d i ppp p"),
     "vessel_grad": (_I, "pp pp p p i pp ll ii pp i ffff i p"),
+    "vif_workspace_floats": (_L, "ll ii"),
+    "vif_scale_fwd": (_I, "pp pp p ll ii i fff p"),
+    "vif_final": (_I, "p ll ii i ppp p"),
+    "vif_scale_bwd": (_I, "pp p p i pp pp ll ii i fff p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

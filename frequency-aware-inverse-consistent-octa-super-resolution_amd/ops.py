@@ -3312,3 +3312,148 @@ def vessel_dice(a, b, sigmas=VESSEL_SIGMAS, weights=None, beta=0.5, c=0.1, eps=1
 if vesselness.__doc__:                                        # python -OO strips docstrings
     vesselness.__doc__ %= _VESSEL_DOC
     vessel_dice.__doc__ %= _VESSEL_DOC
+
+
+# ----------------------------------------------------------------------------------------
+# Visual information fidelity in the pixel domain (csrc/vif.hip)
+# ----------------------------------------------------------------------------------------
+VIF_SCALES = 4
+VIF_MIN_SIDE = 41
+VIF_EPS = 1e-8
+
+
+def vif_window(scale):
+    """The taps of scale ``scale``'s window as Python floats: ``K = 2^(4 - scale) + 1``, ``exp(-(k - (K-1)/2)^2 / (2 (K/5)^2))`` normalised to sum 1."""
+    K = (1 << (4 - scale)) + 1
+    v = [math.exp(-((k - (K - 1) / 2.0) ** 2) / (2.0 * (K / 5.0) ** 2)) for k in range(K)]
+    total = math.fsum(v)
+    return [t / total for t in v]
+
+
+def vif_sides(side):
+    """The sides of the four scales' images for a side of scale 0: ``side_{s+1} = (side_s - K_{s+1} + 2) // 2``."""
+    out = [int(side)]
+    for s in range(1, VIF_SCALES):
+        out.append((out[-1] - ((1 << (4 - s)) + 1) + 2) // 2)
+    return out
+
+
+def _vif_check_scalars(sigma_n_sq, value_range):
+    """The refusals of ``vif`` that concern no tensor; returns ``(sigma_n_sq, lo, hi)``."""
+    sn = _vessel_number(sigma_n_sq, "sigma_n_sq")
+    if not (sn > 0 and sn < float("inf")):
+        raise ValueError("sigma_n_sq must be positive and finite, got %r" % (sigma_n_sq,))
+    try:
+        lo, hi = value_range
+    except (TypeError, ValueError):
+        raise TypeError("value_range must be a pair (lo, hi), got %r" % (value_range,)) from None
+    lo, hi = _vessel_number(lo, "value_range's lo"), _vessel_number(hi, "value_range's hi")
+    if not (hi > lo and math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("value_range must be finite with hi > lo, got %r" % (value_range,))
+    return sn, lo, hi
+
+
+def _vif_check_tensors(a, b):
+    for t, what in ((a, "a"), (b, "b")):
+        if not torch.is_tensor(t):
+            raise TypeError("%s must be a tensor, got %s" % (what, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise TypeError("%s must be a float32 tensor, got %s" % (what, t.dtype))
+        if t.dim() != 4:
+            raise ValueError("%s must be (N, C, H, W), got %s" % (what, tuple(t.shape)))
+    if a.shape != b.shape:
+        raise ValueError("a and b must have the same shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("vif takes non-empty images, got %s" % (tuple(a.shape),))
+    if a.shape[2] < VIF_MIN_SIDE or a.shape[3] < VIF_MIN_SIDE:
+        raise ValueError("vif needs sides >= %d (one position of the coarsest scale sees %d x %d pixels), got %s"
+                         % (VIF_MIN_SIDE, VIF_MIN_SIDE, VIF_MIN_SIDE, tuple(a.shape)))
+    for t, what in ((a, "a"), (b, "b")):
+        if not t.is_cuda:
+            raise ValueError("%s must be on a GPU device, got %s" % (what, t.device))
+    if a.device != b.device:
+        raise ValueError("a and b must be on one device, got %s and %s" % (a.device, b.device))
+
+
+class _VIF(Function):
+    """``apply(a, b, sigma_n_sq, lo, hi, per_image, want_a, want_b) -> score``.  Four ``vif_scale_fwd`` and one ``vif_final`` forward, four
+    ``vif_scale_bwd`` backward, coarsest first.  Saved where an input needs a gradient: the two images, the pairs of scales 1..3, which
+    the forward writes in any case, and the (2, N) table; otherwise nothing.  The backward reads the upstream gradient on the device."""
+
+    @staticmethod
+    def forward(ctx, a, b, sn, lo, hi, per_image, want_a, want_b):
+        N, C, H, W = a.shape
+        dev = a.device
+        n = _lib.load().faoctasr_vif_workspace_floats(N, C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_vif_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "vif")                    # per stream: consumed by the same call's last launch
+        want = want_a or want_b
+        hs, wsd = vif_sides(H), vif_sides(W)
+        xs, rs = [a], [b]
+        for s in range(1, VIF_SCALES):
+            xs.append(torch.empty((N, C, hs[s], wsd[s]), dtype=torch.float32, device=dev))
+            rs.append(torch.empty((N, C, hs[s], wsd[s]), dtype=torch.float32, device=dev))
+        table = torch.empty((2, N), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = None if per_image else torch.empty((), dtype=torch.float32, device=dev)
+        for s in range(VIF_SCALES):
+            last = s == VIF_SCALES - 1
+            call("vif_scale_fwd", ptr(xs[s]), ptr(rs[s]), None if last else ptr(xs[s + 1]), None if last else ptr(rs[s + 1]), ws.data_ptr(),
+                 N, C, H, W, s, lo, hi, sn, stream_ptr())
+        call("vif_final", ws.data_ptr(), N, C, H, W, int(not per_image), ptr(out_image), ptr(out_mean), ptr(table), stream_ptr())
+        ctx.cfg = (sn, lo, hi, want_a, want_b)
+        if want:
+            ctx.save_for_backward(*(xs + rs + [table]))
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        sn, lo, hi, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 8
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("vif's forward ran without gradients enabled for this input: nothing was saved")
+        saved = ctx.saved_tensors
+        xs, rs, table = saved[:VIF_SCALES], saved[VIF_SCALES:2 * VIF_SCALES], saved[2 * VIF_SCALES]
+        N, C, H, W = xs[0].shape
+        g = _c(g).reshape(-1)
+        da = db = None
+        for s in reversed(range(VIF_SCALES)):
+            na = torch.empty_like(xs[s]) if need_a else None
+            nb = torch.empty_like(rs[s]) if need_b else None
+            call("vif_scale_bwd", ptr(xs[s]), ptr(rs[s]), ptr(table), ptr(g), g.numel(), ptr(da), ptr(db), ptr(na), ptr(nb), N, C, H, W, s,
+                 lo, hi, sn, stream_ptr())
+            da, db = na, nb
+        return (da, db) + (None,) * 6
+
+
+def vif(a, b, sigma_n_sq=2.0, value_range=(-1., 1.), per_image=False):
+    """The visual information fidelity in the pixel domain (VIFp; Sheikh & Bovik 2006) of ``a``, the image under test, against ``b``, the
+    reference, both ``(N, C, H, W)`` with ``H, W >= 41``: the Gaussian-channel information ``a`` keeps about ``b`` over the information
+    ``b`` itself carries, against a visual-noise floor ``sigma_n_sq``, at four scales.
+
+    With ``u = (t - lo) * 255 / (hi - lo)`` for ``value_range = (lo, hi)``, ``EPS = 1e-8`` and, per scale ``s = 0..3``, the window ``w_s`` of
+    ``K_s = 2^(4-s) + 1`` taps ``exp(-(k - (K_s-1)/2)^2 / (2 (K_s/5)^2))`` normalised to sum 1 and ``W_s * t`` its separable VALID convolution:
+    at ``s > 0`` both images are first filtered with the new scale's window and decimated (``[::2, ::2]``); then ``mx = W_s*x``, ``mr = W_s*r``,
+    ``sxx = relu(W_s*(x x) - mx^2)``, ``srr = relu(W_s*(r r) - mr^2)``, ``sxr = W_s*(x r) - mx mr``, ``g = sxr / (srr + EPS)``, ``sv = sxx - g sxr``,
+    and in this order: where ``srr < EPS``: ``g = 0, sv = sxx, srr = 0``; where ``sxx < EPS``: ``g = 0, sv = 0``; where ``g < 0``: ``sv = sxx, g = 0``;
+    where ``sv <= EPS``: ``sv = EPS``.
+
+        V[n] = (sum_s sum log10(1 + g^2 srr / (sv + sigma_n_sq)) + EPS) / (sum_s sum log10(1 + srr / sigma_n_sq) + EPS)
+
+    with the inner sums over the channels and positions of image n.  ``V(a, b)`` is NOT ``V(b, a)``: a reconstruction that adds contrast the
+    reference lacks can score above 1, a blurred one scores below 1, and regions whose local contrast sits below the noise floor cost
+    almost nothing.  ``V(t, t)`` is 1 up to rounding; the loss is ``1 - V``.  The mean over n as a 0-d fp32 tensor, or ``(N,)`` with
+    ``per_image``.  Gradients to both images; a ``where`` passes the gradient of the branch it took, ``relu'(0) = 0``, a clamped value
+    passes none.  Channels are independent grey planes; fp32, no double backward.
+
+    Five calls into csrc/vif.hip forward (four ``vif_scale_fwd``, ``vif_final``) and four backward (``vif_scale_bwd``, coarsest first);
+    under ``no_grad``, or for inputs that need no gradient, nothing is saved, otherwise the two images, the pairs of scales 1..3 (a third
+    of the inputs) and a (2, N) table.  Halving the upstream gradient halves the gradients bit for bit, one side's gradient has the
+    same bits with or without the other's, and runs are bit-reproducible."""
+    sn, lo, hi = _vif_check_scalars(sigma_n_sq, value_range)
+    _vif_check_tensors(a, b)
+    grad = torch.is_grad_enabled()
+    return _VIF.apply(a.contiguous(), b.contiguous(), sn, lo, hi, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)

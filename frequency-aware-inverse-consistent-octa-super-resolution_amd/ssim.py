@@ -1,7 +1,7 @@
 """SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
 same window behind the same interface (csrc/msssim.hip), and HaarPSI (csrc/haarpsi.hip) and the local normalised cross-correlation (csrc/lncc.hip) behind the same ``forward`` / ``index`` pair,
 and GMSD and multi-scale GMSD (csrc/gmsd.hip) behind it too, and the Hessian vesselness
-filter with its Dice index (csrc/vessel.hip)."""
+filter with its Dice index (csrc/vessel.hip), and the pixel-domain visual information fidelity (csrc/vif.hip)."""
 from math import exp
 
 import torch
@@ -255,3 +255,35 @@ class VesselDice(torch.nn.Module):
     def extra_repr(self):
         return "sigmas={}, weights={}, beta={}, c={}, eps={}, value_range={}, bright={}, size_average={}".format(
             self.sigmas, self.weights, self.beta, self.c, self.eps, self.value_range, self.bright, self.size_average)
+
+
+def vif(img1, img2, sigma_n_sq=2.0, value_range=(-1., 1.), size_average=True):
+    """The pixel-domain visual information fidelity of ``img1`` (the image under test) against ``img2`` (the reference) with ``ssim``'s
+    interface: the mean over the batch, or ``(N,)`` with ``size_average=False`` (``ops.vif``).  Not symmetric in its arguments."""
+    return ops.vif(img1, img2, sigma_n_sq, value_range, not size_average)
+
+
+class VIF(torch.nn.Module):
+    """forward(img1, img2) -> the visual information fidelity in the pixel domain (VIFp; Sheikh & Bovik 2006) of ``img1``, the image under
+    test, against ``img2``, the reference, with ``SSIM``'s interface: the Gaussian-channel information ``img1`` keeps about ``img2`` over
+    the information ``img2`` itself carries, against the visual-noise floor ``sigma_n_sq`` (in 0..255 units of ``value_range``), at four
+    scales.  NOT symmetric: an image that adds contrast the reference lacks can score above 1, a blurred one scores below 1; 1 up to
+    rounding for identical images, so the loss is ``1 - VIF()(x, ref)``.  The mean over the batch, or ``(N,)`` with ``size_average=False``.
+    fp32, grey planes, sides >= 41, no double backward (csrc/vif.hip)."""
+
+    def __init__(self, sigma_n_sq=2.0, value_range=(-1., 1.), size_average=True):
+        super().__init__()
+        ops._vif_check_scalars(sigma_n_sq, value_range)
+        self.sigma_n_sq = float(sigma_n_sq)
+        self.value_range = (float(value_range[0]), float(value_range[1]))
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.vif(img1, img2, self.sigma_n_sq, self.value_range, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "sigma_n_sq={}, value_range={}, size_average={}".format(self.sigma_n_sq, self.value_range, self.size_average)

@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
-from .ssim import GMSD, MSGMSD, MSSSIM, HaarPSI, LNCC, VesselDice
+from .ssim import GMSD, MSGMSD, MSSSIM, VIF, HaarPSI, LNCC, VesselDice
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
@@ -266,7 +266,7 @@ class TrainStep:
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
                  msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
-                 ffl_batch_matrix=False, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
+                 ffl_batch_matrix=False, vif_weight=0.0, vif_sigma_n_sq=2.0, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
                  vessel_weight=0.0, vessel_sigmas=(1., 2., 3.), vessel_c=0.1,
                  haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2, gmsd_weight=0.0, gmsd_multiscale=False, gmsd_c=0.0026,
                  lncc_weight=0.0, lncc_win=9, lncc_eps=1e-5):
@@ -333,6 +333,12 @@ class TrainStep:
         images' range (-1, 1): the overlap of the two images' Hessian ridge maps.  Every other term here pools over all pixels alike;
         this one looks only at where the tubes are, so a capillary the generator drops or breaks counts.
 
+        ``vif_weight`` (default 0: nothing is constructed or launched): adds ``loss_vif = vif_weight * ((1 - V(recovered_A, real_A)) +
+        (1 - V(recovered_B, real_B)))`` to ``loss_G``, V the pixel-domain visual information fidelity ``VIF(sigma_n_sq=vif_sigma_n_sq)`` on the
+        images' range (-1, 1) with the reconstruction as the image under test and the real image as the reference.  Every other index
+        here is a symmetric similarity; this one is information-theoretic and asymmetric, and its noise floor gates out regions whose
+        contrast sits below the visual noise, so an error in the vessel-free background costs almost nothing and one on a capillary a lot.
+
         ``lncc_weight`` (default 0: nothing is constructed or launched): adds ``loss_lncc = lncc_weight * ((1 - S(fake_B, real_A)) +
         (1 - S(fake_A, real_B)))`` to ``loss_G``, S the local normalised cross-correlation ``LNCC(win=lncc_win, eps=lncc_eps)``: the
         squared correlation coefficient of a fake and the image of the other domain it was made from inside a sliding box.  Where
@@ -398,6 +404,13 @@ class TrainStep:
             raise ValueError("vessel_weight must be a finite number >= 0, got %r" % (vessel_weight,))
         self.vessel_weight = vessel_weight
         self.vessel = VesselDice(sigmas=vessel_sigmas, c=vessel_c).to(dev) if vessel_weight else None
+        #: opt-in visual information fidelity term on the cycle reconstructions (ssim.VIF; 0 = off, no module is built)
+        if not (isinstance(vif_weight, (int, float)) and not isinstance(vif_weight, bool) and math.isfinite(vif_weight) and vif_weight >= 0):
+            raise ValueError("vif_weight must be a finite number >= 0, got %r" % (vif_weight,))
+        if not (isinstance(vif_sigma_n_sq, (int, float)) and not isinstance(vif_sigma_n_sq, bool) and math.isfinite(vif_sigma_n_sq) and vif_sigma_n_sq > 0):
+            raise ValueError("vif_sigma_n_sq must be a finite number > 0, got %r" % (vif_sigma_n_sq,))
+        self.vif_weight = vif_weight
+        self.vif = VIF(sigma_n_sq=vif_sigma_n_sq).to(dev) if vif_weight else None
         #: opt-in local normalised cross-correlation of each fake against its source (ssim.LNCC; 0 = off, no module is built)
         if not (isinstance(lncc_weight, (int, float)) and math.isfinite(lncc_weight) and lncc_weight >= 0):
             raise ValueError("lncc_weight must be a finite number >= 0, got %r" % (lncc_weight,))
@@ -724,6 +737,8 @@ class TrainStep:
             t["loss_gmsd"] = self.gmsd_weight * self.gmsd(rec, real)
         if self.vessel_weight:
             t["loss_vessel"] = self.vessel_weight * (1 - self.vessel(rec, real))
+        if self.vif_weight:
+            t["loss_vif"] = self.vif_weight * (1 - self.vif(rec, real))
         if self.ffl_weight:
             t["loss_ffl"] = self.ffl_weight * self.ffl(rec, real)
         return t
@@ -782,6 +797,9 @@ class TrainStep:
         if self.vessel_weight:
             L["loss_vessel"] = self.vessel_weight * ((1 - self.vessel(o["recovered_A"], real_A)) + (1 - self.vessel(o["recovered_B"], real_B)))
             total = total + L["loss_vessel"]
+        if self.vif_weight:
+            L["loss_vif"] = self.vif_weight * ((1 - self.vif(o["recovered_A"], real_A)) + (1 - self.vif(o["recovered_B"], real_B)))
+            total = total + L["loss_vif"]
         if self.ffl_weight:
             L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))
             total = total + L["loss_ffl"]

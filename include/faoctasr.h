@@ -638,6 +638,34 @@ int faoctasr_vessel_grad(const float* x, const float* y, const float* map_x, con
                          float* dx, float* dy, long N, long C, int H, int W, const double* sigmas, const double* weights, int scales,
                          float beta, float c, float lo, float hi, int bright, faoctasr_stream_t stream);
 
+/* ---- visual information fidelity, pixel domain (VIFp; csrc/vif.hip) ---------------------------------------
+ * x (the image under test), r (the reference): contiguous (N, C, H, W), H, W >= 41, channels independent grey planes pooled inside an
+ * image.  u = (t - lo) * 255 / (hi - lo), hi > lo; EPS = 1e-8; sigma_n_sq finite and > 0.  Scale s = 0..3: K_s = 2^(4-s) + 1,
+ *   w_s[k] = exp(-(k - (K_s-1)/2)^2 / (2 (K_s/5)^2)) / sum (computed in double during the call, passed to the kernel by value: nothing is
+ *   allocated or copied, every launch is capturable); W_s * t the separable VALID convolution; at s > 0 x_s = (W_s * x_{s-1})[::2, ::2], r_s
+ *   likewise.  mx = W_s*x_s, mr = W_s*r_s, sxx = relu(W_s*(x_s x_s) - mx^2), srr = relu(W_s*(r_s r_s) - mr^2), sxr = W_s*(x_s r_s) - mx mr,
+ *   g = sxr / (srr + EPS), sv = sxx - g sxr, then in this order: srr < EPS: g = 0, sv = sxx, srr = 0; sxx < EPS: g = 0, sv = 0;
+ *   g < 0: sv = sxx, g = 0; sv <= EPS: sv = EPS.  num_s[n] = sum log10(1 + g^2 srr / (sv + sigma_n_sq)), den_s[n] = sum log10(1 + srr / sigma_n_sq);
+ *   V[n] = (sum_s num_s + EPS) / (sum_s den_s + EPS).  V(x, r) is NOT V(r, x).
+ * H, W are always the sides of scale 0; the sides of scale s + 1 are (side_s - K_{s+1} + 2) / 2.
+ * scale_fwd, once per scale in any order after the scale's pair exists: x, r are the pair of that scale (scale 0: the inputs, mapped
+ *   inside); writes one partial of num and one of den per block into the workspace of faoctasr_vif_workspace_floats(N, C, H, W) floats
+ *   (-1 on a bad shape) and, at scales 0..2, the pair of the next scale into next_x, next_r (NULL at scale 3).
+ * final: adds an image's partials in double in a fixed order, a wave per image; out_image[N]; out_mean (may be NULL) the batch mean,
+ *   from the same launch; table (may be NULL) [2][N]: 1 / ((den + EPS) ln 10) and V / ((den + EPS) ln 10), times 1 / N with `average`.
+ * scale_bwd, once per scale, coarsest first: x, r the pair of that scale, g a DEVICE array of gN floats (1 = shared, or N), dnext_x /
+ *   dnext_r the gradients scale + 1 wrote (NULL at scale 3); writes the gradient with respect to that scale's pair, at scale 0 that of
+ *   the inputs.  A NULL dx or dr skips that side (its dnext is then NULL too).
+ * Halving g halves the gradients bit for bit; one side's gradient has the same bits with or without the other.  No atomics. */
+long faoctasr_vif_workspace_floats(long N, long C, int H, int W);
+int faoctasr_vif_scale_fwd(const float* x, const float* r, float* next_x, float* next_r, float* workspace, long N, long C, int H, int W,
+                           int scale, float lo, float hi, float sigma_n_sq, faoctasr_stream_t stream);
+int faoctasr_vif_final(const float* workspace, long N, long C, int H, int W, int average, float* out_image, float* out_mean, float* table,
+                       faoctasr_stream_t stream);
+int faoctasr_vif_scale_bwd(const float* x, const float* r, const float* table, const float* g, int gN, const float* dnext_x,
+                           const float* dnext_r, float* dx, float* dr, long N, long C, int H, int W, int scale, float lo, float hi,
+                           float sigma_n_sq, faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
