@@ -117,6 +117,10 @@ _SIG = {
     "vif_scale_fwd": (_I, "pp pp p ll ii i fff p"),
     "vif_final": (_I, "p ll ii i ppp p"),
     "vif_scale_bwd": (_I, "pp p p i pp pp ll ii i fff p"),
+    "cldice_workspace_floats": (_L, "ll ii"),
+    "cldice_index": (_I, "pp pp pp pp p ll ii i ff i p"),
+    "cldice_final": (_I, "p ll ii d i ppp p"),
+    "cldice_grad": (_I, "pp pp pp pp p p i pp ll ii i ff i p"),
     "loss_workspace_floats": (_L, ""),
     "loss_fwd": (_I, "ppp l i f p p"),
     "loss_bwd": (_I, "pppp l i f i p"),

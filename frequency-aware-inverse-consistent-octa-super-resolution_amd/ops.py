@@ -3457,3 +3457,176 @@ def vif(a, b, sigma_n_sq=2.0, value_range=(-1., 1.), per_image=False):
     _vif_check_tensors(a, b)
     grad = torch.is_grad_enabled()
     return _VIF.apply(a.contiguous(), b.contiguous(), sn, lo, hi, bool(per_image), grad and a.requires_grad, grad and b.requires_grad)
+
+
+# ----------------------------------------------------------------------------------------
+# Soft skeletons and soft-clDice (csrc/cldice.hip)
+# ----------------------------------------------------------------------------------------
+CLDICE_MAX_ITERS = 10
+
+
+def _cldice_check_scalars(iters, value_range, smooth=0.0):
+    """The refusals of ``soft_skeleton`` and ``cldice`` that concern no tensor; returns ``(iters, smooth, lo, hi)``."""
+    if isinstance(iters, bool) or not isinstance(iters, int):
+        raise TypeError("iters must be an integer, got %r" % (iters,))
+    if not 1 <= iters <= CLDICE_MAX_ITERS:
+        raise ValueError("iters must lie in 1..%d (the halo of iters + 2 is staged in LDS), got %d" % (CLDICE_MAX_ITERS, iters))
+    smooth = _vessel_number(smooth, "smooth")
+    if not (smooth >= 0 and smooth < float("inf")):
+        raise ValueError("smooth must be finite and >= 0, got %r" % (smooth,))
+    try:
+        lo, hi = value_range
+    except (TypeError, ValueError):
+        raise TypeError("value_range must be a pair (lo, hi), got %r" % (value_range,)) from None
+    lo, hi = _vessel_number(lo, "value_range's lo"), _vessel_number(hi, "value_range's hi")
+    if not (hi > lo and math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError("value_range must be finite with hi > lo, got %r" % (value_range,))
+    return iters, smooth, lo, hi
+
+
+def _cldice_records(like, iters):
+    """The records of one image: ``iters + 1`` coefficient maps and as many maps of selection bytes, 5 (iters + 1) bytes per sample."""
+    return (torch.empty((iters + 1,) + tuple(like.shape), dtype=torch.float32, device=like.device),
+            torch.empty((iters + 1,) + tuple(like.shape), dtype=torch.uint8, device=like.device))
+
+
+class _SoftSkeleton(Function):
+    """``apply(x, iters, lo, hi, bright, want) -> skeleton map``.  One ``cldice_index`` in its one-image form forward, one ``cldice_grad``
+    in its map form backward; saved where the input needs a gradient: its records (``_cldice_records``), not the image."""
+
+    @staticmethod
+    def forward(ctx, x, iters, lo, hi, bright, want):
+        N, C, H, W = x.shape
+        out = torch.empty_like(x)
+        rec, sel = _cldice_records(x, iters) if want else (None, None)
+        call("cldice_index", ptr(x), None, ptr(out), None, ptr(rec), None if sel is None else sel.data_ptr(), None, None, None, N, C, H, W, iters,
+             lo, hi, int(bright), stream_ptr())
+        ctx.cfg = (iters, lo, hi, bright, want)
+        if want:
+            ctx.save_for_backward(rec, sel)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 6
+        iters, lo, hi, bright, want = ctx.cfg
+        if not want:
+            raise _lib.KernelError("soft_skeleton's forward ran without gradients enabled for this input: nothing was saved")
+        rec, sel = ctx.saved_tensors
+        _, N, C, H, W = rec.shape
+        g = _c(g)
+        dx = torch.empty_like(g)
+        call("cldice_grad", None, None, ptr(rec), sel.data_ptr(), None, None, None, None, None, ptr(g), 0, ptr(dx), None, N, C, H, W, iters, lo, hi,
+             int(bright), stream_ptr())
+        return (dx,) + (None,) * 5
+
+
+class _ClDice(Function):
+    """``apply(a, b, iters, smooth, lo, hi, bright, per_image, want_a, want_b) -> score``.  ``cldice_index`` and ``cldice_final`` forward, one
+    ``cldice_grad`` backward.  Saved per input that needs a gradient: its records and the other image's skeleton map, which ``cldice_index``
+    then also writes, besides the two images and the (4, N) table; otherwise nothing.  The backward reads the upstream gradient on the
+    device."""
+
+    @staticmethod
+    def forward(ctx, a, b, iters, smooth, lo, hi, bright, per_image, want_a, want_b):
+        N, C, H, W = a.shape
+        dev = a.device
+        n = _lib.load().faoctasr_cldice_workspace_floats(N, C, H, W)
+        if n < 0:
+            raise _lib.KernelError("faoctasr_cldice_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+        ws = _lib.workspace(dev, n, "cldice")                 # per stream: consumed by the same call's last launch
+        want = want_a or want_b
+        rec_a, sel_a = _cldice_records(a, iters) if want_a else (None, None)
+        rec_b, sel_b = _cldice_records(b, iters) if want_b else (None, None)
+        skel_a = torch.empty_like(a) if want_b else None
+        skel_b = torch.empty_like(b) if want_a else None
+        table = torch.empty((4, N), dtype=torch.float32, device=dev) if want else None
+        out_image = torch.empty((N,), dtype=torch.float32, device=dev)
+        out_mean = None if per_image else torch.empty((), dtype=torch.float32, device=dev)
+        call("cldice_index", ptr(a), ptr(b), ptr(skel_a), ptr(skel_b), ptr(rec_a), None if sel_a is None else sel_a.data_ptr(), ptr(rec_b),
+             None if sel_b is None else sel_b.data_ptr(), ws.data_ptr(), N, C, H, W, iters, lo, hi, int(bright), stream_ptr())
+        call("cldice_final", ws.data_ptr(), N, C, H, W, smooth, int(not per_image), ptr(out_image), ptr(out_mean), ptr(table), stream_ptr())
+        ctx.cfg = (iters, lo, hi, bright, want_a, want_b)
+        if want:
+            ctx.save_for_backward(*[t for t in (a, b, table, rec_a, sel_a, skel_b, rec_b, sel_b, skel_a) if t is not None])
+        return out_image if per_image else out_mean
+
+    @staticmethod
+    def backward(ctx, g):
+        iters, lo, hi, bright, want_a, want_b = ctx.cfg
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return (None,) * 10
+        if (need_a and not want_a) or (need_b and not want_b):
+            raise _lib.KernelError("cldice's forward ran without gradients enabled for this input: nothing was saved")
+        saved = list(ctx.saved_tensors)
+        a, b, table = saved[:3]
+        rest = saved[3:]
+        rec_a, sel_a, skel_b = rest[:3] if want_a else (None, None, None)
+        rec_b, sel_b, skel_a = rest[3 if want_a else 0:][:3] if want_b else (None, None, None)
+        N, C, H, W = a.shape
+        g = _c(g).reshape(-1)
+        da = torch.empty_like(a) if need_a else None
+        db = torch.empty_like(b) if need_b else None
+        call("cldice_grad", ptr(a), ptr(b), ptr(rec_a), None if sel_a is None else sel_a.data_ptr(), ptr(rec_b),
+             None if sel_b is None else sel_b.data_ptr(), ptr(skel_a), ptr(skel_b), ptr(table), ptr(g), g.numel(), ptr(da), ptr(db), N, C, H, W,
+             iters, lo, hi, int(bright), stream_ptr())
+        return (da, db) + (None,) * 8
+
+
+_CLDICE_DOC = """With ``u = (x - lo) / (hi - lo)`` for ``value_range = (lo, hi)`` (``(hi - x) / (hi - lo)`` with ``bright=False``: dark vessels), ``E(I)[q]`` the
+    minimum of ``I`` over the 5-point cross around ``q`` and ``D(I)[q]`` the maximum over the 3 x 3 square, positions outside the image left out
+    (``max_pool2d`` with its implicit padding), and ``K = iters``:
+
+        I_0 = u,  I_{k+1} = E(I_k),  O_k = D(I_{k+1}),  delta_k = relu(I_k - O_k),  k = 0..K
+        s_0 = delta_0,  s_k = s_{k-1} + relu(delta_k - s_{k-1} delta_k),  skel(u) = s_K
+
+    the soft skeleton of Shit et al. (CVPR 2021).  ``iters`` is an integer in 1..10 (the authors' default is 3; for retinal vessels they
+    go up to the largest vessel radius in pixels; the limit is the halo of ``iters + 2`` the kernels keep in LDS).  ``relu'(0) = 0``.
+    Ties: the result does not depend on which of several equal values a minimum or maximum takes; the gradient sends the whole
+    cotangent to the FIRST of the tied positions in row-major order (cross: up, left, centre, right, down; square: top-left to
+    bottom-right).  That is a valid subgradient and conserves the total; where the values of a plane are distinct it is the gradient,
+    and on plateaus (a quantised image, the exact zeros of a vesselness map) it differs from ``max_pool2d``'s backward, whose choice
+    depends on its scan order.  Channels are independent grey planes; any sides >= 1; finite inputs; fp32, no double backward."""
+
+
+def soft_skeleton(x, iters=3, value_range=(-1., 1.), bright=True):
+    """The soft skeleton of ``x`` ``(N, C, H, W)`` by iterated min / max pooling: a map the shape of ``x``, differentiable.
+    %s
+
+    One launch of csrc/cldice.hip forward and one backward; saved where ``x`` needs a gradient: 5 (iters + 1) bytes per sample (per level
+    one coefficient and one selection byte), by which the backward routes an arbitrary upstream map."""
+    iters, _, lo, hi = _cldice_check_scalars(iters, value_range)
+    _vessel_check_tensors([(x, "x")])
+    want = torch.is_grad_enabled() and x.requires_grad
+    return _SoftSkeleton.apply(x.contiguous(), iters, lo, hi, bool(bright), want)
+
+
+def cldice(a, b, iters=3, smooth=1.0, value_range=(-1., 1.), bright=True, per_image=False):
+    """Soft-clDice, the centre-line Dice of two images ``(N, C, H, W)``: how much of each image's soft skeleton lies inside the other image.
+    %s
+
+    Per image n, the sums over its channels and positions:
+
+        Tprec = (sum skel(a) u_b + smooth) / (sum skel(a) + smooth),   Tsens = (sum skel(b) u_a + smooth) / (sum skel(b) + smooth)
+        S[n] = 2 Tprec Tsens / (Tprec + Tsens), 0 where that denominator is 0; a ratio whose own denominator is 0 is taken as 0
+
+    ``smooth >= 0`` acts on sums, not means, as in the authors' code; unlike theirs the sums run per image and the batch is averaged, as
+    every index here does.  The loss is ``1 - S``.  The mean over n as a 0-d fp32 tensor, or ``(N,)`` with ``per_image``.  Gradients to
+    both images.  Two calls into csrc/cldice.hip forward (``cldice_index``, ``cldice_final``) and one backward (``cldice_grad``); under
+    ``no_grad``, or for inputs that need no gradient, nothing is saved, otherwise the two images, a (4, N) table and per input that
+    needs a gradient its 5 (iters + 1) bytes per sample of records and the other image's skeleton map.  ``cldice(x, y) == cldice(y, x)``
+    bit for bit with swapped gradients, halving the upstream gradient halves the gradients bit for bit, one side's gradient has the
+    same bits with or without the other's, and runs are bit-reproducible.  On vessel maps: ``cldice(vesselness(x), vesselness(y),
+    value_range=(0, 1))`` composes through autograd; such maps hold regions of exactly 0, plateaus on which the tie rule above applies."""
+    iters, smooth, lo, hi = _cldice_check_scalars(iters, value_range, smooth)
+    _vessel_check_tensors([(a, "a"), (b, "b")])
+    grad = torch.is_grad_enabled()
+    return _ClDice.apply(a.contiguous(), b.contiguous(), iters, smooth, lo, hi, bool(bright), bool(per_image), grad and a.requires_grad,
+                         grad and b.requires_grad)
+
+
+if soft_skeleton.__doc__:                                     # python -OO strips docstrings
+    soft_skeleton.__doc__ %= _CLDICE_DOC
+    cldice.__doc__ %= _CLDICE_DOC

@@ -1,7 +1,8 @@
 """SSIM behind the reference's ``ssim.py`` interface (ssim.py:7-73) on one fused separable HIP kernel, and multi-scale SSIM on the
 same window behind the same interface (csrc/msssim.hip), and HaarPSI (csrc/haarpsi.hip) and the local normalised cross-correlation (csrc/lncc.hip) behind the same ``forward`` / ``index`` pair,
 and GMSD and multi-scale GMSD (csrc/gmsd.hip) behind it too, and the Hessian vesselness
-filter with its Dice index (csrc/vessel.hip), and the pixel-domain visual information fidelity (csrc/vif.hip)."""
+filter with its Dice index (csrc/vessel.hip), the pixel-domain visual information fidelity (csrc/vif.hip), and the soft skeleton
+with soft-clDice (csrc/cldice.hip)."""
 from math import exp
 
 import torch
@@ -287,3 +288,57 @@ class VIF(torch.nn.Module):
 
     def extra_repr(self):
         return "sigma_n_sq={}, value_range={}, size_average={}".format(self.sigma_n_sq, self.value_range, self.size_average)
+
+
+def cldice(img1, img2, iters=3, smooth=1.0, value_range=(-1., 1.), bright=True, size_average=True):
+    """The soft-clDice index with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with ``size_average=False``
+    (``ops.cldice``).  An index: the loss is ``1 - cldice(...)``."""
+    return ops.cldice(img1, img2, iters, smooth, value_range, bright, not size_average)
+
+
+class SoftSkeleton(torch.nn.Module):
+    """forward(x) -> the soft skeleton of ``x`` ``(N, C, H, W)``, the shape of ``x`` (``ops.soft_skeleton``): ``iters`` rounds of min pooling
+    over the 5-point cross, each followed by a 3 x 3 max pooling, keep what an opening removes (Shit et al., CVPR 2021).  ``iters`` in
+    1..10.  Differentiable, with the tie rule of ``ops.soft_skeleton``; fp32, grey planes (csrc/cldice.hip)."""
+
+    def __init__(self, iters=3, value_range=(-1., 1.), bright=True):
+        super().__init__()
+        ops._cldice_check_scalars(iters, value_range)
+        self.iters = iters
+        self.value_range = (float(value_range[0]), float(value_range[1]))
+        self.bright = bool(bright)
+
+    def forward(self, x):
+        return ops.soft_skeleton(x, self.iters, self.value_range, self.bright)
+
+    def extra_repr(self):
+        return "iters={}, value_range={}, bright={}".format(self.iters, self.value_range, self.bright)
+
+
+class SoftClDice(torch.nn.Module):
+    """The soft centre-line Dice (soft-clDice; Shit et al., CVPR 2021) of two images: per image, the harmonic mean of
+    ``Tprec = (sum skel(img1) u2 + smooth) / (sum skel(img1) + smooth)`` and ``Tsens = (sum skel(img2) u1 + smooth) / (sum skel(img2) + smooth)``,
+    ``skel`` the ``SoftSkeleton`` and ``u`` the image mapped to [0, 1].  It rewards connected centre lines, not overlapping area: a
+    capillary broken for a few pixels loses its skeleton there.  ``index(img1, img2, per_image)`` is the index ``S``; ``forward`` is the
+    LOSS ``1 - S``, the mean over the batch or ``(N,)`` with ``size_average=False``.  ``iters`` in 1..10; fp32, grey planes, no double
+    backward; on plateaus the gradient follows the tie rule of ``ops.cldice`` (csrc/cldice.hip)."""
+
+    def __init__(self, iters=3, smooth=1.0, value_range=(-1., 1.), bright=True, size_average=True):
+        super().__init__()
+        ops._cldice_check_scalars(iters, value_range, smooth)
+        self.iters = iters
+        self.smooth = float(smooth)
+        self.value_range = (float(value_range[0]), float(value_range[1]))
+        self.bright = bool(bright)
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index ``S`` with ``per_image`` as given instead of ``not size_average``."""
+        return ops.cldice(img1, img2, self.iters, self.smooth, self.value_range, self.bright, per_image)
+
+    def forward(self, img1, img2):
+        return 1 - self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "iters={}, smooth={}, value_range={}, bright={}, size_average={}".format(self.iters, self.smooth, self.value_range, self.bright,
+                                                                                    self.size_average)

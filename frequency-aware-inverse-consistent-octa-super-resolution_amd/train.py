@@ -19,7 +19,7 @@ import torch.distributed as dist
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
 from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
-from .ssim import GMSD, MSGMSD, MSSSIM, VIF, HaarPSI, LNCC, VesselDice
+from .ssim import GMSD, MSGMSD, MSSSIM, VIF, HaarPSI, LNCC, SoftClDice, VesselDice
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
 
@@ -265,7 +265,7 @@ class TrainStep:
                  reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
-                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
+                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None, cldice_weight=0.0, cldice_iters=3, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
                  ffl_batch_matrix=False, vif_weight=0.0, vif_sigma_n_sq=2.0, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
                  vessel_weight=0.0, vessel_sigmas=(1., 2., 3.), vessel_c=0.1,
                  haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2, gmsd_weight=0.0, gmsd_multiscale=False, gmsd_c=0.0026,
@@ -339,6 +339,12 @@ class TrainStep:
         here is a symmetric similarity; this one is information-theoretic and asymmetric, and its noise floor gates out regions whose
         contrast sits below the visual noise, so an error in the vessel-free background costs almost nothing and one on a capillary a lot.
 
+        ``cldice_weight`` (default 0: nothing is constructed or launched): adds ``loss_cldice = cldice_weight * ((1 - S(recovered_A, real_A))
+        + (1 - S(recovered_B, real_B)))`` to ``loss_G``, S the soft centre-line Dice ``SoftClDice(iters=cldice_iters).index`` on the images'
+        range (-1, 1): how much of each image's soft skeleton lies inside the other image.  The vessel Dice term counts overlapping
+        area, so a capillary broken for three pixels loses three pixels' worth; this one counts centre lines, so the break costs the
+        connection.  ``cldice_iters`` in 1..10, at most the largest vessel radius in pixels.
+
         ``lncc_weight`` (default 0: nothing is constructed or launched): adds ``loss_lncc = lncc_weight * ((1 - S(fake_B, real_A)) +
         (1 - S(fake_A, real_B)))`` to ``loss_G``, S the local normalised cross-correlation ``LNCC(win=lncc_win, eps=lncc_eps)``: the
         squared correlation coefficient of a fake and the image of the other domain it was made from inside a sliding box.  Where
@@ -411,6 +417,11 @@ class TrainStep:
             raise ValueError("vif_sigma_n_sq must be a finite number > 0, got %r" % (vif_sigma_n_sq,))
         self.vif_weight = vif_weight
         self.vif = VIF(sigma_n_sq=vif_sigma_n_sq).to(dev) if vif_weight else None
+        #: opt-in soft-clDice term on the cycle reconstructions (ssim.SoftClDice; 0 = off, no module is built)
+        if not (isinstance(cldice_weight, (int, float)) and not isinstance(cldice_weight, bool) and math.isfinite(cldice_weight) and cldice_weight >= 0):
+            raise ValueError("cldice_weight must be a finite number >= 0, got %r" % (cldice_weight,))
+        self.cldice_weight = cldice_weight
+        self.cldice = SoftClDice(iters=cldice_iters).to(dev) if cldice_weight else None
         #: opt-in local normalised cross-correlation of each fake against its source (ssim.LNCC; 0 = off, no module is built)
         if not (isinstance(lncc_weight, (int, float)) and math.isfinite(lncc_weight) and lncc_weight >= 0):
             raise ValueError("lncc_weight must be a finite number >= 0, got %r" % (lncc_weight,))
@@ -739,6 +750,8 @@ class TrainStep:
             t["loss_vessel"] = self.vessel_weight * (1 - self.vessel(rec, real))
         if self.vif_weight:
             t["loss_vif"] = self.vif_weight * (1 - self.vif(rec, real))
+        if self.cldice_weight:
+            t["loss_cldice"] = self.cldice_weight * self.cldice(rec, real)
         if self.ffl_weight:
             t["loss_ffl"] = self.ffl_weight * self.ffl(rec, real)
         return t
@@ -800,6 +813,9 @@ class TrainStep:
         if self.vif_weight:
             L["loss_vif"] = self.vif_weight * ((1 - self.vif(o["recovered_A"], real_A)) + (1 - self.vif(o["recovered_B"], real_B)))
             total = total + L["loss_vif"]
+        if self.cldice_weight:
+            L["loss_cldice"] = self.cldice_weight * (self.cldice(o["recovered_A"], real_A) + self.cldice(o["recovered_B"], real_B))
+            total = total + L["loss_cldice"]
         if self.ffl_weight:
             L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))
             total = total + L["loss_ffl"]

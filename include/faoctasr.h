@@ -666,6 +666,40 @@ int faoctasr_vif_scale_bwd(const float* x, const float* r, const float* table, c
                            const float* dnext_r, float* dx, float* dr, long N, long C, int H, int W, int scale, float lo, float hi,
                            float sigma_n_sq, faoctasr_stream_t stream);
 
+/* ---- soft-clDice: soft skeletons and the centre-line Dice (csrc/cldice.hip) -------------------------------
+ * x, y: contiguous (N, C, H, W), channels independent grey planes pooled inside an image, any sides >= 1, finite values.
+ *   u = (x - lo) / (hi - lo), hi > lo; bright == 0 uses (hi - x) / (hi - lo).  iters = K in 1..10.
+ *   E(I)[q] = min of I over the cross {up, left, q, right, down}, D(I)[q] = max over the 3 x 3 square, positions outside the image left out;
+ *   I_0 = u, I_{k+1} = E(I_k), O_k = D(I_{k+1}), delta_k = relu(I_k - O_k), k = 0..K; s_0 = delta_0, s_k = s_{k-1} + relu(delta_k - s_{k-1} delta_k);
+ *   skel(u) = s_K.  Tprec = (sum skel(x) u_y + smooth) / (sum skel(x) + smooth), Tsens = (sum skel(y) u_x + smooth) / (sum skel(y) + smooth), sums
+ *   over the channels and positions of image n, a ratio of denominator 0 taken as 0; S[n] = 2 Tprec Tsens / (Tprec + Tsens), 0 where that
+ *   denominator is 0.
+ * Records (written only where asked, read by grad): per side rec [K + 1][N][C][H][W] floats, the coefficient c_k that turns the skeleton's
+ *   cotangent at q into that of delta_k at q, and sel [K + 1][N][C][H][W] bytes: bits 0-2 the arg-min of q's cross in I_k (up, left, centre,
+ *   right, down = 0..4), bits 3-6 the arg-max of q's square in I_{k+1} (3 (dy + 1) + (dx + 1) = 0..8), each the FIRST position in that
+ *   order whose value equals the result: the tie rule, a valid subgradient, which on plateaus differs from a framework's pooling backward.
+ * index: with y, writes one partial each of sum skel(x) u_y, sum skel(x), sum skel(y) u_x, sum skel(y) per block into the workspace of
+ *   faoctasr_cldice_workspace_floats(N, C, H, W) floats (-1 on a bad shape; 8-byte aligned); skel_x, skel_y (each may be NULL) take the
+ *   skeleton maps, rec_x / sel_x and rec_y / sel_y (each pair or NULL) the records.  With y NULL (and no workspace, skel_y, rec_y, sel_y) it
+ *   writes the skeleton map of x into skel_x and, given rec_x / sel_x, its records: the soft-skeleton filter.
+ * final: adds the partials in double in a fixed order, a wave per image; out_image[N]; out_mean (may be NULL) the batch mean, from the
+ *   same call; table (may be NULL) [4][N]: dS / d(each of the four sums, in the order above), times 1 / N with `average`.
+ * grad: with a table, the index's gradient: g is a DEVICE array of gN floats (1 = shared, or N); dx needs rec_x, sel_x and skel_y, dy needs
+ *   rec_y, sel_y and skel_x; a NULL dx or dy skips that side and leaves the other side's bits.  With table NULL (and y, dy, rec_y, sel_y
+ *   NULL) the filter's: g is the upstream map, the size of x.  The kernel routes cotangents by the records alone, level K down to 0, in
+ *   gather form: it does not repeat the forward's arithmetic.
+ * Swapping x and y leaves the score bit for bit and swaps the gradients; halving g halves them bit for bit.  No atomics. */
+long faoctasr_cldice_workspace_floats(long N, long C, int H, int W);
+int faoctasr_cldice_index(const float* x, const float* y, float* skel_x, float* skel_y, float* rec_x, unsigned char* sel_x, float* rec_y,
+                          unsigned char* sel_y, float* workspace, long N, long C, int H, int W, int iters, float lo, float hi, int bright,
+                          faoctasr_stream_t stream);
+int faoctasr_cldice_final(float* workspace, long N, long C, int H, int W, double smooth, int average, float* out_image, float* out_mean,
+                          float* table, faoctasr_stream_t stream);
+int faoctasr_cldice_grad(const float* x, const float* y, const float* rec_x, const unsigned char* sel_x, const float* rec_y,
+                         const unsigned char* sel_y, const float* skel_x, const float* skel_y, const float* table, const float* g, int gN,
+                         float* dx, float* dy, long N, long C, int H, int W, int iters, float lo, float hi, int bright,
+                         faoctasr_stream_t stream);
+
 /* ---- losses (train.py:91-99) -----------------------------------------------------------------
  * kind 0: sum (a-b)^2 (MSELoss), 1: sum |a-b| (L1Loss), 2: BCEWithLogits(input=a, target=b) sum.
  * out[0] = scale * sum (overwritten); workspace: faoctasr_loss_workspace_floats() floats.  */
