@@ -380,11 +380,24 @@ __global__ void mean_mix_bwd_kernel(const float* __restrict__ g, float* __restri
     if (db) for (int i = threadIdx.x; i < Lb; i += blockDim.x) db[(long)n * Lb + i] = gv * wb / (float)Lb;
 }
 
-// torch.optim.AdamW single-tensor arithmetic order: decay, moments, bias corrections, update
+// torch.optim.AdamW single-tensor arithmetic order: decay, moments, bias corrections, update.  One element; the multiply-adds are
+// written out and contraction is off, so that the float4 body, the scalar tail and both kernels round alike: left to the compiler,
+// adamw_kernel's tail added b2 * v and (1 - b2) * g * g unfused while its body and adamw_dev_kernel's tail fused them
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float decay, float b1, float omb1, float b2, float omb2,
+                                           float eps, float step_size, float inv_sqrt_bc2, float gscale) {
+#pragma clang fp contract(off)
+    const float gg = g * gscale;
+    m = fmaf(omb1, gg, b1 * m);
+    v = fmaf(gg, omb2 * gg, b2 * v);
+    const float denom = fmaf(sqrtf(v), inv_sqrt_bc2, eps);
+    p = fmaf(decay, p, -(step_size * (m / denom)));
+}
+
 __device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
                                            float lr, float b1, float b2, float eps, float wd, float step_size, float inv_sqrt_bc2, float gscale) {
     const long stride = (long)gridDim.x * blockDim.x;
     const long n4 = n >> 2;
+    const float decay = fmaf(-lr, wd, 1.f), omb1 = 1.f - b1, omb2 = 1.f - b2;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pv = reinterpret_cast<float4*>(p)[i];
         const float4 gv = reinterpret_cast<const float4*>(g)[i];
@@ -392,26 +405,13 @@ __device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* _
         float4 vv = reinterpret_cast<float4*>(v)[i];
         float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float gg = gp[k] * gscale;
-            float pk = pp[k] * (1.f - lr * wd);
-            mp[k] = b1 * mp[k] + (1.f - b1) * gg;
-            vp[k] = b2 * vp[k] + (1.f - b2) * gg * gg;
-            const float denom = sqrtf(vp[k]) * inv_sqrt_bc2 + eps;
-            pp[k] = pk - step_size * (mp[k] / denom);
-        }
+        for (int k = 0; k < 4; ++k) adamw_elem(pp[k], gp[k], mp[k], vp[k], decay, b1, omb1, b2, omb2, eps, step_size, inv_sqrt_bc2, gscale);
         reinterpret_cast<float4*>(p)[i] = pv;
         reinterpret_cast<float4*>(m)[i] = mv;
         reinterpret_cast<float4*>(v)[i] = vv;
     }
-    for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float gg = g[i] * gscale;
-        float pk = p[i] * (1.f - lr * wd);
-        m[i] = b1 * m[i] + (1.f - b1) * gg;
-        v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
-        const float denom = sqrtf(v[i]) * inv_sqrt_bc2 + eps;
-        p[i] = pk - step_size * (m[i] / denom);
-    }
+    for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        adamw_elem(p[i], g[i], m[i], v[i], decay, b1, omb1, b2, omb2, eps, step_size, inv_sqrt_bc2, gscale);
 }
 
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
@@ -646,6 +646,7 @@ int faoctasr_haar_dfront_fwd(const float* x, float* y, int N, int H, int W, int 
 
 int faoctasr_haar_dfront_bwd(const float* dy, float* dx, int N, int H, int W, int mode, faoctasr_stream_t stream) {
     if (!dy || !dx) return fail(FAOCTASR_EINVAL, "haar_dfront_bwd: null pointer");
+    if ((H & 1) || (W & 1)) return fail(FAOCTASR_EUNSUPPORTED, "haar_dfront: odd size");
     const long tot = (long)N * (H / 2) * (W / 2);
     if (tot <= 0) return FAOCTASR_OK;
     hipLaunchKernelGGL(haar_dfront_bwd_kernel, dim3(grid_for(tot, 256)), dim3(256), 0, (hipStream_t)stream, dy, dx, N, H, W, mode);

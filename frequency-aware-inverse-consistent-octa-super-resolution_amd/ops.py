@@ -30,6 +30,21 @@ def act_code(a):
     return a if isinstance(a, int) else _ACT[a]
 
 
+def _act_args(act, slope):
+    """(activation code, slope) for the kernels.  Their backward takes the LeakyReLU derivative from the sign of the activation's
+    OUTPUT (csrc/common.h act_grad_from_out), which is the sign of its input only while slope >= 0: a negative slope would give a
+    correct forward value and a wrong gradient, so it is refused."""
+    code, slope = act_code(act), float(slope)
+    if code == ACT_LRELU and not slope >= 0.0:
+        raise _lib.KernelError("LeakyReLU slope must be >= 0, got %r: the backward kernels read the derivative off the output's sign" % slope)
+    return code, slope
+
+
+def _same_shape(what, a, b):
+    if a.shape != b.shape:
+        raise _lib.KernelError("%s operands differ in shape: %s vs %s" % (what, tuple(a.shape), tuple(b.shape)))
+
+
 def _c(t):
     if not t.is_cuda:
         raise _lib.KernelError("operand lives on %s: the HIP operators have no CPU/eager fallback" % t.device)
@@ -507,7 +522,7 @@ class _Conv2d(Function):
 
 
 def conv2d(x, w, bias=None, stride=1, pad=0, reflect=False, act=None, slope=0.2, link=None):
-    return _Conv2d.apply(x, w, bias, int(stride), int(pad), 1 if reflect else 0, act_code(act), float(slope), link)
+    return _Conv2d.apply(x, w, bias, int(stride), int(pad), 1 if reflect else 0, *_act_args(act, slope), link)
 
 
 class _ConvTranspose2d(Function):
@@ -586,7 +601,7 @@ class _ConvTranspose2d(Function):
 
 
 def conv_transpose2d(x, w, bias=None, stride=1, pad=0, out_pad=0, act=None, slope=0.2):
-    return _ConvTranspose2d.apply(x, w, bias, int(stride), int(pad), int(out_pad), act_code(act), float(slope))
+    return _ConvTranspose2d.apply(x, w, bias, int(stride), int(pad), int(out_pad), *_act_args(act, slope))
 
 
 # ----------------------------------------------------------------------------------------
@@ -680,11 +695,11 @@ class _BatchNormEval(Function):
 
 
 def batchnorm_eval(x, gamma, beta, running_mean, running_var, eps=1e-5, act=None, slope=0.2):
-    return _BatchNormEval.apply(x, gamma, beta, running_mean, running_var, float(eps), act_code(act), float(slope))
+    return _BatchNormEval.apply(x, gamma, beta, running_mean, running_var, float(eps), *_act_args(act, slope))
 
 
 def batchnorm_train(x, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5, act=None, slope=0.2, residual=None, link=None):
-    y, _ = _BatchNormTrain.apply(x, gamma, beta, residual, running_mean, running_var, float(momentum), float(eps), act_code(act), float(slope),
+    y, _ = _BatchNormTrain.apply(x, gamma, beta, residual, running_mean, running_var, float(momentum), float(eps), *_act_args(act, slope),
                                  link if residual is not None else None)
     return y
 
@@ -719,7 +734,7 @@ class _InstanceNorm(Function):
 
 
 def instance_norm(x, gamma=None, beta=None, eps=1e-5, act=None, slope=0.2):
-    return _InstanceNorm.apply(x, gamma, beta, float(eps), act_code(act), float(slope))
+    return _InstanceNorm.apply(x, gamma, beta, float(eps), *_act_args(act, slope))
 
 
 # ----------------------------------------------------------------------------------------
@@ -745,12 +760,14 @@ class _Act(Function):
 
 
 def activation(x, act, slope=0.2):
-    return _Act.apply(x, act_code(act), float(slope))
+    return _Act.apply(x, *_act_args(act, slope))
 
 
 class _Cat2Act(Function):
     @staticmethod
     def forward(ctx, a, b, act, slope):
+        if a.dim() != 4 or b.dim() != 4 or a.shape[0] != b.shape[0] or a.shape[2:] != b.shape[2:]:
+            raise _lib.KernelError("cat2_act operands must be (N,C,H,W) tensors that agree in N, H and W: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
         a, b = _c(a), _c(b)
         N, Ca, H, W = a.shape
         Cb = b.shape[1]
@@ -776,12 +793,13 @@ class _Cat2Act(Function):
 
 def cat2_act(a, b, act=None, slope=0.2):
     """torch.cat([a, b], 1) followed by an activation (model.py:266+249, 268+431, 298+431)."""
-    return _Cat2Act.apply(a, b, act_code(act), float(slope))
+    return _Cat2Act.apply(a, b, *_act_args(act, slope))
 
 
 class _Add(Function):
     @staticmethod
     def forward(ctx, a, b):
+        _same_shape("add", a, b)
         a, b = _c(a), _c(b)
         y = torch.empty_like(a)
         call("axpby", ptr(a), ptr(b), ptr(y), a.numel(), 1.0, 1.0, stream_ptr())
@@ -799,6 +817,7 @@ def add(a, b):
 class _Axpby(Function):
     @staticmethod
     def forward(ctx, a, b, alpha, beta):
+        _same_shape("axpby", a, b)
         a, b = _c(a), _c(b)
         y = torch.empty_like(a)
         call("axpby", ptr(a), ptr(b), ptr(y), a.numel(), alpha, beta, stream_ptr())
@@ -2537,6 +2556,8 @@ def bce_with_logits(inp, target, weight=1.0):
 class _MeanMix(Function):
     @staticmethod
     def forward(ctx, a, b, wa, wb):
+        if a.dim() < 1 or b.dim() < 1 or a.shape[0] != b.shape[0]:
+            raise _lib.KernelError("mean_mix operands differ in batch size: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
         a, b = _c(a), _c(b)
         N = a.shape[0]
         La, Lb = a.numel() // N, b.numel() // N
