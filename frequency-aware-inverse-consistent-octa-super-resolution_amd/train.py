@@ -12,6 +12,7 @@ import math
 import os
 import random
 import struct
+from collections import namedtuple
 
 import torch
 import torch.distributed as dist
@@ -219,6 +220,53 @@ def _after(waiter, mark):
         waiter.wait_event(mark.event)
 
 
+_Term = namedtuple("_Term", "name side share attr build check", defaults=(None, None, None))
+
+#: The opt-in terms of ``loss_G``, in the order they are added to it.  ``name`` gives the key ``loss_<name>`` and the attribute
+#: ``<name>_weight`` (0 = off: no module is built, nothing is launched).  ``side`` is the image pair a term compares: "cycle" =
+#: (recovered_X, real_X), "fake" = (a fake, the image of the other domain it was made from).  ``share(step, x, y)`` is the UNWEIGHTED
+#: value for one pair: the loss is ``w * (share(pair A) + share(pair B))`` in ``generator_loss`` and ``w * share(pair)`` on each chain
+#: of the two-chain schedule.  ``build(k, dev)`` makes the module from the constructor's keywords ``k`` and is stored under ``attr``
+#: (None when the weight is 0); ``share`` reads it from the step at call time.  ``check``: how ``_check_weight`` treats the weight.
+#: ``whf`` has no ``share``: its weight goes inside ``ops.l1_loss`` and it is one running sum over levels (``TrainStep._whf_sum``).
+OPT_IN_TERMS = (
+    _Term("ssim", "cycle", lambda s, rec, real: 1 - ops.ssim(rec, real)),                    # train.py:234 (commented out there)
+    _Term("whf", "cycle", None, "dwt_loss",                                                  # L1 of the wavelet high-frequency bands
+          lambda k, dev: (SWTForward if k["dwt_stationary"] else DWTForward)(J=k["dwt_levels"], wave=k["dwt_wave"], mode=k["dwt_mode"]).to(dev)),
+    _Term("phase", "cycle", lambda s, rec, real: 1 + ops.phase_loss(rec, real, s.phase_radius)),          # model.py:36-58
+    _Term("cwt", "cycle", lambda s, rec, real: s.cwt_loss(rec, real), "cwt_loss",
+          lambda k, dev: DTCWTMagnitudeLoss(biort=k["cwt_biort"], qshift=k["cwt_qshift"], J=k["cwt_levels"], mode=k["cwt_mode"]).to(dev)),
+    _Term("cwssim", "cycle", lambda s, rec, real: 1 - s.cwssim(rec, real), "cwssim",
+          lambda k, dev: CWSSIM(biort=k["cwssim_biort"], qshift=k["cwssim_qshift"], J=k["cwssim_levels"], mode=k["cwssim_mode"],
+                                win=k["cwssim_win"]).to(dev)),
+    _Term("msssim", "cycle", lambda s, rec, real: 1 - s.msssim(rec, real), "msssim",
+          lambda k, dev: MSSSIM(levels=k["msssim_levels"], weights=k["msssim_weights"]).to(dev)),
+    _Term("haarpsi", "cycle", lambda s, rec, real: 1 - s.haarpsi(rec, real), "haarpsi",
+          lambda k, dev: HaarPSI(c=k["haarpsi_c"], alpha=k["haarpsi_alpha"]).to(dev)),
+    _Term("gmsd", "cycle", lambda s, rec, real: s.gmsd(rec, real), "gmsd",                   # a distortion: the value is the term
+          lambda k, dev: (MSGMSD(c=k["gmsd_c"]) if k["gmsd_multiscale"] else GMSD(c=k["gmsd_c"])).to(dev), "number"),
+    _Term("vessel", "cycle", lambda s, rec, real: 1 - s.vessel(rec, real), "vessel",
+          lambda k, dev: VesselDice(sigmas=k["vessel_sigmas"], c=k["vessel_c"]).to(dev), "number"),
+    _Term("vif", "cycle", lambda s, rec, real: 1 - s.vif(rec, real), "vif",
+          lambda k, dev: VIF(sigma_n_sq=k["vif_sigma_n_sq"]).to(dev), "no_bool"),
+    _Term("cldice", "cycle", lambda s, rec, real: s.cldice(rec, real), "cldice",             # the module's forward is the loss 1 - S
+          lambda k, dev: SoftClDice(iters=k["cldice_iters"]).to(dev), "no_bool"),
+    _Term("ffl", "cycle", lambda s, rec, real: s.ffl(rec, real), "ffl",
+          lambda k, dev: FocalFrequencyLoss(alpha=k["ffl_alpha"], log_matrix=k["ffl_log_matrix"], batch_matrix=k["ffl_batch_matrix"]), "number"),
+    _Term("tv", "fake", lambda s, fake, src: ops.tv_loss(fake)),                             # model.py:17-33; looks at the fake alone
+    _Term("mi", "fake", lambda s, fake, src: s.mi.upper - s.mi(fake, src), "mi",
+          lambda k, dev: MutualInformationLoss(bins=k["mi_bins"], sigma_ratio=k["mi_sigma_ratio"], normalized=k["mi_normalized"]), "number"),
+    _Term("lncc", "fake", lambda s, fake, src: 1 - s.lncc(fake, src), "lncc",
+          lambda k, dev: LNCC(win=k["lncc_win"], eps=k["lncc_eps"]).to(dev), "number"),
+)
+
+
+def _check_weight(name, w, check):
+    """``check`` None: anything goes (the terms older than the check); "number": a finite number >= 0; "no_bool": and no bool."""
+    if check and not (isinstance(w, (int, float)) and not (check == "no_bool" and isinstance(w, bool)) and math.isfinite(w) and w >= 0):
+        raise ValueError("%s_weight must be a finite number >= 0, got %r" % (name, w))
+
+
 class TrainStep:
     #: which of the schedule's six roles share a HIP stream (see __init__).  The runtime multiplexes streams onto 4 hardware queues
     #: in creation order, and MORE concurrency is not better (one stream per role on 8 queues: 116.3 ms; on the default 4 queues the
@@ -350,6 +398,7 @@ class TrainStep:
         squared correlation coefficient of a fake and the image of the other domain it was made from inside a sliding box.  Where
         the mutual information sees one joint histogram per plane, this term is spatial: a vessel that moved lowers it wherever it
         moved, whatever the intensity map between the domains.  The gradient reaches the fake only."""
+        keywords = dict(locals())                   # what OPT_IN_TERMS' weights and module builders read
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
         self.precision = precision
@@ -367,66 +416,15 @@ class TrainStep:
             for n in (self.netG_A2B, self.netG_B2A, self.netD_A, self.netD_B):
                 n.apply(weights_init_normal)
         self.w = dict(beta1=beta1, beta2=beta2, beta3=beta3, beta4=beta4, beta5=beta5)     # train.py:50-54
-        self.ssim_weight, self.whf_weight, self.dwt_levels = ssim_weight, whf_weight, dwt_levels
-        #: opt-in spectral term: phase_weight * (1 + phase_consistency_loss) per image pair (model.py:36-58; 0 = reference behaviour)
-        self.phase_weight, self.phase_radius = phase_weight, phase_radius
-        #: opt-in smoothness term on the generators' outputs: tv_weight * (TVLoss(fake_B) + TVLoss(fake_A)) (model.py:17-33; 0 = off)
-        self.tv_weight = tv_weight
-        self.dwt_stationary = bool(dwt_stationary)
-        self.dwt_loss = ((SWTForward if self.dwt_stationary else DWTForward)(J=dwt_levels, wave=dwt_wave, mode=dwt_mode).to(dev)
-                         if whf_weight else None)
-        #: opt-in dual-tree magnitude term on the cycle reconstructions (wavelets.DTCWTMagnitudeLoss; 0 = off, no module is built)
-        self.cwt_weight = cwt_weight
-        self.cwt_loss = (DTCWTMagnitudeLoss(biort=cwt_biort, qshift=cwt_qshift, J=cwt_levels, mode=cwt_mode).to(dev)
-                         if cwt_weight else None)
-        #: opt-in complex-wavelet SSIM term on the cycle reconstructions (wavelets.CWSSIM; 0 = off, no module is built)
-        self.cwssim_weight = cwssim_weight
-        self.cwssim = (CWSSIM(biort=cwssim_biort, qshift=cwssim_qshift, J=cwssim_levels, mode=cwssim_mode, win=cwssim_win).to(dev)
-                       if cwssim_weight else None)
-        #: opt-in multi-scale SSIM term on the cycle reconstructions (ssim.MSSSIM; 0 = off, no module is built)
-        self.msssim_weight = msssim_weight
-        self.msssim = MSSSIM(levels=msssim_levels, weights=msssim_weights).to(dev) if msssim_weight else None
-        #: opt-in focal frequency term on the cycle reconstructions (model.FocalFrequencyLoss; 0 = off, no module is built)
-        if not (isinstance(ffl_weight, (int, float)) and math.isfinite(ffl_weight) and ffl_weight >= 0):
-            raise ValueError("ffl_weight must be a finite number >= 0, got %r" % (ffl_weight,))
-        self.ffl_weight = ffl_weight
-        self.ffl = (FocalFrequencyLoss(alpha=ffl_alpha, log_matrix=ffl_log_matrix, batch_matrix=ffl_batch_matrix)
-                    if ffl_weight else None)
-        #: opt-in mutual-information term of each fake against its source (model.MutualInformationLoss; 0 = off, no module is built)
-        if not (isinstance(mi_weight, (int, float)) and math.isfinite(mi_weight) and mi_weight >= 0):
-            raise ValueError("mi_weight must be a finite number >= 0, got %r" % (mi_weight,))
-        self.mi_weight = mi_weight
-        self.mi = MutualInformationLoss(bins=mi_bins, sigma_ratio=mi_sigma_ratio, normalized=mi_normalized) if mi_weight else None
-        #: opt-in HaarPSI term on the cycle reconstructions (ssim.HaarPSI; 0 = off, no module is built)
-        self.haarpsi_weight = haarpsi_weight
-        self.haarpsi = HaarPSI(c=haarpsi_c, alpha=haarpsi_alpha).to(dev) if haarpsi_weight else None
-        #: opt-in GMSD / MS-GMSD term on the cycle reconstructions (ssim.GMSD, ssim.MSGMSD; 0 = off, no module is built)
-        if not (isinstance(gmsd_weight, (int, float)) and math.isfinite(gmsd_weight) and gmsd_weight >= 0):
-            raise ValueError("gmsd_weight must be a finite number >= 0, got %r" % (gmsd_weight,))
-        self.gmsd_weight = gmsd_weight
-        self.gmsd = ((MSGMSD(c=gmsd_c) if gmsd_multiscale else GMSD(c=gmsd_c)).to(dev)) if gmsd_weight else None
-        #: opt-in vessel Dice term on the cycle reconstructions (ssim.VesselDice; 0 = off, no module is built)
-        if not (isinstance(vessel_weight, (int, float)) and math.isfinite(vessel_weight) and vessel_weight >= 0):
-            raise ValueError("vessel_weight must be a finite number >= 0, got %r" % (vessel_weight,))
-        self.vessel_weight = vessel_weight
-        self.vessel = VesselDice(sigmas=vessel_sigmas, c=vessel_c).to(dev) if vessel_weight else None
-        #: opt-in visual information fidelity term on the cycle reconstructions (ssim.VIF; 0 = off, no module is built)
-        if not (isinstance(vif_weight, (int, float)) and not isinstance(vif_weight, bool) and math.isfinite(vif_weight) and vif_weight >= 0):
-            raise ValueError("vif_weight must be a finite number >= 0, got %r" % (vif_weight,))
+        self.dwt_levels, self.dwt_stationary, self.phase_radius = dwt_levels, bool(dwt_stationary), phase_radius
         if not (isinstance(vif_sigma_n_sq, (int, float)) and not isinstance(vif_sigma_n_sq, bool) and math.isfinite(vif_sigma_n_sq) and vif_sigma_n_sq > 0):
             raise ValueError("vif_sigma_n_sq must be a finite number > 0, got %r" % (vif_sigma_n_sq,))
-        self.vif_weight = vif_weight
-        self.vif = VIF(sigma_n_sq=vif_sigma_n_sq).to(dev) if vif_weight else None
-        #: opt-in soft-clDice term on the cycle reconstructions (ssim.SoftClDice; 0 = off, no module is built)
-        if not (isinstance(cldice_weight, (int, float)) and not isinstance(cldice_weight, bool) and math.isfinite(cldice_weight) and cldice_weight >= 0):
-            raise ValueError("cldice_weight must be a finite number >= 0, got %r" % (cldice_weight,))
-        self.cldice_weight = cldice_weight
-        self.cldice = SoftClDice(iters=cldice_iters).to(dev) if cldice_weight else None
-        #: opt-in local normalised cross-correlation of each fake against its source (ssim.LNCC; 0 = off, no module is built)
-        if not (isinstance(lncc_weight, (int, float)) and math.isfinite(lncc_weight) and lncc_weight >= 0):
-            raise ValueError("lncc_weight must be a finite number >= 0, got %r" % (lncc_weight,))
-        self.lncc_weight = lncc_weight
-        self.lncc = LNCC(win=lncc_win, eps=lncc_eps).to(dev) if lncc_weight else None
+        for term in OPT_IN_TERMS:                   # <name>_weight, and the term's module under its attribute (None at weight 0)
+            weight = keywords[term.name + "_weight"]
+            _check_weight(term.name, weight, term.check)
+            setattr(self, term.name + "_weight", weight)
+            if term.attr:
+                setattr(self, term.attr, term.build(keywords, dev) if weight else None)
         # train.py:102-103: one AdamW per side, lr 1.3e-4, betas (0.9, 0.999), default eps/weight_decay
         self.opt_G = ParamArena(live_parameters(self.netG_A2B) + live_parameters(self.netG_B2A), lr, betas)
         self.opt_D = ParamArena(live_parameters(self.netD_A) + live_parameters(self.netD_B), lr, betas)
@@ -671,13 +669,8 @@ class TrainStep:
             L["loss_cycle_BAB"] = ops.l1_loss(o["recovered_B"], real_B, w["beta3"]) + \
                 ops.bce_with_logits(o["hf_feature_B"], o["hf_feature_recovered_B"], w["beta1"])
             root = L["loss_GAN_B2A"] + L["loss_cycle_BAB"]
-            extra_B = self._extension_terms(o["recovered_B"], real_B)       # opt-in SSIM / wavelet-HF terms: one half per chain
-            if self.tv_weight:                  # fake_A was made on this stream: its share of the TV term joins chain B's root
-                extra_B["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_A"])
-            if self.mi_weight:                  # likewise fake_A's mutual information with the real_B it was made from
-                extra_B["loss_mi"] = self.mi_weight * (self.mi.upper - self.mi(o["fake_A"], real_B))
-            if self.lncc_weight:                # ... and its local normalised cross-correlation with it
-                extra_B["loss_lncc"] = self.lncc_weight * (1 - self.lncc(o["fake_A"], real_B))
+            extra_B = self._extension_terms(o["recovered_B"], real_B)       # the opt-in terms (OPT_IN_TERMS): one half per chain
+            extra_B.update(self._fake_terms(o["fake_A"], real_B))           # fake_A was made on this stream, from real_B
             for k, v in extra_B.items():
                 root = root + v
         # ---- chain A, losses and backward
@@ -688,12 +681,7 @@ class TrainStep:
             L["loss_cycle_ABA"] = ops.l1_loss(o["recovered_A"], real_A, w["beta3"]) + ops.bce_with_logits(o["hf_feature_A"], o["hf_feature_recovered_A"])
             chain_A = L["loss_GAN_A2B"] + L["loss_cycle_ABA"]
             extra_A = self._extension_terms(o["recovered_A"], real_A)
-            if self.tv_weight:                  # ... and fake_B's share joins chain A's, on chain A's stream
-                extra_A["loss_tv"] = self.tv_weight * ops.tv_loss(o["fake_B"])
-            if self.mi_weight:
-                extra_A["loss_mi"] = self.mi_weight * (self.mi.upper - self.mi(o["fake_B"], real_A))
-            if self.lncc_weight:
-                extra_A["loss_lncc"] = self.lncc_weight * (1 - self.lncc(o["fake_B"], real_A))
+            extra_A.update(self._fake_terms(o["fake_B"], real_A))           # ... and fake_B's shares join chain A's, on chain A's stream
             for k, v in extra_A.items():
                 chain_A = chain_A + v
             ops.wgrad_stream = side
@@ -723,44 +711,33 @@ class TrainStep:
             return [y[:, :, 1:] for y in self.dwt_loss(img)]
         return self.dwt_loss(img)[1]
 
-    def _extension_terms(self, rec, real):
-        """One image pair's share of the opt-in terms of ``generator_loss`` (SSIM: train.py:234; wavelet-HF L1; spectral phase; focal frequency)."""
+    def _whf_sum(self, acc, rec, real):
+        """``acc`` plus the wavelet-HF term of one image pair: the weighted L1 of every level's bands, added level by level."""
+        for a, b in zip(self._whf_bands(rec), self._whf_bands(real)):
+            acc = acc + ops.l1_loss(a, b, self.whf_weight)
+        return acc
+
+    def _pair_terms(self, side, x, y):
+        """One image pair's weighted share of every enabled term of ``OPT_IN_TERMS`` on ``side``, in table order."""
         t = {}
-        if self.ssim_weight:
-            t["loss_ssim"] = self.ssim_weight * (1 - ops.ssim(rec, real))
-        if self.whf_weight:
-            acc = 0
-            yh_r, yh_t = self._whf_bands(rec), self._whf_bands(real)
-            for a, b in zip(yh_r, yh_t):
-                acc = acc + ops.l1_loss(a, b, self.whf_weight)
-            t["loss_whf"] = acc
-        if self.phase_weight:
-            t["loss_phase"] = self.phase_weight * (1 + ops.phase_loss(rec, real, self.phase_radius))
-        if self.cwt_weight:
-            t["loss_cwt"] = self.cwt_weight * self.cwt_loss(rec, real)
-        if self.cwssim_weight:
-            t["loss_cwssim"] = self.cwssim_weight * (1 - self.cwssim(rec, real))
-        if self.msssim_weight:
-            t["loss_msssim"] = self.msssim_weight * (1 - self.msssim(rec, real))
-        if self.haarpsi_weight:
-            t["loss_haarpsi"] = self.haarpsi_weight * (1 - self.haarpsi(rec, real))
-        if self.gmsd_weight:
-            t["loss_gmsd"] = self.gmsd_weight * self.gmsd(rec, real)
-        if self.vessel_weight:
-            t["loss_vessel"] = self.vessel_weight * (1 - self.vessel(rec, real))
-        if self.vif_weight:
-            t["loss_vif"] = self.vif_weight * (1 - self.vif(rec, real))
-        if self.cldice_weight:
-            t["loss_cldice"] = self.cldice_weight * self.cldice(rec, real)
-        if self.ffl_weight:
-            t["loss_ffl"] = self.ffl_weight * self.ffl(rec, real)
+        for term in OPT_IN_TERMS:
+            w = getattr(self, term.name + "_weight")
+            if w and term.side == side:
+                t["loss_" + term.name] = w * term.share(self, x, y) if term.share else self._whf_sum(0, x, y)
         return t
 
+    def _extension_terms(self, rec, real):
+        """One cycle pair's share (a reconstruction and its input) of the opt-in terms: what one chain of the two-chain schedule
+        adds to its root.  {} for the default step."""
+        return self._pair_terms("cycle", rec, real)
+
+    def _fake_terms(self, fake, source):
+        """A chain's share of the opt-in terms on its fake and the image of the other domain the fake was made from."""
+        return self._pair_terms("fake", fake, source)
+
     def generator_loss(self, o, real_A, real_B):
-        """train.py:221-236 (+ the opt-in SSIM term of the commented line train.py:234, a wavelet-HF L1 term, the spectral phase term and
-        the total-variation term of the two fakes and the mutual information and local normalised cross-correlation of each fake with
-        its source).  ``L["_root"]`` is
-        what remains to be back-propagated (everything, unless ``forward_generators`` already did the identity terms)."""
+        """train.py:221-236, then every enabled term of ``OPT_IN_TERMS`` in table order.  ``L["_root"]`` is what remains to be
+        back-propagated (everything, unless ``forward_generators`` already did the identity terms)."""
         w = self.w
         ones, _ = self.targets(real_A.shape[0])
         L = {}
@@ -777,57 +754,18 @@ class TrainStep:
         else:
             L["loss_idt"] = ops.l1_loss(real_A, o["idt_A"], w["beta2"]) + ops.l1_loss(real_B, o["idt_B"], w["beta2"])
             total = total + L["loss_idt"]
-        if self.ssim_weight:
-            L["loss_ssim"] = self.ssim_weight * ((1 - ops.ssim(o["recovered_A"], real_A)) + (1 - ops.ssim(o["recovered_B"], real_B)))
-            total = total + L["loss_ssim"]
-        if self.whf_weight:
-            t = 0
-            for rec, real in ((o["recovered_A"], real_A), (o["recovered_B"], real_B)):
-                yh_r, yh_t = self._whf_bands(rec), self._whf_bands(real)
-                for a, b in zip(yh_r, yh_t):
-                    t = t + ops.l1_loss(a, b, self.whf_weight)
-            L["loss_whf"] = t
+        pairs = {"cycle": (("recovered_A", real_A), ("recovered_B", real_B)), "fake": (("fake_B", real_A), ("fake_A", real_B))}
+        for term in OPT_IN_TERMS:                   # both pairs at once: the A pair is the left operand of the sum
+            weight = getattr(self, term.name + "_weight")
+            if not weight:
+                continue
+            A, B = ((o[key], real) for key, real in pairs[term.side])
+            if term.share:
+                t = weight * (term.share(self, *A) + term.share(self, *B))
+            else:                                   # whf: one chain of additions across both pairs
+                t = self._whf_sum(self._whf_sum(0, *A), *B)
+            L["loss_" + term.name] = t
             total = total + t
-        if self.phase_weight:
-            L["loss_phase"] = self.phase_weight * ((1 + ops.phase_loss(o["recovered_A"], real_A, self.phase_radius)) +
-                                                   (1 + ops.phase_loss(o["recovered_B"], real_B, self.phase_radius)))
-            total = total + L["loss_phase"]
-        if self.cwt_weight:
-            L["loss_cwt"] = self.cwt_weight * (self.cwt_loss(o["recovered_A"], real_A) + self.cwt_loss(o["recovered_B"], real_B))
-            total = total + L["loss_cwt"]
-        if self.cwssim_weight:
-            L["loss_cwssim"] = self.cwssim_weight * ((1 - self.cwssim(o["recovered_A"], real_A)) + (1 - self.cwssim(o["recovered_B"], real_B)))
-            total = total + L["loss_cwssim"]
-        if self.msssim_weight:
-            L["loss_msssim"] = self.msssim_weight * ((1 - self.msssim(o["recovered_A"], real_A)) + (1 - self.msssim(o["recovered_B"], real_B)))
-            total = total + L["loss_msssim"]
-        if self.haarpsi_weight:
-            L["loss_haarpsi"] = self.haarpsi_weight * ((1 - self.haarpsi(o["recovered_A"], real_A)) + (1 - self.haarpsi(o["recovered_B"], real_B)))
-            total = total + L["loss_haarpsi"]
-        if self.gmsd_weight:
-            L["loss_gmsd"] = self.gmsd_weight * (self.gmsd(o["recovered_A"], real_A) + self.gmsd(o["recovered_B"], real_B))
-            total = total + L["loss_gmsd"]
-        if self.vessel_weight:
-            L["loss_vessel"] = self.vessel_weight * ((1 - self.vessel(o["recovered_A"], real_A)) + (1 - self.vessel(o["recovered_B"], real_B)))
-            total = total + L["loss_vessel"]
-        if self.vif_weight:
-            L["loss_vif"] = self.vif_weight * ((1 - self.vif(o["recovered_A"], real_A)) + (1 - self.vif(o["recovered_B"], real_B)))
-            total = total + L["loss_vif"]
-        if self.cldice_weight:
-            L["loss_cldice"] = self.cldice_weight * (self.cldice(o["recovered_A"], real_A) + self.cldice(o["recovered_B"], real_B))
-            total = total + L["loss_cldice"]
-        if self.ffl_weight:
-            L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))
-            total = total + L["loss_ffl"]
-        if self.tv_weight:
-            L["loss_tv"] = self.tv_weight * (ops.tv_loss(o["fake_B"]) + ops.tv_loss(o["fake_A"]))
-            total = total + L["loss_tv"]
-        if self.mi_weight:
-            L["loss_mi"] = self.mi_weight * ((self.mi.upper - self.mi(o["fake_B"], real_A)) + (self.mi.upper - self.mi(o["fake_A"], real_B)))
-            total = total + L["loss_mi"]
-        if self.lncc_weight:
-            L["loss_lncc"] = self.lncc_weight * ((1 - self.lncc(o["fake_B"], real_A)) + (1 - self.lncc(o["fake_A"], real_B)))
-            total = total + L["loss_lncc"]
         L["_root"] = total
         L["loss_G"] = total if done is None else total.detach() + done
         return L

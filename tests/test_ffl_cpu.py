@@ -262,7 +262,8 @@ def test_train_step_arguments(fa, monkeypatch):
 
 
 def test_train_step_terms_call_the_module(fa):
-    """Both places the opt-in terms live name ``loss_ffl``; with the module replaced by a stub no kernel runs."""
+    """``_extension_terms`` names ``loss_ffl``; with the module replaced by a stub no kernel runs (``generator_loss``:
+    tests/test_train_terms_cpu.py)."""
     nets = (fa.NetworkA2B(), fa.NetworkB2A(), fa.FS_DiscriminatorA(1), fa.FS_DiscriminatorB(1))
     ts = fa.TrainStep(*nets, device="cpu", ffl_weight=0.5)
     ts.ffl = lambda rec, real: (rec * real).mean()
@@ -270,6 +271,4 @@ def test_train_step_terms_call_the_module(fa):
     t = ts._extension_terms(rec, real)
     assert list(t) == ["loss_ffl"] and float(t["loss_ffl"]) == 0.5 * 0.25
     assert fa.TrainStep(*nets, device="cpu")._extension_terms(rec, real) == {}
-    src = inspect.getsource(fa.TrainStep.generator_loss)
-    assert 'L["loss_ffl"] = self.ffl_weight * (self.ffl(o["recovered_A"], real_A) + self.ffl(o["recovered_B"], real_B))' in src
     assert "if self.phase_weight or self.ffl_weight:" in inspect.getsource(fa.TrainStep.step)

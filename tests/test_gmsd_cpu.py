@@ -535,8 +535,8 @@ def test_train_step_builds_the_module_only_when_asked(fa, monkeypatch):
 
 
 def test_train_step_adds_the_term_where_loss_haarpsi_is_added(fa):
-    """``_extension_terms`` (one half per chain of the two-chain schedule, which ``GraphedTrainStep`` captures) and the single-stream
-    ``generator_loss`` name ``loss_gmsd`` next to ``loss_haarpsi``; with the module replaced by a stub no kernel runs."""
+    """``_extension_terms`` (one half per chain of the two-chain schedule, which ``GraphedTrainStep`` captures) names ``loss_gmsd``; with
+    the module replaced by a stub no kernel runs (the single-stream ``generator_loss``: tests/test_train_terms_cpu.py)."""
     nets = (fa.NetworkA2B(), fa.NetworkB2A(), fa.FS_DiscriminatorA(1), fa.FS_DiscriminatorB(1))
     ts = fa.TrainStep(*nets, device="cpu", gmsd_weight=0.5)
     ts.gmsd = lambda rec, real: (rec * real).mean()
@@ -544,10 +544,4 @@ def test_train_step_adds_the_term_where_loss_haarpsi_is_added(fa):
     t = ts._extension_terms(rec, real)
     assert list(t) == ["loss_gmsd"] and float(t["loss_gmsd"]) == 0.5 * 0.25
     assert fa.TrainStep(*nets, device="cpu")._extension_terms(rec, real) == {}
-    src = inspect.getsource(fa.TrainStep.generator_loss)
-    assert 'L["loss_gmsd"] = self.gmsd_weight * (self.gmsd(o["recovered_A"], real_A) + self.gmsd(o["recovered_B"], real_B))' in src
-    assert 'total = total + L["loss_gmsd"]' in src
-    src = inspect.getsource(fa.TrainStep)
-    assert 'extra_A = self._extension_terms(o["recovered_A"], real_A)' in src and 'extra_B = self._extension_terms(o["recovered_B"], real_B)' in src
-    assert src.count('"loss_gmsd"') == src.count('"loss_haarpsi"') == 3
     assert not hasattr(fa.GraphedTrainStep, "generator_loss")              # it captures the TrainStep's own terms

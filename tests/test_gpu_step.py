@@ -586,3 +586,33 @@ def test_reproducible_forward_mode(fa, O):
             assert v == pytest.approx(L2[k], rel=2e-5, abs=1e-7), k
     for x, y in ((g0, g1), (d0, d1)):
         assert float((x.double() - y.double()).norm() / y.double().norm()) < 1e-5
+
+
+OPT_IN = ("ssim", "whf", "phase", "cwt", "cwssim", "msssim", "haarpsi", "gmsd", "vessel", "vif", "cldice", "ffl", "tv", "mi", "lncc")
+
+
+def test_all_opt_in_terms_in_both_eager_schedules(fa, O):
+    """192^2, batch 1 (large enough for VIF's 41-pixel minimum and five MS-SSIM levels), every opt-in weight non-zero: the
+    single-stream ``generator_loss`` and the two-chain schedule return the same opt-in keys, in the order the terms are added to
+    ``loss_G``, every value finite, and ``loss_G`` above the default step's on the same batch (every term is non-negative here and
+    several are far from 0).  ``cwssim_levels=1``: more levels need q-shift taps the package does not carry."""
+    a, b = (t.cuda() for t in O.synthetic_batch(1, 192))
+    kw = dict(reproducible_forward=True, dwt_levels=2, cwssim_levels=1, **{n + "_weight": 0.25 for n in OPT_IN})
+    saved = fa.TrainStep.overlap_min_pixels
+    out = {}
+    try:
+        for two_chains in (False, True):
+            fa.TrainStep.overlap_min_pixels = 0 if two_chains else 1 << 40
+            for key, extra in (("default", dict(reproducible_forward=True)), ("all", kw)):
+                random.seed(1234)
+                n = build_nets(fa, O)
+                out[two_chains, key] = fa.TrainStep(n["A2B"], n["B2A"], n["D_A"], n["D_B"], **extra).step(a, b, sync=True)
+    finally:
+        fa.TrainStep.overlap_min_pixels = saved
+    for two_chains in (False, True):
+        L, Ld = out[two_chains, "all"], out[two_chains, "default"]
+        assert [k for k in L if k[5:] in OPT_IN] == ["loss_" + n for n in OPT_IN], (two_chains, list(L))
+        assert not [k for k in Ld if k[5:] in OPT_IN]
+        assert all(np.isfinite(v) for v in L.values()), (two_chains, L)
+        print("all opt-in terms, two_chains=%s: loss_G %.6f against %.6f by default" % (two_chains, L["loss_G"], Ld["loss_G"]))
+        assert L["loss_G"] > Ld["loss_G"]

@@ -585,8 +585,8 @@ def test_train_step_builds_the_module_only_when_asked(fa, monkeypatch):
 
 
 def test_train_step_adds_the_term_where_loss_gmsd_is_added(fa):
-    """``_extension_terms`` (one half per chain of the two-chain schedule, which ``GraphedTrainStep`` captures) and the single-stream
-    ``generator_loss`` name ``loss_vessel`` next to ``loss_gmsd``; with the module replaced by a stub no kernel runs."""
+    """``_extension_terms`` (one half per chain of the two-chain schedule, which ``GraphedTrainStep`` captures) names ``loss_vessel``; with
+    the module replaced by a stub no kernel runs (the single-stream ``generator_loss``: tests/test_train_terms_cpu.py)."""
     nets = (fa.NetworkA2B(), fa.NetworkB2A(), fa.FS_DiscriminatorA(1), fa.FS_DiscriminatorB(1))
     ts = fa.TrainStep(*nets, device="cpu", vessel_weight=0.5)
     ts.vessel = lambda rec, real: (rec * real).mean()
@@ -594,10 +594,4 @@ def test_train_step_adds_the_term_where_loss_gmsd_is_added(fa):
     t = ts._extension_terms(rec, real)
     assert list(t) == ["loss_vessel"] and float(t["loss_vessel"]) == 0.5 * (1 - 0.25)
     assert fa.TrainStep(*nets, device="cpu")._extension_terms(rec, real) == {}
-    src = inspect.getsource(fa.TrainStep.generator_loss)
-    assert 'L["loss_vessel"] = self.vessel_weight * ((1 - self.vessel(o["recovered_A"], real_A)) + (1 - self.vessel(o["recovered_B"], real_B)))' in src
-    assert 'total = total + L["loss_vessel"]' in src
-    assert src.index('L["loss_gmsd"]') < src.index('L["loss_vessel"]') < src.index('L["loss_ffl"]')
-    src = inspect.getsource(fa.TrainStep)
-    assert src.count('"loss_vessel"') == src.count('"loss_gmsd"') == 3
     assert not hasattr(fa.GraphedTrainStep, "generator_loss")              # it captures the TrainStep's own terms

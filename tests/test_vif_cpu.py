@@ -468,8 +468,8 @@ def test_train_step_builds_the_module_only_when_asked(fa, monkeypatch):
 
 
 def test_train_step_adds_the_term_where_loss_vessel_is_added(fa):
-    """``_extension_terms`` (one half per chain of the two-chain schedule, which ``GraphedTrainStep`` captures) and the single-stream
-    ``generator_loss`` name ``loss_vif`` next to ``loss_vessel``; with the module replaced by a stub no kernel runs."""
+    """``_extension_terms`` (one half per chain of the two-chain schedule, which ``GraphedTrainStep`` captures) names ``loss_vif``; with
+    the module replaced by a stub no kernel runs (the single-stream ``generator_loss``: tests/test_train_terms_cpu.py)."""
     nets = (fa.NetworkA2B(), fa.NetworkB2A(), fa.FS_DiscriminatorA(1), fa.FS_DiscriminatorB(1))
     ts = fa.TrainStep(*nets, device="cpu", vif_weight=0.5)
     seen = []
@@ -479,10 +479,4 @@ def test_train_step_adds_the_term_where_loss_vessel_is_added(fa):
     assert list(t) == ["loss_vif"] and float(t["loss_vif"]) == 0.5 * (1 - 0.125)
     assert seen[0][0] is rec and seen[0][1] is real                        # the reconstruction first, the ground truth second
     assert fa.TrainStep(*nets, device="cpu")._extension_terms(rec, real) == {}
-    src = inspect.getsource(fa.TrainStep.generator_loss)
-    assert 'L["loss_vif"] = self.vif_weight * ((1 - self.vif(o["recovered_A"], real_A)) + (1 - self.vif(o["recovered_B"], real_B)))' in src
-    assert 'total = total + L["loss_vif"]' in src
-    assert src.index('L["loss_vessel"]') < src.index('L["loss_vif"]') < src.index('L["loss_ffl"]')
-    src = inspect.getsource(fa.TrainStep)
-    assert src.count('"loss_vif"') == src.count('"loss_vessel"') == 3
     assert not hasattr(fa.GraphedTrainStep, "generator_loss")              # it captures the TrainStep's own terms
