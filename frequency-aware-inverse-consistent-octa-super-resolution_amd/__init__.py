@@ -7,7 +7,7 @@ HIP kernels for gfx950 behind the C ABI of ``include/faoctasr.h``.
 from . import _lib, ops
 from ._lib import KernelError
 from .model import (Discriminator, FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A, ResidualBlock, ResnetBlock,
-                    ResnetGenerator, TVLoss, UnetGenerator, UnetSkipConnectionBlock, phase_consistency_loss, shallowNet)
+                    ResnetGenerator, SpectralProfileLoss, TVLoss, UnetGenerator, UnetSkipConnectionBlock, phase_consistency_loss, shallowNet)
 from .evaluate import evaluate_pairs, evaluate_pairs_with, image_metrics, super_resolve
 from . import ssim                # stays the MODULE: the reference does `import ssim; ssim.SSIM()` (train.py:24,97)
 from .ssim import SSIM, MSSSIM, ms_ssim, HaarPSI, LNCC, GMSD, MSGMSD, Vesselness, VesselDice, VIF, SoftSkeleton, SoftClDice
@@ -18,6 +18,6 @@ from .utils import (DeviceReplayBuffer, LambdaLR, ReplayBuffer, frequency_split,
 from .wavelets import AFB1D, AFB2D, SFB1D, SFB2D, DWT1DForward, DWT1DInverse, DWTForward, DWTInverse, SWTForward, SWTInverse, daubechies
 from .wavelets import DTCWTForward, DTCWTInverse, ScatLayer, ScatLayerj2, DTCWTMagnitudeLoss, CWSSIM
 DTCWT, IDTCWT = DTCWTForward, DTCWTInverse          # the reference's aliases (pytorch_wavelets/__init__.py)
-from .ops import DWT1D_FUSED_MAX
+from .ops import DWT1D_FUSED_MAX, radial_bins
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -64,6 +64,10 @@ _SIG = {
     "ffl_workspace_floats": (_L, "iiii"),
     "ffl_fwd": (_I, "pppp f ii ppp iiii p"),
     "ffl_bwd": (_I, "pppp f i ppp iiii p"),
+    "sprof_workspace_floats": (_L, "i iiii ii"),
+    "sprof_profile_fwd": (_I, "ppp ppp ppp iiii ii p"),
+    "sprof_loss_fwd": (_I, "pppp ppp d iii ppp ppp iiii ii p"),
+    "sprof_bwd": (_I, "p i p pp pp pp pp p iiii ii p"),
     "mi_workspace_floats": (_L, "iiii i"),
     "mi_fwd": (_I, "pp ppp iiii i ffff ii p"),
     "mi_bwd": (_I, "ppp p pp iiii i fff i p"),

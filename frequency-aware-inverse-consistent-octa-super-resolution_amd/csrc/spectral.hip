@@ -23,6 +23,7 @@
 // Block 256 threads, output tile 64x64, K chunk 16; waves 2x2, four 32x32 accumulators each (Re_x, J_x, Re_y, J_y).
 //
 // The focal frequency loss (second half of this file) runs on the same tables, row pass and tile, with two accumulators.
+// The spectral-profile loss (third section) runs them on the half spectrum: columns 0..W/2 only, both GEMM passes half as wide.
 #include <cstdint>
 #include "common.h"
 
@@ -565,6 +566,356 @@ static int ffl_check(const char* what, const void* ws, int N, int C, int H, int 
 
 static int ffl_form(float alpha) { return alpha == 0.f ? FFL_ONE : alpha == 1.f ? FFL_SQRT : alpha == 2.f ? FFL_ID : FFL_POW; }
 
+
+// ---- spectral-profile loss (after Durall, Keuper, Keuper, CVPR 2020) --------------------------------------------------------------
+//   q = |fft2(x)|^2 / (HW),  A[k] = mean of q over the ring bin(u,v) = floor(M sqrt(u_c^2/H^2 + v_c^2/W^2)) = k,  M = min(H, W),
+//   a = log(A + eps);  L = mean_{n,c,k>=k_min} (a_x - a_y)^2, or on the batch means of a (the unpaired, domain form).
+// |F|^2 of a real image is point-symmetric and so is bin(u,v): only the columns v < Wh = W/2 + 1 are transformed, a column counting
+// m_v = 2 times unless it is its own mirror (v = 0, and v = W/2 for even W).  Both GEMM passes are half as wide as the other two
+// losses', forward and backward:
+//   [P | Q] = X [C_W[:, :Wh] | S_W[:, :Wh]]        row pass, W x 2Wh half tables (the caller's, cut from faoctasr_dft_tables)
+//   Re, J as above on H x Wh;  pw = m_v (Re^2 + J^2) / (HW)   formed in the accumulator registers
+//   A[k] = (1 / cnt_k) sum of pw over the bin      a gather along a host-built CSR list (the geometry is fixed): no atomics
+//   finish (one block, double, fixed order): logs, batch means, loss, and coef[p][k] = dL/dA[p,k] / cnt_k for the backward
+//   (dRe, dJ) = g (2/(HW)) m_v coef[p][bin] (Re, J) formed while staging;  [T1 | T2] as above;  dX = [T1 | T2] [C_W[:, :Wh]^T ; S_W[:, :Wh]^T]
+// x and y run one instruction sequence each (L(x,y) == L(y,x) bit for bit); the epilogues are compiled without contraction.
+// Wh == W (a measuring switch of tools/sprof_bench.py) runs the same kernels on the full spectrum with every m_v = 1.
+struct SprofWs {
+    float* pq;          // [sides][N*C][H][2Wh]: [P | Q] in the forward, [T1 | T2] in the backward
+    float* pw;          // [sides][N*C][H][Wh]: the weighted power plane
+    float* coef;        // [N*C][K]: the profile op's backward forms its coefficient table here
+    long total;
+};
+
+static SprofWs sprof_ws(float* ws, long sides, long imgs, long H, long Wh, long K) {
+    SprofWs p;
+    long off = 0;
+    p.pq = ws + off;
+    off += sides * imgs * H * 2 * Wh;
+    p.pw = ws + off;
+    off += sides * imgs * H * Wh;
+    p.coef = ws + off;
+    off += imgs * K;
+    p.total = off;
+    return p;
+}
+
+// number of radial bins, in integers: 1 + the largest k with k^2 H^2 W^2 <= M^2 ((H/2)^2 W^2 + (W/2)^2 H^2); sides <= 1024 fit int64
+static int sprof_bins(long H, long W) {
+    const long M = H < W ? H : W, hh = H / 2, ww = W / 2;
+    const long num = M * M * (hh * hh * W * W + ww * ww * H * H), den = H * H * W * W;
+    long k = 0;
+    while ((k + 1) * (k + 1) * den <= num) ++k;
+    return (int)k + 1;
+}
+
+__device__ __forceinline__ float sprof_mv(int v, int W, int Wh) { return (Wh == W || v == 0 || 2 * v == W) ? 1.f : 2.f; }
+
+// column pass on the half plane for S images (x, or x and y) of one (sample, channel): pw for every image; Re, J only for an image
+// whose save pointer is not null (its gradient will be wanted)
+template <int S>
+__global__ __launch_bounds__(256) void sprof_col_fwd_kernel(const float* __restrict__ pq, const float* __restrict__ tabH,
+                                                            float* __restrict__ pw, float* __restrict__ save_x, float* __restrict__ save_y,
+                                                            int H, int W, int Wh, long imgs) {
+#pragma clang fp contract(off)
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[2 * S][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int u0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const float* pqx = pq + img * H * 2 * Wh;
+    const float* pqy = pq + (imgs + img) * H * 2 * Wh;
+    f32x16 rx, jx, ry, jy;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rx[r] = jx[r] = ry[r] = jy[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, u0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int k = k0 + (e >> 6), v = v0 + (e & 63);
+            const bool ok = k < H && v < Wh;
+            const long o = (long)k * 2 * Wh + v;
+            Bs[0][e] = ok ? pqx[o] : 0.f;
+            Bs[1][e] = ok ? pqx[o + Wh] : 0.f;
+            if (S == 2) {
+                Bs[2 * S - 2][e] = ok ? pqy[o] : 0.f;
+                Bs[2 * S - 1][e] = ok ? pqy[o + Wh] : 0.f;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float px = Bs[0][bo], qx = Bs[1][bo];
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, px, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(as, px, jx, 0, 0, 0);
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qx, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qx, jx, 0, 0, 0);
+            if (S == 2) {
+                const float py = Bs[2 * S - 2][bo], qy = Bs[2 * S - 1][bo];
+                ry = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, py, ry, 0, 0, 0);
+                jy = __builtin_amdgcn_mfma_f32_32x32x2f32(as, py, jy, 0, 0, 0);
+                ry = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qy, ry, 0, 0, 0);
+                jy = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qy, jy, 0, 0, 0);
+            }
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < Wh) {
+        const long hwh = (long)H * Wh;
+        const float mv = sprof_mv(v, W, Wh), hw = (float)(H * W);
+        float* pwx = pw + img * hwh;
+        float* pwy = pw + (imgs + img) * hwh;
+        float* sx = save_x ? save_x + img * 2 * hwh : nullptr;
+        float* sy = (S == 2 && save_y) ? save_y + img * 2 * hwh : nullptr;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int u = u0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (u < H) {
+                const long o = (long)u * Wh + v;
+                pwx[o] = mv * ((rx[rr] * rx[rr] + jx[rr] * jx[rr]) / hw);
+                if (sx) {
+                    sx[o] = rx[rr];
+                    sx[hwh + o] = jx[rr];
+                }
+                if (S == 2) {
+                    pwy[o] = mv * ((ry[rr] * ry[rr] + jy[rr] * jy[rr]) / hw);
+                    if (sy) {
+                        sy[o] = ry[rr];
+                        sy[hwh + o] = jy[rr];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// one wave per (plane, bin): the bin's segment of the CSR list (half-plane indices in ascending order) added lane-strided in double,
+// then one butterfly.  A[plane][k] = sum / cnt_k
+__global__ __launch_bounds__(256) void sprof_bin_kernel(const float* __restrict__ pw, const int* __restrict__ csr_off,
+                                                        const int* __restrict__ csr_idx, const int* __restrict__ cnt, float* __restrict__ A,
+                                                        long planes, int K, long hwh) {
+    const int lane = threadIdx.x & 63;
+    const long id = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (id >= planes * K) return;                           // uniform over the wave
+    const int k = (int)(id % K);
+    const float* pl = pw + (id / K) * hwh;
+    int b = csr_off[k], e = csr_off[k + 1];
+    b = b < 0 ? 0 : b;
+    e = e > hwh ? (int)hwh : e;
+    double s = 0.0;
+    for (int i = b + lane; i < e; i += 64) {
+        const int j = csr_idx[i];
+        if (j >= 0 && j < hwh) s += (double)pl[j];
+    }
+    s = wave_sum(s);
+    if (lane == 0) A[id] = (float)(s / (double)cnt[k]);
+}
+
+// dL/dA / cnt_k of one entry, given d = dL/da already scaled
+__device__ __forceinline__ float sprof_coef(double d, double A, double eps, int cnt) { return (float)(d / (A + eps) / (double)cnt); }
+
+// single block, double, fixed order.  A: [2][imgs][K].  Paired form: per sample n the sum of (a_x - a_y)^2 over c and k >= k_min by
+// the block tree, the samples added in index order.  Batch form: thread k adds a[., k] over the planes in index order, then the
+// squared differences of the means go through the tree.  coef_x / coef_y (each may be nullptr) get dL/dA / cnt_k with the mean's
+// divisor folded in; per_image: of that sample's own mean
+__global__ __launch_bounds__(256) void sprof_finish_kernel(const float* __restrict__ A, const int* __restrict__ cnt, float* __restrict__ loss,
+                                                           float* __restrict__ per, float* __restrict__ coef_x, float* __restrict__ coef_y,
+                                                           int N, int C, int K, int k_min, double eps, int batch, int per_image) {
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const long imgs = (long)N * C;
+    const float* Ax = A;
+    const float* Ay = A + imgs * K;
+    const double bins = (double)(K - k_min);
+    if (batch) {
+        double acc = 0.0;
+        const double div = bins * (double)imgs;
+        for (int k = tid; k < K; k += 256) {
+            double sx = 0.0, sy = 0.0;
+            for (long p = 0; p < imgs; ++p) {
+                sx += log((double)Ax[p * K + k] + eps);
+                sy += log((double)Ay[p * K + k] + eps);
+            }
+            const double d = sx / (double)imgs - sy / (double)imgs;
+            const bool in = k >= k_min;
+            if (in) acc += d * d;
+            const double gx = in ? 2.0 * d / div : 0.0;
+            for (long p = 0; p < imgs; ++p) {
+                if (coef_x) coef_x[p * K + k] = sprof_coef(gx, (double)Ax[p * K + k], eps, cnt[k]);
+                if (coef_y) coef_y[p * K + k] = sprof_coef(-gx, (double)Ay[p * K + k], eps, cnt[k]);
+            }
+        }
+        acc = block_tree_256(acc, red);
+        if (tid == 0) *loss = (float)(acc / bins);
+        return;
+    }
+    const double div = (per_image ? 1.0 : (double)N) * (double)C * bins;
+    double total = 0.0;
+    for (int n = 0; n < N; ++n) {
+        double acc = 0.0;
+        for (long e = tid; e < (long)C * K; e += 256) {
+            const int k = (int)(e % K);
+            const long o = ((long)n * C + e / K) * K + k;
+            const double ax = (double)Ax[o], ay = (double)Ay[o];
+            const double d = log(ax + eps) - log(ay + eps);
+            const bool in = k >= k_min;
+            if (in) acc += d * d;
+            const double gx = in ? 2.0 * d / div : 0.0;
+            if (coef_x) coef_x[o] = sprof_coef(gx, ax, eps, cnt[k]);
+            if (coef_y) coef_y[o] = sprof_coef(-gx, ay, eps, cnt[k]);
+        }
+        acc = block_tree_256(acc, red);
+        total += acc;
+        if (tid == 0 && per) per[n] = (float)(acc / ((double)C * bins));
+    }
+    if (tid == 0) *loss = (float)(total / ((double)N * (double)C * bins));
+}
+
+// the profile op's backward: coef[p][k] = gA[p][k] / cnt_k
+__global__ __launch_bounds__(256) void sprof_cotangent_kernel(const float* __restrict__ gA, const int* __restrict__ cnt,
+                                                              float* __restrict__ coef, long n, int K) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) coef[i] = gA[i] / (float)cnt[i % K];
+}
+
+// [T1 | T2] = [C_H dRe + S_H dJ | C_H dJ - S_H dRe] on the half plane, for the x image (want_x) and / or the y image (want_y);
+// (dRe, dJ) = g (2/(HW)) m_v coef[p][bin(u,v)] (Re, J) formed from the saved planes while they are staged.  g: one device scalar,
+// or one per sample (g_stride 1), or nullptr (= 1: the profile op, whose cotangent is the coefficient table)
+__global__ __launch_bounds__(256) void sprof_col_bwd_kernel(const float* __restrict__ save_x, const float* __restrict__ save_y,
+                                                            const float* __restrict__ coef_x, const float* __restrict__ coef_y,
+                                                            const short* __restrict__ binmap, const float* __restrict__ tabH,
+                                                            const float* __restrict__ g, int g_stride, float* __restrict__ T, int H, int W,
+                                                            int Wh, int C, int K, long imgs, float c2, int want_x, int want_y) {
+#pragma clang fp contract(off)
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[4][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int h0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const long hwh = (long)H * Wh;
+    const float* plx = want_x ? save_x + img * 2 * hwh : nullptr;
+    const float* ply = want_y ? save_y + img * 2 * hwh : nullptr;
+    const float* cx = want_x ? coef_x + img * K : nullptr;
+    const float* cy = want_y ? coef_y + img * K : nullptr;
+    const int sv = v0 + (tid & 63);
+    const float gs = (g ? g[(img / C) * g_stride] : 1.f) * c2 * sprof_mv(sv, W, Wh);
+    f32x16 t1x, t2x, t1y, t2y;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t1x[r] = t2x[r] = t1y[r] = t2y[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, h0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int u = k0 + (e >> 6);
+            float drx = 0.f, djx = 0.f, dry = 0.f, djy = 0.f;
+            if (u < H && sv < Wh) {
+                const long o = (long)u * Wh + sv;
+                int b = binmap[o];
+                b = b < 0 ? 0 : (b < K ? b : K - 1);
+                if (want_x) {
+                    const float w = gs * cx[b];
+                    drx = w * plx[o];
+                    djx = w * plx[hwh + o];
+                }
+                if (want_y) {
+                    const float w = gs * cy[b];
+                    dry = w * ply[o];
+                    djy = w * ply[hwh + o];
+                }
+            }
+            Bs[0][e] = drx;
+            Bs[1][e] = djx;
+            Bs[2][e] = dry;
+            Bs[3][e] = djy;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            if (want_x) {
+                const float dr = Bs[0][bo], dj = Bs[1][bo];
+                t1x = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1x, 0, 0, 0);
+                t2x = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2x, 0, 0, 0);
+                t1x = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1x, 0, 0, 0);
+                t2x = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2x, 0, 0, 0);
+            }
+            if (want_y) {
+                const float dr = Bs[2][bo], dj = Bs[3][bo];
+                t1y = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1y, 0, 0, 0);
+                t2y = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2y, 0, 0, 0);
+                t1y = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1y, 0, 0, 0);
+                t2y = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2y, 0, 0, 0);
+            }
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < Wh) {
+        float* Tx = T + img * H * 2 * Wh;
+        float* Ty = T + (imgs + img) * H * 2 * Wh;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int h = h0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (h < H) {
+                const long o = (long)h * 2 * Wh + v;
+                if (want_x) {
+                    Tx[o] = t1x[rr];
+                    Tx[o + Wh] = t2x[rr];
+                }
+                if (want_y) {
+                    Ty[o] = t1y[rr];
+                    Ty[o + Wh] = t2y[rr];
+                }
+            }
+        }
+    }
+}
+
+static int sprof_check(const char* what, int sides, int N, int C, int H, int W, int Wh, int K) {
+    if (N < 1 || C < 1 || H < 2 || W < 2) return fail(FAOCTASR_EINVAL, "%s: bad shape N %d C %d H %d W %d (H, W >= 2)", what, N, C, H, W);
+    if (H > 1024 || W > 1024) return fail(FAOCTASR_EUNSUPPORTED, "%s: H %d, W %d > 1024", what, H, W);
+    if ((long)N * C * sides > 65535) return fail(FAOCTASR_EUNSUPPORTED, "%s: %d * N*C %ld > 65535", what, sides, (long)N * C);
+    if ((long)N * C * H > (1L << 21)) return fail(FAOCTASR_EUNSUPPORTED, "%s: N*C*H %ld > 2^21", what, (long)N * C * H);
+    if (Wh != W / 2 + 1 && Wh != W) return fail(FAOCTASR_EINVAL, "%s: Wh %d is neither W/2 + 1 = %d nor W = %d", what, Wh, W / 2 + 1, W);
+    if (K != sprof_bins(H, W)) return fail(FAOCTASR_EINVAL, "%s: K %d, but %d x %d has %d radial bins", what, K, H, W, sprof_bins(H, W));
+    return FAOCTASR_OK;
+}
+
+// row pass, column pass and binning of `sides` images (y == nullptr: one)
+static int sprof_profiles(const char* what, const float* x, const float* y, const float* tabH, const float* halfW, const int* csr_off,
+                          const int* csr_idx, const int* cnt, float* A, float* save_x, float* save_y, const SprofWs& p, int N, int C, int H,
+                          int W, int Wh, int K, hipStream_t stream) {
+    const long imgs = (long)N * C;
+    const int sides = y ? 2 : 1;
+    long diff = 0;
+    if (y) {
+        const intptr_t d = (intptr_t)y - (intptr_t)x;
+        if (d % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "%s: x and y are not 4-byte aligned to each other", what);
+        diff = (long)(d / (intptr_t)sizeof(float));
+    }
+    int rc = faoctasr_sgemm_batched(x, halfW, p.pq, (int)(imgs * H), 2 * Wh, W, W, 2 * Wh, 2 * Wh, diff, 0, imgs * H * 2 * Wh, sides,
+                                    (faoctasr_stream_t)stream);
+    if (rc) return rc;
+    dim3 grid((Wh + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    if (y)
+        hipLaunchKernelGGL(sprof_col_fwd_kernel<2>, grid, dim3(256), 0, stream, (const float*)p.pq, tabH, p.pw, save_x, save_y, H, W, Wh, imgs);
+    else
+        hipLaunchKernelGGL(sprof_col_fwd_kernel<1>, grid, dim3(256), 0, stream, (const float*)p.pq, tabH, p.pw, save_x, save_y, H, W, Wh, imgs);
+    rc = check_launch(what);
+    if (rc) return rc;
+    const long waves = sides * imgs * K;
+    hipLaunchKernelGGL(sprof_bin_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, (const float*)p.pw, csr_off, csr_idx, cnt, A,
+                       sides * imgs, K, (long)H * Wh);
+    return check_launch(what);
+}
+
 }  // namespace faoctasr
 
 using namespace faoctasr;
@@ -697,4 +1048,87 @@ extern "C" int faoctasr_ffl_bwd(const float* g, const float* planes, const float
     hipLaunchKernelGGL(negate_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, (const float*)dx,
                        dy, n);
     return check_launch("ffl_bwd (negation)");
+}
+
+extern "C" long faoctasr_sprof_workspace_floats(int sides, int N, int C, int H, int W, int Wh, int K) {
+    if (sides < 1 || sides > 2) {
+        fail(FAOCTASR_EINVAL, "sprof_workspace_floats: sides %d is neither 1 nor 2", sides);
+        return -1;
+    }
+    if (sprof_check("sprof_workspace_floats", sides, N, C, H, W, Wh, K)) return -1;
+    return sprof_ws(nullptr, sides, (long)N * C, H, Wh, K).total;
+}
+
+extern "C" int faoctasr_sprof_profile_fwd(const float* x, const float* tabH, const float* halfW, const int* csr_off, const int* csr_idx,
+                                          const int* cnt, float* A, float* save, float* workspace, int N, int C, int H, int W, int Wh, int K,
+                                          faoctasr_stream_t stream) {
+    if (!x || !tabH || !halfW || !csr_off || !csr_idx || !cnt || !A || !workspace) return fail(FAOCTASR_EINVAL, "sprof_profile_fwd: null pointer");
+    int rc = sprof_check("sprof_profile_fwd", 1, N, C, H, W, Wh, K);
+    if (rc) return rc;
+    const SprofWs p = sprof_ws(workspace, 1, (long)N * C, H, Wh, K);
+    return sprof_profiles("sprof_profile_fwd", x, nullptr, tabH, halfW, csr_off, csr_idx, cnt, A, save, nullptr, p, N, C, H, W, Wh, K,
+                          (hipStream_t)stream);
+}
+
+extern "C" int faoctasr_sprof_loss_fwd(const float* x, const float* y, const float* tabH, const float* halfW, const int* csr_off,
+                                       const int* csr_idx, const int* cnt, double eps, int k_min, int batch_profile, int per_image, float* loss,
+                                       float* loss_per_image, float* A, float* save_x, float* save_y, float* workspace, int N, int C, int H,
+                                       int W, int Wh, int K, faoctasr_stream_t stream) {
+    if (!x || !y || !tabH || !halfW || !csr_off || !csr_idx || !cnt || !loss || !A || !workspace)
+        return fail(FAOCTASR_EINVAL, "sprof_loss_fwd: null pointer");
+    int rc = sprof_check("sprof_loss_fwd", 2, N, C, H, W, Wh, K);
+    if (rc) return rc;
+    if (!(eps > 0.0) || eps > 1.0e300) return fail(FAOCTASR_EINVAL, "sprof_loss_fwd: eps %g must be finite and > 0", eps);
+    if (k_min < 0 || k_min >= K) return fail(FAOCTASR_EINVAL, "sprof_loss_fwd: k_min %d outside [0, %d)", k_min, K);
+    if (per_image && (batch_profile || !loss_per_image))
+        return fail(FAOCTASR_EINVAL, "sprof_loss_fwd: per_image needs loss_per_image and excludes batch_profile");
+    const long imgs = (long)N * C;
+    const SprofWs p = sprof_ws(workspace, 2, imgs, H, Wh, K);
+    rc = sprof_profiles("sprof_loss_fwd", x, y, tabH, halfW, csr_off, csr_idx, cnt, A, save_x, save_y, p, N, C, H, W, Wh, K, (hipStream_t)stream);
+    if (rc) return rc;
+    // the coefficient table of a side follows its saved planes
+    const long planes = imgs * 2 * H * Wh;
+    hipLaunchKernelGGL(sprof_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)A, cnt, loss, loss_per_image,
+                       save_x ? save_x + planes : nullptr, save_y ? save_y + planes : nullptr, N, C, K, k_min, eps, batch_profile ? 1 : 0,
+                       per_image ? 1 : 0);
+    return check_launch("sprof_loss_fwd (finish)");
+}
+
+extern "C" int faoctasr_sprof_bwd(const float* g, int g_per_image, const float* gA, const float* save_x, const float* save_y, const float* tabH,
+                                  const float* halfW, const short* binmap, const int* cnt, float* dx, float* dy, float* workspace, int N, int C,
+                                  int H, int W, int Wh, int K, faoctasr_stream_t stream) {
+    if (!tabH || !halfW || !binmap || !cnt || !workspace) return fail(FAOCTASR_EINVAL, "sprof_bwd: null pointer");
+    if (!g == !gA) return fail(FAOCTASR_EINVAL, "sprof_bwd: exactly one of g (the loss) and gA (the profile) must be given");
+    int rc = sprof_check("sprof_bwd", gA ? 1 : 2, N, C, H, W, Wh, K);
+    if (rc) return rc;
+    if (gA && dy) return fail(FAOCTASR_EINVAL, "sprof_bwd: the profile has one input");
+    if ((dx && !save_x) || (dy && !save_y)) return fail(FAOCTASR_EINVAL, "sprof_bwd: a gradient is wanted for a side the forward saved nothing for");
+    if (!dx && !dy) return FAOCTASR_OK;
+    const long imgs = (long)N * C, planes = imgs * 2 * H * Wh;
+    const hipStream_t st = (hipStream_t)stream;
+    const SprofWs p = sprof_ws(workspace, gA ? 1 : 2, imgs, H, Wh, K);
+    const float* coef_x = dx ? save_x + planes : nullptr;
+    const float* coef_y = dy ? save_y + planes : nullptr;
+    if (gA) {
+        const long n = imgs * K;
+        hipLaunchKernelGGL(sprof_cotangent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gA, cnt, p.coef, n, K);
+        rc = check_launch("sprof_bwd (cotangent)");
+        if (rc) return rc;
+        coef_x = p.coef;
+    }
+    dim3 grid((Wh + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(sprof_col_bwd_kernel, grid, dim3(256), 0, st, save_x, save_y, coef_x, coef_y, binmap, tabH, g, g_per_image ? 1 : 0, p.pq,
+                       H, W, Wh, C, K, imgs, (float)(2.0 / ((double)H * (double)W)), dx ? 1 : 0, dy ? 1 : 0);
+    rc = check_launch("sprof_bwd (column pass)");
+    if (rc) return rc;
+    // dX = [T1 | T2] [C_W[:, :Wh]^T ; S_W[:, :Wh]^T]: the transposed half table follows the forward one
+    const float* stacked = halfW + 2L * W * Wh;
+    const long sT = imgs * H * 2 * Wh;
+    if (dx && dy) {
+        const intptr_t diff = (intptr_t)dy - (intptr_t)dx;
+        if (diff % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "sprof_bwd: dx and dy are not 4-byte aligned to each other");
+        return faoctasr_sgemm_batched(p.pq, stacked, dx, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, sT, 0, (long)(diff / (intptr_t)sizeof(float)), 2,
+                                      stream);
+    }
+    return faoctasr_sgemm_batched(dx ? p.pq : p.pq + sT, stacked, dx ? dx : dy, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, 0, 0, 0, 1, stream);
 }

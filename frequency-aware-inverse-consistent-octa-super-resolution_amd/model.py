@@ -72,6 +72,31 @@ class FocalFrequencyLoss(nn.Module):
         return "loss_weight=%g, alpha=%g, log_matrix=%s, batch_matrix=%s" % (self.loss_weight, self.alpha, self.log_matrix, self.batch_matrix)
 
 
+class SpectralProfileLoss(nn.Module):
+    """The spectral-profile loss (after Durall, Keuper, Keuper, CVPR 2020; not in the reference): the squared distance of the
+    log azimuthally averaged power spectra ``log(A + eps)`` of two images over the rings k >= ``k_min`` (1 drops the mean
+    brightness).  Generators that upsample with transposed convolutions, as both here do, cannot reproduce the radial decay of the
+    power spectrum of real images; this statistic measures exactly that decay.  It is phase-blind and one short vector per image, so
+    with ``batch_profile`` the log-profiles are averaged over the batch first and the two operands need not be paired: a fake
+    against real images of the domain it should belong to, which is what ``TrainStep(sprof_weight=...)`` adds.  A distortion: 0 for
+    identical inputs.  One fused HIP path on the half spectrum (``ops.spectral_profile_loss``)."""
+
+    def __init__(self, eps=1e-8, k_min=1, batch_profile=False):
+        super().__init__()
+        self.eps, self.k_min = ops.check_sprof_params(eps, k_min)
+        self.batch_profile = bool(batch_profile)
+
+    def forward(self, x, y):
+        return ops.spectral_profile_loss(x, y, self.eps, self.k_min, self.batch_profile)
+
+    def index(self, a, b, per_image=False):
+        """The paired form whatever ``batch_profile`` says (``evaluate_pairs_with(model, pairs, sprof=SpectralProfileLoss())``)."""
+        return ops.spectral_profile_loss(a, b, self.eps, self.k_min, False, per_image)
+
+    def extra_repr(self):
+        return "eps=%g, k_min=%d, batch_profile=%s" % (self.eps, self.k_min, self.batch_profile)
+
+
 class MutualInformationLoss(nn.Module):
     """The differentiable mutual information of two images (not in the reference, which scores results with a hard-histogram NMI,
     utils.py:209-212): Gaussian Parzen windows on ``bins`` centres over ``value_range``, a soft joint histogram per (n, c) plane,

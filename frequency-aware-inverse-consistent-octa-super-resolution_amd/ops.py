@@ -2388,6 +2388,230 @@ def focal_frequency_loss(x, y, alpha=1.0, log_matrix=False, batch_matrix=False):
 
 
 # ----------------------------------------------------------------------------------------
+# spectral-profile loss (after Durall, Keuper, Keuper, CVPR 2020) on the half-spectrum DFT GEMMs
+# ----------------------------------------------------------------------------------------
+SPROF_MAX_SIDE = 1024
+_radial_cache = {}
+_sprof_geom_cache = {}
+_sprof_half_cache = {}
+
+
+def radial_bins(H, W):
+    """``(bin, cnt)`` of the azimuthal average of an H x W spectrum, on the host: ``bin`` int64 (H, W), the ring of every UNSHIFTED
+    frequency, ``floor(M sqrt(u_c^2/H^2 + v_c^2/W^2))`` with ``M = min(H, W)`` and centred ``u_c = ((u + H//2) mod H) - H//2``; ``cnt``
+    int64 (K,), the positions per ring, ``K = 1 + floor(M sqrt((H//2)^2/H^2 + (W//2)^2/W^2))``.  Exact: the floor is settled in
+    int64 (the largest k with ``k^2 H^2 W^2 <= M^2 (u_c^2 W^2 + v_c^2 H^2)``), a floating square root only proposes it.  No ring is
+    empty and ``bin(u, v) == bin(-u, -v)``.  2 <= H, W <= 1024; cached, so do not write into the result."""
+    if isinstance(H, bool) or isinstance(W, bool) or not (isinstance(H, int) and isinstance(W, int)) or not (2 <= H <= SPROF_MAX_SIDE and 2 <= W <= SPROF_MAX_SIDE):
+        raise ValueError("radial_bins: H and W must be ints in [2, %d], got %r and %r" % (SPROF_MAX_SIDE, H, W))
+    hit = _radial_cache.get((H, W))
+    if hit is not None:
+        return hit
+    M = min(H, W)
+    uc = ((torch.arange(H, dtype=torch.int64) + H // 2) % H - H // 2)[:, None]
+    vc = ((torch.arange(W, dtype=torch.int64) + W // 2) % W - W // 2)[None, :]
+    num, den = M * M * (uc * uc * (W * W) + vc * vc * (H * H)), H * H * W * W
+    k = torch.sqrt(num.double() / den).floor().long()
+    for _ in range(3):                                       # the proposal is off by at most one; three rounds leave a margin
+        k = k + ((k + 1) * (k + 1) * den <= num).long() - (k * k * den > num).long()
+    if not bool(((k * k * den <= num) & ((k + 1) * (k + 1) * den > num)).all()):
+        raise AssertionError("radial_bins: the integer floor did not settle at %d x %d" % (H, W))
+    K = 1 + math.isqrt(M * M * ((H // 2) ** 2 * W * W + (W // 2) ** 2 * H * H) // den)
+    cnt = torch.bincount(k.flatten(), minlength=K)
+    if cnt.numel() != K or int(cnt.min()) < 1 or int(cnt.sum()) != H * W:
+        raise AssertionError("radial_bins: %d x %d gave %d bins for K = %d, smallest count %d" % (H, W, cnt.numel(), K, int(cnt.min())))
+    _radial_cache[(H, W)] = (k, cnt)
+    return k, cnt
+
+
+def _dev_key(device):
+    device = torch.device(device)
+    return device, (device.type, device.index if device.index is not None else torch.cuda.current_device())
+
+
+def sprof_half_tables(W, device, full=False):
+    """The half-spectrum tables of the W-point DFT for the spectral profile, cut from ``dft_tables(W)`` once per (W, device):
+    ``[C_W[:, :Wh] | S_W[:, :Wh]]`` (W x 2Wh) followed by its transpose stacked ``[C^T ; S^T]`` (2Wh x W), ``Wh = W//2 + 1``
+    (``full``, a measuring switch: ``Wh = W``).  Like the DFT tables, built before any stream forks or a capture begins."""
+    device, dk = _dev_key(device)
+    key = (W, bool(full)) + dk
+    t = _sprof_half_cache.get(key)
+    if t is None:
+        Wh = W if full else W // 2 + 1
+        cs = dft_tables(W, device)[:2 * W * W].view(W, 2 * W)
+        c, s = cs[:, :Wh], cs[:, W:W + Wh]
+        t = torch.cat((torch.cat((c, s), 1).reshape(-1), torch.cat((c.t(), s.t()), 0).reshape(-1))).contiguous()
+        _sprof_half_cache[key] = t
+    return t
+
+
+def sprof_host_geometry(H, W, full=False):
+    """``(K, Wh, csr_off int32 (K+1,), csr_idx int32 (H*Wh,), cnt int32 (K,), binmap int16 (H, Wh))`` on the host, from
+    ``radial_bins``: the half-plane positions (columns < ``Wh = W//2 + 1``; ``full``: every column) sorted by (bin, position) with
+    their offsets per bin, the FULL-plane counts, and the bin of every half-plane position."""
+    bins, cnt = radial_bins(H, W)
+    K, Wh = cnt.numel(), (W if full else W // 2 + 1)
+    half = bins[:, :Wh].contiguous()
+    flat = half.flatten()
+    off = torch.zeros(K + 1, dtype=torch.int64)
+    off[1:] = torch.cumsum(torch.bincount(flat, minlength=K), 0)
+    return K, Wh, off.int(), torch.argsort(flat, stable=True).int(), cnt.int(), half.short()
+
+
+def sprof_geometry(H, W, device, full=False):
+    """``sprof_host_geometry`` on the device, what the spectral-profile kernels read besides the DFT tables: built once per
+    (H, W, device)."""
+    device, dk = _dev_key(device)
+    key = (H, W, bool(full)) + dk
+    g = _sprof_geom_cache.get(key)
+    if g is None:
+        if device.type != "cuda":
+            raise _lib.KernelError("spectral profile: the kernels run on a GPU; got device %s" % device)
+        g = tuple(t.to(device) if torch.is_tensor(t) else t for t in sprof_host_geometry(H, W, full))
+        _sprof_geom_cache[key] = g
+    return g
+
+
+def sprof_tables(H, W, device, full=False):
+    """Every table of one (H, W, device): ``TrainStep.step`` calls this before its streams fork."""
+    return (dft_tables(H, device), sprof_half_tables(W, device, full)) + sprof_geometry(H, W, device, full)
+
+
+def check_sprof_params(eps, k_min):
+    """``(eps, k_min)`` of the spectral-profile loss as a float and an int: eps finite and > 0, k_min an int >= 0, or ValueError
+    (``k_min < K`` is checked against the shape)."""
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps > 0):
+        raise ValueError("spectral profile loss: eps must be a finite number > 0, got %r" % (eps,))
+    if isinstance(k_min, bool) or not isinstance(k_min, int) or k_min < 0:
+        raise ValueError("spectral profile loss: k_min must be an int >= 0, got %r" % (k_min,))
+    return float(eps), k_min
+
+
+def _sprof_ws(sides, N, C, H, W, Wh, K, device):
+    n = _lib.load().faoctasr_sprof_workspace_floats(sides, N, C, H, W, Wh, K)
+    if n < 0:
+        raise _lib.KernelError("faoctasr_sprof_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+    return torch.empty(max(n, 1), dtype=torch.float32, device=device)         # scratch of this call: free again behind it on the stream
+
+
+def _check_sprof_operands(what, *ts):
+    for x in ts:
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise _lib.KernelError("%s operands must be (N,C,H,W) tensors, got %s" % (what, tuple(getattr(x, "shape", ()))))
+    for x in ts:
+        if x.dtype != torch.float32:
+            raise _lib.KernelError("%s operands must be fp32, got %s" % (what, x.dtype))
+    for x in ts:
+        if not x.is_cuda:
+            raise _lib.KernelError("%s runs as HIP kernels on one GPU; got device %s" % (what, x.device))
+        if not (2 <= x.shape[2] <= SPROF_MAX_SIDE and 2 <= x.shape[3] <= SPROF_MAX_SIDE):
+            raise _lib.KernelError("%s needs 2 <= H, W <= %d, got %s" % (what, SPROF_MAX_SIDE, tuple(x.shape)))
+
+
+def sprof_loss_forward(x, y, eps=1e-8, k_min=1, batch_profile=False, per_image=False, save_x=False, save_y=False, full=False):
+    """The forward launches of the spectral-profile loss without autograd: ``(loss 0-dim, per_image (N,) or None, profiles
+    (2, N, C, K), saved_x, saved_y)``; ``saved_*`` (planes and coefficient table) only where ``save_*`` asks."""
+    x, y = _c(x), _c(y)
+    N, C, H, W = x.shape
+    tab_h, half_w, K, Wh, off, idx, cnt, _ = sprof_tables(H, W, x.device, full)
+    dev = x.device
+    ws = _sprof_ws(2, N, C, H, W, Wh, K, dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    per = torch.empty(N, dtype=torch.float32, device=dev) if per_image else None
+    prof = torch.empty((2, N, C, K), dtype=torch.float32, device=dev)
+    sx = torch.empty(N * C * (2 * H * Wh + K), dtype=torch.float32, device=dev) if save_x else None
+    sy = torch.empty(N * C * (2 * H * Wh + K), dtype=torch.float32, device=dev) if save_y else None
+    call("sprof_loss_fwd", ptr(x), ptr(y), ptr(tab_h), ptr(half_w), off.data_ptr(), idx.data_ptr(), cnt.data_ptr(), eps, k_min,
+         int(batch_profile), int(per_image), ptr(out), ptr(per), ptr(prof), ptr(sx), ptr(sy), ptr(ws), N, C, H, W, Wh, K, stream_ptr())
+    return out, per, prof, sx, sy
+
+
+class _SpectralProfileLoss(Function):
+    @staticmethod
+    def forward(ctx, x, y, eps, k_min, batch_profile, per_image, save_x, save_y, full):
+        out, per, _, sx, sy = sprof_loss_forward(x, y, eps, k_min, batch_profile, per_image, save_x, save_y, full)
+        ctx.save_for_backward(sx, sy)
+        ctx.cfg = (per_image, full) + tuple(x.shape)
+        ctx.dev = x.device
+        return per if per_image else out
+
+    @staticmethod
+    def backward(ctx, g):
+        sx, sy = ctx.saved_tensors
+        per_image, full, N, C, H, W = ctx.cfg
+        tab_h, half_w, K, Wh, _, _, cnt, binmap = sprof_tables(H, W, ctx.dev, full)
+        g = _c(g)
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=ctx.dev) if ctx.needs_input_grad[0] else None
+        dy = torch.empty((N, C, H, W), dtype=torch.float32, device=ctx.dev) if ctx.needs_input_grad[1] else None
+        ws = _sprof_ws(2, N, C, H, W, Wh, K, ctx.dev)
+        call("sprof_bwd", ptr(g), int(per_image), None, ptr(sx), ptr(sy), ptr(tab_h), ptr(half_w), binmap.data_ptr(), cnt.data_ptr(), ptr(dx),
+             ptr(dy), ptr(ws), N, C, H, W, Wh, K, stream_ptr())
+        return (dx, dy) + (None,) * 7
+
+
+def spectral_profile_loss(x, y, eps=1e-8, k_min=1, batch_profile=False, per_image=False, _full_spectrum=False):
+    """The spectral-profile loss of x, y (N,C,H,W) fp32 on one GPU, 2 <= H, W <= 1024, with gradients to both inputs: with
+    ``A[n,c,k]`` the azimuthally averaged power spectrum ``|fft2|^2 / (HW)`` over the rings of ``radial_bins(H, W)`` and ``a =
+    log(A + eps)``, the mean over n, c and k >= ``k_min`` of ``(a_x - a_y)^2`` (0-dim; ``per_image``: (N,), each sample's mean over c
+    and k).  ``batch_profile``: ``a`` is first averaged over n and c and the loss is the mean over k >= ``k_min`` of the squared
+    difference of the two batch means -- phase-blind, translation-invariant and one short vector per domain, so x and y need not be
+    paired (a fake against real images of the domain it should belong to).  ``k_min = 1`` drops the DC ring (the mean brightness).
+    After Durall, Keuper and Keuper (CVPR 2020), whose binary cross-entropy on min-max-normalised profiles has no gradient at the
+    extremes; this is the squared distance of log-profiles.  Only the half spectrum is transformed (csrc/spectral.hip).  Nothing is
+    kept for a side that needs no gradient; no double backward.  Bit-reproducible, ``L(x, y) == L(y, x)`` bit for bit, always exact
+    fp32 (``conv_precision`` does not apply)."""
+    eps, k_min = check_sprof_params(eps, k_min)
+    if per_image and batch_profile:
+        raise ValueError("spectral profile loss: per_image has no meaning with batch_profile (one value per batch)")
+    _check_sprof_operands("spectral_profile_loss", x, y)
+    if x.shape != y.shape:
+        raise _lib.KernelError("spectral_profile_loss operands must have one shape: %s vs %s" % (tuple(x.shape), tuple(y.shape)))
+    if x.device != y.device:
+        raise _lib.KernelError("spectral_profile_loss runs as HIP kernels on one GPU; got devices %s and %s" % (x.device, y.device))
+    K = radial_bins(x.shape[2], x.shape[3])[1].numel()
+    if k_min >= K:
+        raise ValueError("spectral profile loss: k_min %d must be below the %d rings of a %d x %d spectrum" % (k_min, K, x.shape[2], x.shape[3]))
+    grad = torch.is_grad_enabled()                                                   # grad mode is off inside Function.forward
+    return _SpectralProfileLoss.apply(x, y, eps, k_min, bool(batch_profile), bool(per_image), grad and x.requires_grad, grad and y.requires_grad,
+                                      bool(_full_spectrum))
+
+
+class _SpectralProfile(Function):
+    @staticmethod
+    def forward(ctx, x, save, full):
+        x = _c(x)
+        N, C, H, W = x.shape
+        tab_h, half_w, K, Wh, off, idx, cnt, _ = sprof_tables(H, W, x.device, full)
+        ws = _sprof_ws(1, N, C, H, W, Wh, K, x.device)
+        A = torch.empty((N, C, K), dtype=torch.float32, device=x.device)
+        planes = torch.empty(N * C * 2 * H * Wh, dtype=torch.float32, device=x.device) if save else None
+        call("sprof_profile_fwd", ptr(x), ptr(tab_h), ptr(half_w), off.data_ptr(), idx.data_ptr(), cnt.data_ptr(), ptr(A), ptr(planes), ptr(ws),
+             N, C, H, W, Wh, K, stream_ptr())
+        ctx.save_for_backward(planes)
+        ctx.cfg = (full, N, C, H, W)
+        return A
+
+    @staticmethod
+    def backward(ctx, gA):
+        full, N, C, H, W = ctx.cfg
+        planes, = ctx.saved_tensors
+        tab_h, half_w, K, Wh, _, _, cnt, binmap = sprof_tables(H, W, planes.device, full)
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=planes.device)
+        ws = _sprof_ws(1, N, C, H, W, Wh, K, planes.device)
+        call("sprof_bwd", None, 0, ptr(_c(gA)), ptr(planes), None, ptr(tab_h), ptr(half_w), binmap.data_ptr(), cnt.data_ptr(), ptr(dx), None,
+             ptr(ws), N, C, H, W, Wh, K, stream_ptr())
+        return dx, None, None
+
+
+def spectral_profile(x, _full_spectrum=False):
+    """The azimuthally averaged power spectrum of x (N,C,H,W) fp32 on one GPU, 2 <= H, W <= 1024: ``A[n,c,k]``, the mean of
+    ``|fft2(x[n,c])|^2 / (HW)`` over ring k of ``radial_bins(H, W)``, (N, C, K) fp32, differentiable (no double backward).
+    ``sum_k cnt_k A[k] = sum x^2`` (Parseval).  The launches of ``spectral_profile_loss`` for one image."""
+    _check_sprof_operands("spectral_profile", x)
+    return _SpectralProfile.apply(x, torch.is_grad_enabled() and x.requires_grad, bool(_full_spectrum))
+
+
+# ----------------------------------------------------------------------------------------
 # differentiable mutual information (Gaussian Parzen windows, soft joint histogram; csrc/mi.hip)
 # ----------------------------------------------------------------------------------------
 MI_MAX_BINS = 64

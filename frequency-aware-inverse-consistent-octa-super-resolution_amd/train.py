@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from . import ops
 from ._lib import KernelError, call, ptr, stream_ptr
-from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A
+from .model import FocalFrequencyLoss, FS_DiscriminatorA, FS_DiscriminatorB, MutualInformationLoss, NetworkA2B, NetworkB2A, SpectralProfileLoss
 from .ssim import GMSD, MSGMSD, MSSSIM, VIF, HaarPSI, LNCC, SoftClDice, VesselDice
 from .utils import DeviceReplayBuffer, ReplayBuffer, set_requires_grad, weights_init_normal
 from .wavelets import CWSSIM, DTCWTMagnitudeLoss, DWTForward, SWTForward
@@ -224,7 +224,8 @@ _Term = namedtuple("_Term", "name side share attr build check", defaults=(None, 
 
 #: The opt-in terms of ``loss_G``, in the order they are added to it.  ``name`` gives the key ``loss_<name>`` and the attribute
 #: ``<name>_weight`` (0 = off: no module is built, nothing is launched).  ``side`` is the image pair a term compares: "cycle" =
-#: (recovered_X, real_X), "fake" = (a fake, the image of the other domain it was made from).  ``share(step, x, y)`` is the UNWEIGHTED
+#: (recovered_X, real_X), "fake" = (a fake, the image of the other domain it was made from), "domain" = (a fake, the real image of the domain the fake should
+#: belong to: fake_B with real_B -- the two are not paired, so only a statistic of the whole image can sit here).  ``share(step, x, y)`` is the UNWEIGHTED
 #: value for one pair: the loss is ``w * (share(pair A) + share(pair B))`` in ``generator_loss`` and ``w * share(pair)`` on each chain
 #: of the two-chain schedule.  ``build(k, dev)`` makes the module from the constructor's keywords ``k`` and is stored under ``attr``
 #: (None when the weight is 0); ``share`` reads it from the step at call time.  ``check``: how ``_check_weight`` treats the weight.
@@ -258,6 +259,8 @@ OPT_IN_TERMS = (
           lambda k, dev: MutualInformationLoss(bins=k["mi_bins"], sigma_ratio=k["mi_sigma_ratio"], normalized=k["mi_normalized"]), "number"),
     _Term("lncc", "fake", lambda s, fake, src: 1 - s.lncc(fake, src), "lncc",
           lambda k, dev: LNCC(win=k["lncc_win"], eps=k["lncc_eps"]).to(dev), "number"),
+    _Term("sprof", "domain", lambda s, fake, real: s.sprof(fake, real), "sprof",             # a distortion between UNPAIRED images
+          lambda k, dev: SpectralProfileLoss(eps=k["sprof_eps"], k_min=k["sprof_k_min"], batch_profile=k["sprof_batch"]), "number"),
 )
 
 
@@ -313,7 +316,8 @@ class TrainStep:
                  reproducible_forward=False, phase_weight=0.0, phase_radius=5.0, tv_weight=0.0, dwt_wave="haar", dwt_mode="reflect",
                  dwt_stationary=False, cwt_weight=0.0, cwt_levels=1, cwt_biort="near_sym_a", cwt_qshift="qshift_a", cwt_mode="symmetric",
                  cwssim_weight=0.0, cwssim_levels=2, cwssim_win=7, cwssim_biort="near_sym_a", cwssim_qshift="qshift_a", cwssim_mode="symmetric",
-                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None, cldice_weight=0.0, cldice_iters=3, ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
+                 msssim_weight=0.0, msssim_levels=5, msssim_weights=None, cldice_weight=0.0, cldice_iters=3, sprof_weight=0.0, sprof_eps=1e-8, sprof_k_min=1, sprof_batch=True,
+                 ffl_weight=0.0, ffl_alpha=1.0, ffl_log_matrix=False,
                  ffl_batch_matrix=False, vif_weight=0.0, vif_sigma_n_sq=2.0, mi_weight=0.0, mi_bins=32, mi_sigma_ratio=1.0, mi_normalized=False,
                  vessel_weight=0.0, vessel_sigmas=(1., 2., 3.), vessel_c=0.1,
                  haarpsi_weight=0.0, haarpsi_c=30.0, haarpsi_alpha=4.2, gmsd_weight=0.0, gmsd_multiscale=False, gmsd_c=0.0026,
@@ -397,7 +401,15 @@ class TrainStep:
         (1 - S(fake_A, real_B)))`` to ``loss_G``, S the local normalised cross-correlation ``LNCC(win=lncc_win, eps=lncc_eps)``: the
         squared correlation coefficient of a fake and the image of the other domain it was made from inside a sliding box.  Where
         the mutual information sees one joint histogram per plane, this term is spatial: a vessel that moved lowers it wherever it
-        moved, whatever the intensity map between the domains.  The gradient reaches the fake only."""
+        moved, whatever the intensity map between the domains.  The gradient reaches the fake only.
+
+        ``sprof_weight`` (default 0: nothing is constructed, built or launched): adds ``loss_sprof = sprof_weight * (S(fake_B, real_B) +
+        S(fake_A, real_A))`` to ``loss_G``, S the spectral-profile loss ``SpectralProfileLoss(eps=sprof_eps, k_min=sprof_k_min,
+        batch_profile=sprof_batch)``: the squared distance of the log azimuthally averaged power spectra.  Every other term compares a
+        generated image with a specific partner image; this one compares a fake with the DOMAIN it should belong to (the real batch of
+        that domain, unpaired), and it measures the radial decay of the spectrum that generators with transposed convolutions get wrong
+        at the high frequencies.  ``sprof_batch`` (default on) averages the log-profiles over the batch first; off, sample i of the fake
+        is held against sample i of the real batch.  The gradient reaches the fake only."""
         keywords = dict(locals())                   # what OPT_IN_TERMS' weights and module builders read
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
@@ -671,6 +683,7 @@ class TrainStep:
             root = L["loss_GAN_B2A"] + L["loss_cycle_BAB"]
             extra_B = self._extension_terms(o["recovered_B"], real_B)       # the opt-in terms (OPT_IN_TERMS): one half per chain
             extra_B.update(self._fake_terms(o["fake_A"], real_B))           # fake_A was made on this stream, from real_B
+            extra_B.update(self._pair_terms("domain", o["fake_A"], real_A))   # ... and should pass for an image of domain A
             for k, v in extra_B.items():
                 root = root + v
         # ---- chain A, losses and backward
@@ -682,6 +695,7 @@ class TrainStep:
             chain_A = L["loss_GAN_A2B"] + L["loss_cycle_ABA"]
             extra_A = self._extension_terms(o["recovered_A"], real_A)
             extra_A.update(self._fake_terms(o["fake_B"], real_A))           # ... and fake_B's shares join chain A's, on chain A's stream
+            extra_A.update(self._pair_terms("domain", o["fake_B"], real_B))
             for k, v in extra_A.items():
                 chain_A = chain_A + v
             ops.wgrad_stream = side
@@ -754,7 +768,8 @@ class TrainStep:
         else:
             L["loss_idt"] = ops.l1_loss(real_A, o["idt_A"], w["beta2"]) + ops.l1_loss(real_B, o["idt_B"], w["beta2"])
             total = total + L["loss_idt"]
-        pairs = {"cycle": (("recovered_A", real_A), ("recovered_B", real_B)), "fake": (("fake_B", real_A), ("fake_A", real_B))}
+        pairs = {"cycle": (("recovered_A", real_A), ("recovered_B", real_B)), "fake": (("fake_B", real_A), ("fake_A", real_B)),
+                 "domain": (("fake_B", real_B), ("fake_A", real_A))}
         for term in OPT_IN_TERMS:                   # both pairs at once: the A pair is the left operand of the sum
             weight = getattr(self, term.name + "_weight")
             if not weight:
@@ -830,6 +845,9 @@ class TrainStep:
         if self.phase_weight or self.ffl_weight:    # the DFT tables are read on both chains' streams: built (once) before the streams fork
             for n in sorted(set(real_A.shape[-2:]) | set(real_B.shape[-2:])):
                 ops.dft_tables(n, self.device)
+        if self.sprof_weight:                       # ... and so are the half tables, the bin map and the gather list of the spectral profile
+            for h, w in sorted({tuple(real_A.shape[-2:]), tuple(real_B.shape[-2:])}):
+                ops.sprof_tables(h, w, self.device)
         # below ~2 x 256^2 pixels per batch the step is bound by the host's enqueue rate, and the extra events / stream switches
         # of the schedule cost more than the concurrency returns (batch 1 at 256^2: 41.8 vs 39.3 ms; batch 2: 48.3 vs 52.8)
         # ... a CAPTURED step has no host in its way: there the schedule pays at every size (batch 1: 29.9 against 35.4 ms per replay)

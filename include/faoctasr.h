@@ -290,6 +290,37 @@ int faoctasr_ffl_fwd(const float* x, const float* y, const float* tabH, const fl
 int faoctasr_ffl_bwd(const float* g, const float* planes, const float* tabH, const float* tabW, float alpha, int log_matrix,
                      float* dx, float* dy, float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
 
+/* ---- spectral-profile loss (after Durall, Keuper, Keuper, CVPR 2020; not part of the reference) ----------
+ * q = |fft2(x)|^2 / (HW) per plane; A[k] = the mean of q over the ring bin(u,v) = floor(M sqrt(u_c^2/H^2 + v_c^2/W^2)) = k of centred
+ * frequencies, M = min(H, W), K = 1 + floor(M sqrt((H/2)^2/H^2 + (W/2)^2/W^2)) bins; a = log(A + eps).  The loss is the mean over
+ * n, c and k >= k_min of (a_x - a_y)^2 or, with batch_profile, the mean over k >= k_min of the squared difference of the batch means
+ * of a (phase-blind and translation-invariant, so meaningful between unpaired images).  2 <= H, W <= 1024.
+ * Only the half spectrum (columns v < Wh = W/2 + 1) is transformed.  The caller owns every table (nothing is allocated here):
+ *   tabH     faoctasr_dft_tables of H
+ *   halfW    [C_W[:, :Wh] | S_W[:, :Wh]] (W rows of 2 Wh) followed by [C_W[:, :Wh]^T ; S_W[:, :Wh]^T] (2 Wh rows of W)
+ *   csr_off  K + 1 offsets into csr_idx;  csr_idx  the H*Wh flat half-plane positions sorted by (bin, position)
+ *   cnt      K counts of FULL-plane positions per bin;  binmap  int16 H x Wh, the bin of every half-plane position
+ * Wh == W with tables of the full plane is accepted too (every column then counts once): a measuring switch.
+ * Always exact fp32; no atomics, every sum in a fixed order: bit-reproducible, and L(x, y) == L(y, x) bit for bit.
+ * workspace of one forward or one backward for `sides` (1: the profile, 2: the loss) images; -1 on a bad shape */
+long faoctasr_sprof_workspace_floats(int sides, int N, int C, int H, int W, int Wh, int K);
+/* the profile A[N*C][K] of x[N,C,H,W].  save (may be NULL: no backward will follow): N*C*2*H*Wh floats, Re and -Im per plane. */
+int faoctasr_sprof_profile_fwd(const float* x, const float* tabH, const float* halfW, const int* csr_off, const int* csr_idx,
+                               const int* cnt, float* A, float* save, float* workspace, int N, int C, int H, int W, int Wh, int K,
+                               faoctasr_stream_t stream);
+/* the loss of x, y[N,C,H,W]: loss[1], loss_per_image[N] (per_image, which excludes batch_profile; else may be NULL), and both
+ * profiles A[2][N*C][K].  eps finite and > 0, 0 <= k_min < K.  save_x, save_y (each may be NULL: that side gets no gradient):
+ * N*C*(2*H*Wh + K) floats, the planes and then dL/dA / cnt_k, which a single-block finish writes with the loss. */
+int faoctasr_sprof_loss_fwd(const float* x, const float* y, const float* tabH, const float* halfW, const int* csr_off,
+                            const int* csr_idx, const int* cnt, double eps, int k_min, int batch_profile, int per_image, float* loss,
+                            float* loss_per_image, float* A, float* save_x, float* save_y, float* workspace, int N, int C, int H, int W,
+                            int Wh, int K, faoctasr_stream_t stream);
+/* backward of either: dx, dy[N,C,H,W] (either may be NULL; a side needs its save buffer).  The loss: g a device scalar, or with
+ * g_per_image N of them, and gA NULL.  The profile: gA[N*C][K] the cotangent of A, g, save_y and dy NULL. */
+int faoctasr_sprof_bwd(const float* g, int g_per_image, const float* gA, const float* save_x, const float* save_y, const float* tabH,
+                       const float* halfW, const short* binmap, const int* cnt, float* dx, float* dy, float* workspace, int N, int C,
+                       int H, int W, int Wh, int K, faoctasr_stream_t stream);
+
 /* ---- differentiable mutual information (Gaussian Parzen windows; not part of the reference) ----
  * Per (n, c) plane of n_pix = H*W pixels, with K = bins, d = (hi - lo) / K, centres c_k = lo + (k + 1/2) d, sigma = sigma_ratio d:
  * Wa[p,k] = softmax_k(-(x_p - c_k)^2 / (2 sigma^2)) (evaluated stably: any finite x, in the range or not), Wb likewise from y,
