@@ -68,6 +68,9 @@ _SIG = {
     "sprof_profile_fwd": (_I, "ppp ppp ppp iiii ii p"),
     "sprof_loss_fwd": (_I, "pppp ppp d iii ppp ppp iiii ii p"),
     "sprof_bwd": (_I, "p i p pp pp pp pp p iiii ii p"),
+    "frc_workspace_floats": (_L, "iiii ii"),
+    "frc_fwd": (_I, "pppp ppp d iii pppp pp iiii ii p"),
+    "frc_bwd": (_I, "p i p pp p pp p iiii ii p"),
     "mi_workspace_floats": (_L, "iiii i"),
     "mi_fwd": (_I, "pp ppp iiii i ffff ii p"),
     "mi_bwd": (_I, "ppp p pp iiii i fff i p"),

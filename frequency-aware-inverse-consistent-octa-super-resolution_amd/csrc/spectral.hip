@@ -24,6 +24,7 @@
 //
 // The focal frequency loss (second half of this file) runs on the same tables, row pass and tile, with two accumulators.
 // The spectral-profile loss (third section) runs them on the half spectrum: columns 0..W/2 only, both GEMM passes half as wide.
+// The Fourier ring correlation (fourth section) is that path with both transforms kept complex and three ring sums in place of one.
 #include <cstdint>
 #include "common.h"
 
@@ -916,6 +917,247 @@ static int sprof_profiles(const char* what, const float* x, const float* y, cons
     return check_launch(what);
 }
 
+// ---- Fourier ring correlation (Saxton & Baumeister 1982; van Heel & Schatz 2005) --------------------------------------------------
+//   F = fft2(x), G = fft2(y);  per plane and ring k of the spectral profile's geometry, the ring MEANS
+//   Nk = mean Re(F conj G) / (HW),  Xk = mean |F|^2 / (HW),  Yk = mean |G|^2 / (HW)      (Xk, Yk: the spectral profiles, bit for bit)
+//   r_k = Nk / sqrt(Xk Yk + eps)  in double;  index = mean of r_k over c and k_min <= k <= k_max;  curve = r_k at every ring
+// The spectral profile's path with both transforms kept complex and three ring sums in place of one:
+//   [P | Q] = X [C_W[:, :Wh] | S_W[:, :Wh]]        row pass, x and y in one launch
+//   Re, J of both images on H x Wh;  three weighted half planes m_v (Rx Ry + Jx Jy)/HW, m_v |F|^2/HW, m_v |G|^2/HW from the accumulators
+//   one sprof_bin_kernel launch over the 3 N*C planes;  finish (one block, double, fixed order): curve, index, coefficient tables
+//   backward: (dRe_x, dJ_x) = g m_v/(HW) (cN[bin] (Re_y, J_y) + 2 cX[bin] (Re_x, J_x)), the mirror image for y, formed while staging;
+//   [T1 | T2] as above;  dX = [T1 | T2] [C_W[:, :Wh]^T ; S_W[:, :Wh]^T]
+// A ring with Xk Yk = 0 has Nk = 0 (Cauchy-Schwarz, term by term): r_k = 0 and every coefficient is finite (D = sqrt(eps)).
+// x and y run one instruction sequence each: frc(x, y) == frc(y, x) bit for bit, with swapped gradients.
+struct FrcWs {
+    float* pq;          // [2 (x,y)][N*C][H][2Wh]: [P | Q] in the forward, [T1 | T2] in the backward
+    float* pw;          // [3 (N,X,Y)][N*C][H][Wh]: the weighted half planes
+    long total;
+};
+
+static FrcWs frc_ws(float* ws, long imgs, long H, long Wh) {
+    FrcWs p;
+    long off = 0;
+    p.pq = ws + off;
+    off += 2 * imgs * H * 2 * Wh;
+    p.pw = ws + off;
+    off += 3 * imgs * H * Wh;
+    p.total = off;
+    return p;
+}
+
+// column pass of sprof_col_fwd_kernel<2>; the epilogue writes the cross plane and both power planes, and with `save` Re, J of BOTH
+// images ([2 (x,y)][N*C][2 (Re,J)][H][Wh]): the gradient of either image reads the other's spectrum
+__global__ __launch_bounds__(256) void frc_col_fwd_kernel(const float* __restrict__ pq, const float* __restrict__ tabH,
+                                                          float* __restrict__ pw, float* __restrict__ save, int H, int W, int Wh, long imgs) {
+#pragma clang fp contract(off)
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[4][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int u0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const float* pqx = pq + img * H * 2 * Wh;
+    const float* pqy = pq + (imgs + img) * H * 2 * Wh;
+    f32x16 rx, jx, ry, jy;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rx[r] = jx[r] = ry[r] = jy[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, u0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int k = k0 + (e >> 6), v = v0 + (e & 63);
+            const bool ok = k < H && v < Wh;
+            const long o = (long)k * 2 * Wh + v;
+            Bs[0][e] = ok ? pqx[o] : 0.f;
+            Bs[1][e] = ok ? pqx[o + Wh] : 0.f;
+            Bs[2][e] = ok ? pqy[o] : 0.f;
+            Bs[3][e] = ok ? pqy[o + Wh] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float px = Bs[0][bo], qx = Bs[1][bo];
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, px, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(as, px, jx, 0, 0, 0);
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qx, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qx, jx, 0, 0, 0);
+            const float py = Bs[2][bo], qy = Bs[3][bo];
+            ry = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, py, ry, 0, 0, 0);
+            jy = __builtin_amdgcn_mfma_f32_32x32x2f32(as, py, jy, 0, 0, 0);
+            ry = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qy, ry, 0, 0, 0);
+            jy = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qy, jy, 0, 0, 0);
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < Wh) {
+        const long hwh = (long)H * Wh;
+        const float mv = sprof_mv(v, W, Wh), hw = (float)(H * W);
+        float* pwn = pw + img * hwh;
+        float* pwx = pw + (imgs + img) * hwh;
+        float* pwy = pw + (2 * imgs + img) * hwh;
+        float* sx = save ? save + img * 2 * hwh : nullptr;
+        float* sy = save ? save + (imgs + img) * 2 * hwh : nullptr;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int u = u0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (u < H) {
+                const long o = (long)u * Wh + v;
+                pwn[o] = mv * ((rx[rr] * ry[rr] + jx[rr] * jy[rr]) / hw);
+                pwx[o] = mv * ((rx[rr] * rx[rr] + jx[rr] * jx[rr]) / hw);
+                pwy[o] = mv * ((ry[rr] * ry[rr] + jy[rr] * jy[rr]) / hw);
+                if (save) {
+                    sx[o] = rx[rr];
+                    sx[hwh + o] = jx[rr];
+                    sy[o] = ry[rr];
+                    sy[hwh + o] = jy[rr];
+                }
+            }
+        }
+    }
+}
+
+// single block, double, fixed order.  A: [3 (N,X,Y)][imgs][K] ring means.  Per sample n the sum of r over c and k_min <= k <= k_max
+// by the block tree, the samples added in index order.  coef ([3 (cN,cX,cY)][imgs][K], may be nullptr): d index / d (Nk, Xk, Yk)
+// over cnt_k with the mean's divisor folded in (per_image: that sample's own mean), zero outside the band
+__global__ __launch_bounds__(256) void frc_finish_kernel(const float* __restrict__ A, const int* __restrict__ cnt, float* __restrict__ index,
+                                                         float* __restrict__ per, float* __restrict__ curve, float* __restrict__ coef, int N,
+                                                         int C, int K, int k_min, int k_max, double eps, int per_image) {
+#pragma clang fp contract(off)
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    const long imgs = (long)N * C;
+    const float* An = A;
+    const float* Ax = A + imgs * K;
+    const float* Ay = A + 2 * imgs * K;
+    const double rings = (double)(k_max - k_min + 1);
+    const double w = 1.0 / ((per_image ? 1.0 : (double)N) * (double)C * rings);
+    double total = 0.0;
+    for (int n = 0; n < N; ++n) {
+        double acc = 0.0;
+        for (long e = tid; e < (long)C * K; e += 256) {
+            const int k = (int)(e % K);
+            const long o = ((long)n * C + e / K) * K + k;
+            const double nk = (double)An[o], xk = (double)Ax[o], yk = (double)Ay[o];
+            const double D = sqrt(xk * yk + eps);
+            const double r = nk / D;
+            const bool in = k >= k_min && k <= k_max;
+            curve[o] = (float)r;
+            if (in) acc += r;
+            if (coef) {
+                const double c = (double)cnt[k], d3 = 2.0 * (D * D * D);
+                coef[o] = in ? (float)(w / D / c) : 0.f;
+                coef[imgs * K + o] = in ? (float)(-(w * nk * yk) / d3 / c) : 0.f;
+                coef[2 * imgs * K + o] = in ? (float)(-(w * nk * xk) / d3 / c) : 0.f;
+            }
+        }
+        acc = block_tree_256(acc, red);
+        total += acc;
+        if (tid == 0 && per) per[n] = (float)(acc / ((double)C * rings));
+    }
+    if (tid == 0) *index = (float)(total / ((double)N * (double)C * rings));
+}
+
+// sprof_col_bwd_kernel's transform; the operand of a side is formed from BOTH saved images while they are staged:
+// (dRe_x, dJ_x) = g m_v/(HW) (cN[bin] (Re_y, J_y) + 2 cX[bin] (Re_x, J_x)), and with x and y exchanged for y.  g: one device scalar, or
+// one per sample (g_stride 1).  A side that is not wanted costs neither operand, MFMA chain nor stores
+__global__ __launch_bounds__(256) void frc_col_bwd_kernel(const float* __restrict__ save, const float* __restrict__ coef,
+                                                          const short* __restrict__ binmap, const float* __restrict__ tabH,
+                                                          const float* __restrict__ g, int g_stride, float* __restrict__ T, int H, int W, int Wh,
+                                                          int C, int K, long imgs, float c1, int want_x, int want_y) {
+#pragma clang fp contract(off)
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[4][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int h0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const long hwh = (long)H * Wh;
+    const float* plx = save + img * 2 * hwh;
+    const float* ply = save + (imgs + img) * 2 * hwh;
+    const float* cn = coef + img * K;
+    const float* cx = coef + (imgs + img) * K;
+    const float* cy = coef + (2 * imgs + img) * K;
+    const int sv = v0 + (tid & 63);
+    const float gs = g[(img / C) * g_stride] * c1 * sprof_mv(sv, W, Wh);
+    f32x16 t1x, t2x, t1y, t2y;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t1x[r] = t2x[r] = t1y[r] = t2y[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, h0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int u = k0 + (e >> 6);
+            float drx = 0.f, djx = 0.f, dry = 0.f, djy = 0.f;
+            if (u < H && sv < Wh) {
+                const long o = (long)u * Wh + sv;
+                int b = binmap[o];
+                b = b < 0 ? 0 : (b < K ? b : K - 1);
+                const float rex = plx[o], imx = plx[hwh + o], rey = ply[o], imy = ply[hwh + o];
+                const float kn = cn[b];
+                if (want_x) {
+                    const float ks = 2.f * cx[b];
+                    drx = gs * (kn * rey + ks * rex);
+                    djx = gs * (kn * imy + ks * imx);
+                }
+                if (want_y) {
+                    const float ks = 2.f * cy[b];
+                    dry = gs * (kn * rex + ks * rey);
+                    djy = gs * (kn * imx + ks * imy);
+                }
+            }
+            Bs[0][e] = drx;
+            Bs[1][e] = djx;
+            Bs[2][e] = dry;
+            Bs[3][e] = djy;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            if (want_x) {
+                const float dr = Bs[0][bo], dj = Bs[1][bo];
+                t1x = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1x, 0, 0, 0);
+                t2x = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2x, 0, 0, 0);
+                t1x = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1x, 0, 0, 0);
+                t2x = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2x, 0, 0, 0);
+            }
+            if (want_y) {
+                const float dr = Bs[2][bo], dj = Bs[3][bo];
+                t1y = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dr, t1y, 0, 0, 0);
+                t2y = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, dj, t2y, 0, 0, 0);
+                t1y = __builtin_amdgcn_mfma_f32_32x32x2f32(as, dj, t1y, 0, 0, 0);
+                t2y = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, dr, t2y, 0, 0, 0);
+            }
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < Wh) {
+        float* Tx = T + img * H * 2 * Wh;
+        float* Ty = T + (imgs + img) * H * 2 * Wh;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int h = h0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (h < H) {
+                const long o = (long)h * 2 * Wh + v;
+                if (want_x) {
+                    Tx[o] = t1x[rr];
+                    Tx[o + Wh] = t2x[rr];
+                }
+                if (want_y) {
+                    Ty[o] = t1y[rr];
+                    Ty[o + Wh] = t2y[rr];
+                }
+            }
+        }
+    }
+}
+
 }  // namespace faoctasr
 
 using namespace faoctasr;
@@ -1127,6 +1369,72 @@ extern "C" int faoctasr_sprof_bwd(const float* g, int g_per_image, const float* 
     if (dx && dy) {
         const intptr_t diff = (intptr_t)dy - (intptr_t)dx;
         if (diff % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "sprof_bwd: dx and dy are not 4-byte aligned to each other");
+        return faoctasr_sgemm_batched(p.pq, stacked, dx, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, sT, 0, (long)(diff / (intptr_t)sizeof(float)), 2,
+                                      stream);
+    }
+    return faoctasr_sgemm_batched(dx ? p.pq : p.pq + sT, stacked, dx ? dx : dy, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, 0, 0, 0, 1, stream);
+}
+
+extern "C" long faoctasr_frc_workspace_floats(int N, int C, int H, int W, int Wh, int K) {
+    if (sprof_check("frc_workspace_floats", 2, N, C, H, W, Wh, K)) return -1;
+    return frc_ws(nullptr, (long)N * C, H, Wh).total;
+}
+
+extern "C" int faoctasr_frc_fwd(const float* x, const float* y, const float* tabH, const float* halfW, const int* csr_off, const int* csr_idx,
+                                const int* cnt, double eps, int k_min, int k_max, int per_image, float* index, float* index_per_image,
+                                float* curve, float* rings, float* save, float* workspace, int N, int C, int H, int W, int Wh, int K,
+                                faoctasr_stream_t stream) {
+    if (!x || !y || !tabH || !halfW || !csr_off || !csr_idx || !cnt || !index || !curve || !rings || !workspace)
+        return fail(FAOCTASR_EINVAL, "frc_fwd: null pointer");
+    int rc = sprof_check("frc_fwd", 2, N, C, H, W, Wh, K);
+    if (rc) return rc;
+    if (!(eps > 0.0) || eps > 1.0e300) return fail(FAOCTASR_EINVAL, "frc_fwd: eps %g must be finite and > 0", eps);
+    if (k_min < 0 || k_max < k_min || k_max > K - 1)
+        return fail(FAOCTASR_EINVAL, "frc_fwd: the band k_min %d, k_max %d must satisfy 0 <= k_min <= k_max <= %d", k_min, k_max, K - 1);
+    if (per_image && !index_per_image) return fail(FAOCTASR_EINVAL, "frc_fwd: per_image needs index_per_image");
+    const long imgs = (long)N * C;
+    const hipStream_t st = (hipStream_t)stream;
+    const FrcWs p = frc_ws(workspace, imgs, H, Wh);
+    const intptr_t d = (intptr_t)y - (intptr_t)x;
+    if (d % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "frc_fwd: x and y are not 4-byte aligned to each other");
+    rc = faoctasr_sgemm_batched(x, halfW, p.pq, (int)(imgs * H), 2 * Wh, W, W, 2 * Wh, 2 * Wh, (long)(d / (intptr_t)sizeof(float)), 0,
+                                imgs * H * 2 * Wh, 2, stream);
+    if (rc) return rc;
+    dim3 grid((Wh + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(frc_col_fwd_kernel, grid, dim3(256), 0, st, (const float*)p.pq, tabH, p.pw, save, H, W, Wh, imgs);
+    rc = check_launch("frc_fwd (column pass)");
+    if (rc) return rc;
+    const long waves = 3 * imgs * K;
+    hipLaunchKernelGGL(sprof_bin_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, (const float*)p.pw, csr_off, csr_idx, cnt, rings,
+                       3 * imgs, K, (long)H * Wh);
+    rc = check_launch("frc_fwd (ring sums)");
+    if (rc) return rc;
+    // the coefficient tables follow the saved planes
+    hipLaunchKernelGGL(frc_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)rings, cnt, index, index_per_image, curve,
+                       save ? save + imgs * 4 * H * Wh : nullptr, N, C, K, k_min, k_max, eps, per_image ? 1 : 0);
+    return check_launch("frc_fwd (finish)");
+}
+
+extern "C" int faoctasr_frc_bwd(const float* g, int g_per_image, const float* save, const float* tabH, const float* halfW, const short* binmap,
+                                float* dx, float* dy, float* workspace, int N, int C, int H, int W, int Wh, int K, faoctasr_stream_t stream) {
+    if (!g || !tabH || !halfW || !binmap || !workspace) return fail(FAOCTASR_EINVAL, "frc_bwd: null pointer");
+    int rc = sprof_check("frc_bwd", 2, N, C, H, W, Wh, K);
+    if (rc) return rc;
+    if ((dx || dy) && !save) return fail(FAOCTASR_EINVAL, "frc_bwd: a gradient is wanted but the forward saved nothing");
+    if (!dx && !dy) return FAOCTASR_OK;
+    const long imgs = (long)N * C;
+    const FrcWs p = frc_ws(workspace, imgs, H, Wh);
+    dim3 grid((Wh + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(frc_col_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, save, save + imgs * 4 * H * Wh, binmap, tabH, g,
+                       g_per_image ? 1 : 0, p.pq, H, W, Wh, C, K, imgs, (float)(1.0 / ((double)H * (double)W)), dx ? 1 : 0, dy ? 1 : 0);
+    rc = check_launch("frc_bwd (column pass)");
+    if (rc) return rc;
+    // dX = [T1 | T2] [C_W[:, :Wh]^T ; S_W[:, :Wh]^T]: the transposed half table follows the forward one
+    const float* stacked = halfW + 2L * W * Wh;
+    const long sT = imgs * H * 2 * Wh;
+    if (dx && dy) {
+        const intptr_t diff = (intptr_t)dy - (intptr_t)dx;
+        if (diff % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "frc_bwd: dx and dy are not 4-byte aligned to each other");
         return faoctasr_sgemm_batched(p.pq, stacked, dx, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, sT, 0, (long)(diff / (intptr_t)sizeof(float)), 2,
                                       stream);
     }

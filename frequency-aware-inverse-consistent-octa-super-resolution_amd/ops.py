@@ -2612,6 +2612,177 @@ def spectral_profile(x, _full_spectrum=False):
 
 
 # ----------------------------------------------------------------------------------------
+# Fourier ring correlation (Saxton & Baumeister 1982; van Heel & Schatz 2005) on the spectral profile's half-spectrum path
+# ----------------------------------------------------------------------------------------
+FRC_MAX_SMOOTH = 15
+
+
+def check_frc_params(k_min=1, k_max=None, eps=1e-16):
+    """``(k_min, k_max, eps)`` of the Fourier ring correlation: k_min an int >= 0, k_max None or an int >= k_min, eps finite and > 0,
+    or ValueError (``k_max <= K - 1`` is checked against the shape, ``frc_band``)."""
+    if isinstance(k_min, bool) or not isinstance(k_min, int) or k_min < 0:
+        raise ValueError("frc: k_min must be an int >= 0, got %r" % (k_min,))
+    if k_max is not None and (isinstance(k_max, bool) or not isinstance(k_max, int) or k_max < k_min):
+        raise ValueError("frc: k_max must be None or an int >= k_min = %d, got %r" % (k_min, k_max))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps > 0):
+        raise ValueError("frc: eps must be a finite number > 0, got %r" % (eps,))
+    return k_min, k_max, float(eps)
+
+
+def frc_band(H, W, k_min=1, k_max=None):
+    """``(k_min, k_max, K)`` for an H x W spectrum: ``k_max = None`` is the Nyquist ring ``min(H, W) // 2`` (the rings beyond it are
+    the incomplete corner rings); ``0 <= k_min <= k_max <= K - 1`` or ValueError."""
+    K = radial_bins(H, W)[1].numel()
+    if k_max is None:
+        k_max = min(H, W) // 2
+    if not 0 <= k_min <= k_max <= K - 1:
+        raise ValueError("frc: the band needs 0 <= k_min <= k_max <= %d (a %d x %d spectrum has %d rings), got k_min %r, k_max %r"
+                         % (K - 1, H, W, K, k_min, k_max))
+    return k_min, k_max, K
+
+
+def _check_frc_operands(what, x, y):
+    _check_sprof_operands(what, x, y)
+    if x.shape != y.shape:
+        raise _lib.KernelError("%s operands must have one shape: %s vs %s" % (what, tuple(x.shape), tuple(y.shape)))
+    if x.device != y.device:
+        raise _lib.KernelError("%s runs as HIP kernels on one GPU; got devices %s and %s" % (what, x.device, y.device))
+
+
+def _frc_ws(N, C, H, W, Wh, K, device):
+    n = _lib.load().faoctasr_frc_workspace_floats(N, C, H, W, Wh, K)
+    if n < 0:
+        raise _lib.KernelError("faoctasr_frc_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+    return torch.empty(max(n, 1), dtype=torch.float32, device=device)         # scratch of this call: free again behind it on the stream
+
+
+def frc_forward(x, y, k_min=1, k_max=None, eps=1e-16, per_image=False, save=False):
+    """The forward launches of the Fourier ring correlation without autograd: ``(index 0-dim, per_image (N,) or None, curve
+    (N, C, K), rings (3, N, C, K): the ring means Nk, Xk, Yk, saved)``; ``saved`` (both spectra and the coefficient tables) only where
+    ``save`` asks.  ``rings[1]`` / ``rings[2]`` are ``spectral_profile(x)`` / ``(y)`` bit for bit."""
+    x, y = _c(x), _c(y)
+    N, C, H, W = x.shape
+    k_min, k_max, _ = frc_band(H, W, k_min, k_max)
+    tab_h, half_w, K, Wh, off, idx, cnt, _ = sprof_tables(H, W, x.device)
+    dev = x.device
+    ws = _frc_ws(N, C, H, W, Wh, K, dev)
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    per = torch.empty(N, dtype=torch.float32, device=dev) if per_image else None
+    curve = torch.empty((N, C, K), dtype=torch.float32, device=dev)
+    rings = torch.empty((3, N, C, K), dtype=torch.float32, device=dev)
+    saved = torch.empty(N * C * (4 * H * Wh + 3 * K), dtype=torch.float32, device=dev) if save else None
+    call("frc_fwd", ptr(x), ptr(y), ptr(tab_h), ptr(half_w), off.data_ptr(), idx.data_ptr(), cnt.data_ptr(), eps, k_min, k_max,
+         int(per_image), ptr(out), ptr(per), ptr(curve), ptr(rings), ptr(saved), ptr(ws), N, C, H, W, Wh, K, stream_ptr())
+    return out, per, curve, rings, saved
+
+
+class _FRC(Function):
+    @staticmethod
+    def forward(ctx, x, y, k_min, k_max, eps, per_image, save):
+        out, per, _, _, saved = frc_forward(x, y, k_min, k_max, eps, per_image, save)
+        ctx.save_for_backward(saved)
+        ctx.cfg = (per_image,) + tuple(x.shape)
+        ctx.dev = x.device
+        return per if per_image else out
+
+    @staticmethod
+    def backward(ctx, g):
+        saved, = ctx.saved_tensors
+        per_image, N, C, H, W = ctx.cfg
+        tab_h, half_w, K, Wh, _, _, _, binmap = sprof_tables(H, W, ctx.dev)
+        g = _c(g)
+        dx = torch.empty((N, C, H, W), dtype=torch.float32, device=ctx.dev) if ctx.needs_input_grad[0] else None
+        dy = torch.empty((N, C, H, W), dtype=torch.float32, device=ctx.dev) if ctx.needs_input_grad[1] else None
+        ws = _frc_ws(N, C, H, W, Wh, K, ctx.dev)
+        call("frc_bwd", ptr(g), int(per_image), ptr(saved), ptr(tab_h), ptr(half_w), binmap.data_ptr(), ptr(dx), ptr(dy), ptr(ws), N, C, H, W,
+             Wh, K, stream_ptr())
+        return (dx, dy) + (None,) * 5
+
+
+def frc(a, b, k_min=1, k_max=None, eps=1e-16, per_image=False):
+    """The Fourier ring correlation index of a, b (N,C,H,W) fp32 on one GPU, 2 <= H, W <= 1024, with gradients to both images: with
+    ``F = fft2(a)``, ``G = fft2(b)`` and the rings of ``radial_bins(H, W)``, ``r_k = Nk / sqrt(Xk Yk + eps)`` from the ring means ``Nk``
+    of ``Re(F conj G) / (HW)``, ``Xk`` of ``|F|^2 / (HW)`` and ``Yk`` of ``|G|^2 / (HW)`` (in double); the index of an image is the mean
+    of ``r_k`` over c and ``k_min <= k <= k_max``.  0-dim, the batch mean, or (N,) with ``per_image``; the loss is ``1 - frc``.
+    ``k_min = 1`` drops DC; ``k_max = None`` is the Nyquist ring ``min(H, W) // 2``.  In [-1, 1], 1 for identical images, and unchanged
+    by a gain on either image.  A ring with ``Xk Yk = 0`` contributes ``r_k = 0`` with finite gradients.  The spectra of both images
+    are kept when either needs a gradient, nothing otherwise; no double backward.  Bit-reproducible, ``frc(a, b) == frc(b, a)`` bit
+    for bit, always exact fp32 (csrc/spectral.hip)."""
+    k_min, k_max, eps = check_frc_params(k_min, k_max, eps)
+    _check_frc_operands("frc", a, b)
+    k_min, k_max, _ = frc_band(a.shape[2], a.shape[3], k_min, k_max)
+    save = torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)          # grad mode is off inside Function.forward
+    return _FRC.apply(a, b, k_min, k_max, eps, bool(per_image), save)
+
+
+def frc_curve(a, b, eps=1e-16):
+    """The Fourier ring correlation curve of a, b (N,C,H,W) fp32 on one GPU: ``r_k`` of ``frc`` at every ring of
+    ``radial_bins(H, W)``, (N, C, K) fp32.  An evaluation output: it carries no gradient."""
+    _, _, eps = check_frc_params(eps=eps)
+    _check_frc_operands("frc_curve", a, b)
+    with torch.no_grad():
+        return frc_forward(a.detach(), b.detach(), 0, 0, eps)[2]
+
+
+def frc_half_bit(H, W):
+    """The half-bit threshold curve of van Heel & Schatz (2005) for the rings of ``radial_bins(H, W)``, float64 (K,):
+    ``T_k = (0.2071 + 1.9102 / sqrt(cnt_k)) / (1.2071 + 0.9102 / sqrt(cnt_k))``."""
+    s = radial_bins(H, W)[1].double().sqrt()
+    return (0.2071 + 1.9102 / s) / (1.2071 + 0.9102 / s)
+
+
+def check_frc_readout(threshold=1 / 7, smooth=1):
+    """``(threshold, smooth)`` of ``frc_cutoff``: a float in (0, 1) or ``"half-bit"``, an odd int in 1..15, or ValueError."""
+    if isinstance(threshold, str):
+        if threshold != "half-bit":
+            raise ValueError("frc_cutoff: threshold must be a float in (0, 1) or \"half-bit\", got %r" % (threshold,))
+    elif isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not 0 < threshold < 1:
+        raise ValueError("frc_cutoff: threshold must be a float in (0, 1) or \"half-bit\", got %r" % (threshold,))
+    else:
+        threshold = float(threshold)
+    if isinstance(smooth, bool) or not isinstance(smooth, int) or not (1 <= smooth <= FRC_MAX_SMOOTH and smooth % 2 == 1):
+        raise ValueError("frc_cutoff: smooth must be an odd int in 1..%d, got %r" % (FRC_MAX_SMOOTH, smooth))
+    return threshold, smooth
+
+
+def frc_cutoff(curve, H, W, threshold=1 / 7, smooth=1, k_min=1, k_max=None):
+    """The fractional ring ``k*`` at which a Fourier ring correlation curve (N, C, K) of H x W images falls through a threshold,
+    float64 (N, C) on the curve's device.  ``threshold``: a float in (0, 1) (1/7, Nieuwenhuizen et al. 2013), or ``"half-bit"``
+    (``frc_half_bit``).  ``smooth``: an odd window 1..15, a moving average over the rings before the read-out whose window shrinks
+    symmetrically at the two ends of ``[0, K - 1]``.  With ``d_k = r_k - T_k``, ``k*`` belongs to the first k in ``[k_min, k_max]``
+    with ``d_k < 0``: ``k_min`` if that is ``k_min``, else ``(k - 1) + d_{k-1} / (d_{k-1} - d_k)``; without a crossing ``k_max``.
+    The cutoff frequency is ``k* / min(H, W)`` cycles per pixel and the resolution ``min(H, W) / k*`` pixels.  Plain torch ops in
+    float64: a read-out, not a hot path."""
+    k_min, k_max, _ = check_frc_params(k_min, k_max)
+    threshold, smooth = check_frc_readout(threshold, smooth)
+    k_min, k_max, K = frc_band(H, W, k_min, k_max)
+    if not torch.is_tensor(curve) or curve.dim() != 3 or curve.shape[-1] != K or not curve.is_floating_point():
+        raise ValueError("frc_cutoff: the curve must be a floating (N, C, %d) tensor for %d x %d, got %s"
+                         % (K, H, W, tuple(getattr(curve, "shape", ()))))
+    if threshold == "half-bit":
+        T = frc_half_bit(H, W).to(curve.device)
+    else:
+        T = torch.full((K,), threshold, dtype=torch.float64, device=curve.device)
+    r = curve.detach().double()
+    if smooth > 1:
+        k = torch.arange(K, device=r.device)
+        half = torch.minimum(torch.minimum(k, K - 1 - k), torch.full_like(k, smooth // 2))
+        acc = torch.zeros_like(r)
+        for j in range(-(smooth // 2), smooth // 2 + 1):         # neighbours in ascending order, those outside the window as 0
+            acc = acc + torch.where(half >= abs(j), r[..., (k + j).clamp(0, K - 1)], torch.zeros_like(r))
+        r = acc / (2 * half + 1).double()
+    d = r - T
+    below = d[..., k_min:k_max + 1] < 0
+    first = (below.long().cumsum(-1) == 0).sum(-1)               # rings of the band before the first one below the threshold
+    k = first.clamp(max=k_max - k_min) + k_min
+    prev = (k - 1).clamp(min=0)
+    d0, d1 = d.gather(-1, prev[..., None])[..., 0], d.gather(-1, k[..., None])[..., 0]
+    cross = prev.double() + d0 / (d0 - d1)
+    out = torch.where(k == k_min, torch.full_like(cross, float(k_min)), cross)
+    return torch.where(first > k_max - k_min, torch.full_like(cross, float(k_max)), out)
+
+
+# ----------------------------------------------------------------------------------------
 # differentiable mutual information (Gaussian Parzen windows, soft joint histogram; csrc/mi.hip)
 # ----------------------------------------------------------------------------------------
 MI_MAX_BINS = 64

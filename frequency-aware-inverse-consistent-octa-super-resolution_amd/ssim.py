@@ -342,3 +342,70 @@ class SoftClDice(torch.nn.Module):
     def extra_repr(self):
         return "iters={}, smooth={}, value_range={}, bright={}, size_average={}".format(self.iters, self.smooth, self.value_range, self.bright,
                                                                                     self.size_average)
+
+
+def frc(img1, img2, k_min=1, k_max=None, eps=1e-16, size_average=True):
+    """The Fourier ring correlation index with ``ssim``'s interface: the mean over the batch, or ``(N,)`` with ``size_average=False``
+    (``ops.frc``).  An index: the loss is ``1 - frc(...)``."""
+    return ops.frc(img1, img2, k_min, k_max, eps, not size_average)
+
+
+class FRC(torch.nn.Module):
+    """forward(img1, img2) -> the Fourier ring correlation index (Saxton & Baumeister 1982; van Heel & Schatz 2005) with ``SSIM``'s
+    interface: the correlation of the two spectra ring by ring, ``r_k = Nk / sqrt(Xk Yk + eps)`` from the ring means of
+    ``Re(F conj G)``, ``|F|^2`` and ``|G|^2`` over the rings of ``radial_bins(H, W)``, averaged over the channels and the rings
+    ``k_min..k_max`` of an image (``k_min = 1`` drops DC; ``k_max = None`` is the Nyquist ring ``min(H, W) // 2``).  It keeps phase
+    and does not change under a gain on either image.  1 for identical images; the mean over the batch, or ``(N,)`` with
+    ``size_average=False``; the loss is ``1 - FRC()(x, y)``, with gradients to both images.  A ring where either image has no power
+    contributes 0.  fp32, sides 2..1024, no double backward (csrc/spectral.hip)."""
+
+    def __init__(self, k_min=1, k_max=None, eps=1e-16, size_average=True):
+        super().__init__()
+        self.k_min, self.k_max, self.eps = ops.check_frc_params(k_min, k_max, eps)
+        self.size_average = size_average
+
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average``."""
+        return ops.frc(img1, img2, self.k_min, self.k_max, self.eps, per_image)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, not self.size_average)
+
+    def extra_repr(self):
+        return "k_min={}, k_max={}, eps={}, size_average={}".format(self.k_min, self.k_max, self.eps, self.size_average)
+
+
+class FRCResolution(torch.nn.Module):
+    """The resolution read off the Fourier ring correlation curve: the fractional ring ``k*`` at which the curve of ``(img1, img2)``
+    falls through ``threshold`` (a float in (0, 1), 1/7 after Nieuwenhuizen et al. 2013, or ``"half-bit"`` after van Heel & Schatz
+    2005), after a moving average over ``smooth`` rings, searched in ``k_min..k_max`` (``ops.frc_cutoff``).
+    ``index(img1, img2, per_image)`` is the cutoff frequency ``k* / min(H, W)`` in cycles per pixel, averaged over the channels:
+    higher is better, so its batch mean in ``evaluate_pairs_with`` is meaningful; ``(N,)`` float64 with ``per_image``, else the
+    batch mean.  ``curve(img1, img2)`` is the curve (N, C, K) and ``resolution(img1, img2)`` the resolution ``min(H, W) / k*`` in
+    pixels, float64 (N, C) (inf where ``k* = 0``).  ``forward`` is ``index`` with the batch mean.  An evaluation read-out: no gradient."""
+
+    def __init__(self, threshold=1 / 7, smooth=1, k_min=1, k_max=None, eps=1e-16):
+        super().__init__()
+        self.k_min, self.k_max, self.eps = ops.check_frc_params(k_min, k_max, eps)
+        self.threshold, self.smooth = ops.check_frc_readout(threshold, smooth)
+
+    def curve(self, img1, img2):
+        return ops.frc_curve(img1, img2, self.eps)
+
+    def cutoff(self, img1, img2):
+        """``k*``, float64 (N, C)."""
+        H, W = img1.shape[-2:]
+        return ops.frc_cutoff(self.curve(img1, img2), H, W, self.threshold, self.smooth, self.k_min, self.k_max)
+
+    def index(self, img1, img2, per_image):
+        f = (self.cutoff(img1, img2) / min(img1.shape[-2:])).mean(1)
+        return f if per_image else f.mean()
+
+    def resolution(self, img1, img2):
+        return min(img1.shape[-2:]) / self.cutoff(img1, img2)
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, False)
+
+    def extra_repr(self):
+        return "threshold={}, smooth={}, k_min={}, k_max={}, eps={}".format(self.threshold, self.smooth, self.k_min, self.k_max, self.eps)

@@ -321,6 +321,25 @@ int faoctasr_sprof_bwd(const float* g, int g_per_image, const float* gA, const f
                        const float* halfW, const short* binmap, const int* cnt, float* dx, float* dy, float* workspace, int N, int C,
                        int H, int W, int Wh, int K, faoctasr_stream_t stream);
 
+/* ---- Fourier ring correlation (Saxton & Baumeister 1982, van Heel & Schatz 2005; not part of the reference) ----
+ * With F = fft2(x), G = fft2(y) per plane and the rings, tables and limits of the spectral profile above, the ring MEANS
+ *   Nk = mean Re(F conj G) / (HW),  Xk = mean |F|^2 / (HW),  Yk = mean |G|^2 / (HW),   r_k = Nk / sqrt(Xk Yk + eps) in double.
+ * The index of an image is the mean of r_k over c and k_min <= k <= k_max; the curve is r_k at every ring.  Xk and Yk are the
+ * spectral profiles of x and y bit for bit.  A ring with Xk Yk = 0 has r_k = 0 and finite gradients.  Always exact fp32; no
+ * atomics, every sum in a fixed order: bit-reproducible, and frc(x, y) == frc(y, x) bit for bit with swapped gradients.
+ * workspace of one forward or one backward; -1 on a bad shape */
+long faoctasr_frc_workspace_floats(int N, int C, int H, int W, int Wh, int K);
+/* index[1] (the batch mean), index_per_image[N] (needed with per_image, else may be NULL; always each sample's own mean),
+ * curve[N*C][K], rings[3][N*C][K] (Nk, Xk, Yk).  eps finite and > 0, 0 <= k_min <= k_max <= K - 1.  save (may be NULL: no backward
+ * will follow): N*C*(4*H*Wh + 3*K) floats, Re and -Im of x and of y and then the coefficient tables d index / d (Nk, Xk, Yk) / cnt_k
+ * (per_image: of each sample's own mean), which the single-block finish writes with the index. */
+int faoctasr_frc_fwd(const float* x, const float* y, const float* tabH, const float* halfW, const int* csr_off, const int* csr_idx,
+                     const int* cnt, double eps, int k_min, int k_max, int per_image, float* index, float* index_per_image, float* curve,
+                     float* rings, float* save, float* workspace, int N, int C, int H, int W, int Wh, int K, faoctasr_stream_t stream);
+/* dx, dy[N,C,H,W] (either may be NULL; one side still reads both saved spectra).  g a device scalar, or with g_per_image N of them. */
+int faoctasr_frc_bwd(const float* g, int g_per_image, const float* save, const float* tabH, const float* halfW, const short* binmap,
+                     float* dx, float* dy, float* workspace, int N, int C, int H, int W, int Wh, int K, faoctasr_stream_t stream);
+
 /* ---- differentiable mutual information (Gaussian Parzen windows; not part of the reference) ----
  * Per (n, c) plane of n_pix = H*W pixels, with K = bins, d = (hi - lo) / K, centres c_k = lo + (k + 1/2) d, sigma = sigma_ratio d:
  * Wa[p,k] = softmax_k(-(x_p - c_k)^2 / (2 sigma^2)) (evaluated stably: any finite x, in the range or not), Wb likewise from y,
