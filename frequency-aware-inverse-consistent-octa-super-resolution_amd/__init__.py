@@ -10,8 +10,8 @@ from .model import (Discriminator, FocalFrequencyLoss, FS_DiscriminatorA, FS_Dis
                     ResnetGenerator, SpectralProfileLoss, TVLoss, UnetGenerator, UnetSkipConnectionBlock, phase_consistency_loss, shallowNet)
 from .evaluate import evaluate_pairs, evaluate_pairs_with, image_metrics, super_resolve
 from . import ssim                # stays the MODULE: the reference does `import ssim; ssim.SSIM()` (train.py:24,97)
-from .ssim import SSIM, MSSSIM, ms_ssim, HaarPSI, LNCC, GMSD, MSGMSD, Vesselness, VesselDice, VIF, SoftSkeleton, SoftClDice, FRC, FRCResolution, frc
-from .ops import frc_curve, frc_cutoff
+from .ssim import SSIM, MSSSIM, ms_ssim, HaarPSI, LNCC, GMSD, MSGMSD, Vesselness, VesselDice, VIF, SoftSkeleton, SoftClDice, FRC, FRCResolution, frc, Registered, RegistrationShift
+from .ops import frc_curve, frc_cutoff, phase_correlation, phase_correlation_surface, fourier_shift
 from .ssim import ssim as ssim_fn  # the function ssim.py:65-73; not exported under the submodule's name
 from .data import GpuTransformA, GpuTransformB, crop_resize_normalize, random_crop_offsets
 from .train import GraphedTrainStep, ParamArena, TrainStep, live_parameters

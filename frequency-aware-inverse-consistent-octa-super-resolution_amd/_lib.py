@@ -71,6 +71,10 @@ _SIG = {
     "frc_workspace_floats": (_L, "iiii ii"),
     "frc_fwd": (_I, "pppp ppp d iii pppp pp iiii ii p"),
     "frc_bwd": (_I, "p i p pp p pp p iiii ii p"),
+    "pcorr_workspace_floats": (_L, "iiii ii i"),
+    "pcorr_fwd": (_I, "pppp p d iiiii ppp p iiii ii p"),
+    "fourier_shift_workspace_floats": (_L, "iiii"),
+    "fourier_shift": (_I, "pp f pp pp iiii p"),
     "mi_workspace_floats": (_L, "iiii i"),
     "mi_fwd": (_I, "pp ppp iiii i ffff ii p"),
     "mi_bwd": (_I, "ppp p pp iiii i fff i p"),

@@ -25,6 +25,7 @@
 // The focal frequency loss (second half of this file) runs on the same tables, row pass and tile, with two accumulators.
 // The spectral-profile loss (third section) runs them on the half spectrum: columns 0..W/2 only, both GEMM passes half as wide.
 // The Fourier ring correlation (fourth section) is that path with both transforms kept complex and three ring sums in place of one.
+// Phase correlation and the Fourier shift (fifth section) add the way back: the half-spectrum inverse as a forward pass.
 #include <cstdint>
 #include "common.h"
 
@@ -1158,6 +1159,401 @@ __global__ __launch_bounds__(256) void frc_col_bwd_kernel(const float* __restric
     }
 }
 
+// ---- phase-correlation registration and the Fourier shift (Kuglin & Hines 1975; Guizar-Sicairos, Thurman & Fienup 2008) ----------
+//   F = fft2(a), G = fft2(b);  R = G conj(F) / (HW),  Rn = R / sqrt(|R|^2 + eps) (or R), zero in every ring above k_max
+//   surface = sum_c Re ifft2(Rn): its peak lies at d when b(p) = a(p - d);  the coarse peak is the first maximum inside the window
+//   up[j,i] = (1/HW) sum_c sum_u sum_{v<Wh} m_v Re(Rn[c,u,v] exp(2 pi i (f_u (s_y + o_j) + f_v (s_x + o_i)))),  o_j = (j - T/2) / U:
+//   the inverse transform evaluated on T x T points around the coarse peak, as two small DFT-as-GEMM contractions
+// The FRC forward with an epilogue that keeps only Rn, and the first forward use of the half-spectrum inverse, which so far existed
+// as backward passes: with a half plane Z = A - iB (the convention of Re, J above) of a real image,
+//   [T1 | T2] = [C_H A + S_H B | C_H B - S_H A]  on the operand m_v/(HW) Z;   X = [T1 | T2] [C_W[:, :Wh]^T ; S_W[:, :Wh]^T]
+// hspec_inv_col_kernel is that column pass.  Its table is either the H-point DFT table or a per-sample T x H table of the upsampled
+// DFT, so the refinement's first contraction is the same kernel; its operand is summed over the channels while it is staged (the
+// surface and `up` are sums over c of a linear map), or multiplied by the ramp of the Fourier shift
+//   fourier_shift(x, d) = Re ifft2(fft2(x) exp(-2 pi i (f_u d_y + f_v d_x))),  f of numpy.fft.fftfreq (Nyquist at -1/2):
+// the real part turns the Nyquist row and column (even sides) into cos(pi d_y), cos(pi d_x) and the bin that is Nyquist on both axes
+// into cos(pi (d_y + d_x)): the effective ramp is Hermitian, and separable everywhere but in that one bin.
+// No atomics; every sum in a fixed order; nothing here waits for the host: the peak stays on the device between the launches.
+struct PcorrWs {
+    float* pq;          // [2 (a,b)][N*C][H][2Wh]: [P | Q]; then [N][H][2Wh]: [T1 | T2] of the inverse
+    float* rn;          // [N*C][2][H][Wh]: Rn as (Re, -Im)
+    float* surf;        // [N][H][W] when the caller does not ask for the surface
+    float* ey;          // [N][H][2T]: cos | sin of 2 pi f_u (s_y + o_j)
+    float* ex;          // [N][2][Wh][T]: cos, sin of 2 pi f_v (s_x + o_i)
+    float* up;          // [N][T][2Wh]: [T1 | T2] of the refinement
+    int* coarse;        // [N][2]: the coarse peak (s_y, s_x), signed
+    long total;
+};
+
+static int pcorr_points(int U) { return (3 * U + 1) / 2; }              // T = ceil(1.5 U)
+
+static PcorrWs pcorr_ws(float* ws, long N, long C, long H, long W, long Wh, long U) {
+    PcorrWs p;
+    const long T = U > 1 ? pcorr_points((int)U) : 0;
+    long off = 0;
+    p.pq = ws + off;
+    off += 2 * N * C * H * 2 * Wh;
+    p.rn = ws + off;
+    off += N * C * 2 * H * Wh;
+    p.surf = ws + off;
+    off += N * H * W;
+    p.ey = ws + off;
+    off += N * H * 2 * T;
+    p.ex = ws + off;
+    off += N * 2 * Wh * T;
+    p.up = ws + off;
+    off += N * T * 2 * Wh;
+    p.coarse = (int*)(ws + off);
+    off += 2 * N;
+    p.total = off;
+    return p;
+}
+
+struct FshiftWs {
+    float* pq;          // [N*C][H][2Wh]: [P | Q] in the forward passes, [T1 | T2] in the inverse ones
+    float* planes;      // [N*C][2][H][Wh]: Re, -Im
+    float* pw;          // [N*C][H][Wh]: the power plane sprof_col_fwd_kernel also writes (not read)
+    long total;
+};
+
+static FshiftWs fshift_ws(float* ws, long imgs, long H, long Wh) {
+    FshiftWs p;
+    long off = 0;
+    p.pq = ws + off;
+    off += imgs * H * 2 * Wh;
+    p.planes = ws + off;
+    off += imgs * 2 * H * Wh;
+    p.pw = ws + off;
+    off += imgs * H * Wh;
+    p.total = off;
+    return p;
+}
+
+// every product of the two spectra in one place: G conj(F) for F = rx - i jx, G = ry - i jy, as (Re, -Im).  Exchanging the images
+// leaves re and negates im exactly (the caller compiles this without contraction)
+__device__ __forceinline__ void pcorr_cross(float rx, float jx, float ry, float jy, float& re, float& im) {
+#pragma clang fp contract(off)
+    re = rx * ry + jx * jy;
+    im = jy * rx - ry * jx;
+}
+
+// column pass of frc_col_fwd_kernel; the epilogue forms Rn from the four accumulators and writes that half plane only
+__global__ __launch_bounds__(256) void pcorr_col_fwd_kernel(const float* __restrict__ pq, const float* __restrict__ tabH,
+                                                            const short* __restrict__ binmap, float* __restrict__ rn, int H, int W, int Wh,
+                                                            long imgs, float eps, int k_max, int normalize) {
+#pragma clang fp contract(off)
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[4][PH_KC * PH_T];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long img = blockIdx.z;
+    const int u0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const float* pqx = pq + img * H * 2 * Wh;
+    const float* pqy = pq + (imgs + img) * H * 2 * Wh;
+    f32x16 rx, jx, ry, jy;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rx[r] = jx[r] = ry[r] = jy[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables(Cs, Ss, tabH, H, k0, u0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int k = k0 + (e >> 6), v = v0 + (e & 63);
+            const bool ok = k < H && v < Wh;
+            const long o = (long)k * 2 * Wh + v;
+            Bs[0][e] = ok ? pqx[o] : 0.f;
+            Bs[1][e] = ok ? pqx[o + Wh] : 0.f;
+            Bs[2][e] = ok ? pqy[o] : 0.f;
+            Bs[3][e] = ok ? pqy[o + Wh] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float px = Bs[0][bo], qx = Bs[1][bo];
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, px, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(as, px, jx, 0, 0, 0);
+            rx = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qx, rx, 0, 0, 0);
+            jx = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qx, jx, 0, 0, 0);
+            const float py = Bs[2][bo], qy = Bs[3][bo];
+            ry = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, py, ry, 0, 0, 0);
+            jy = __builtin_amdgcn_mfma_f32_32x32x2f32(as, py, jy, 0, 0, 0);
+            ry = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, qy, ry, 0, 0, 0);
+            jy = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, qy, jy, 0, 0, 0);
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < Wh) {
+        const long hwh = (long)H * Wh;
+        const float hw = (float)(H * W);
+        float* out = rn + img * 2 * hwh;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int u = u0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (u < H) {
+                const long o = (long)u * Wh + v;
+                float re, im;
+                pcorr_cross(rx[rr], jx[rr], ry[rr], jy[rr], re, im);
+                re = re / hw;
+                im = im / hw;
+                if (normalize) {
+                    const float d = sqrtf(re * re + im * im + eps);
+                    re = re / d;
+                    im = im / d;
+                }
+                if (binmap[o] > k_max) re = im = 0.f;
+                out[o] = re;
+                out[hwh + o] = im;
+            }
+        }
+    }
+}
+
+// stage one 16 x 64 chunk of a table pair stored k-major: C[k][r] at tab[k * ld + r], S[k][r] at tab[k * ld + half + r], k < K, r < R
+__device__ __forceinline__ void stage_tables_ld(float* Cs, float* Ss, const float* __restrict__ tab, int K, int R, int ld, int half, int k0,
+                                                int r0, int tid) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int e = tid + 256 * i;
+        const int k = k0 + (e >> 6), r = r0 + (e & 63);
+        const bool ok = k < K && r < R;
+        Cs[e] = ok ? tab[(long)k * ld + r] : 0.f;
+        Ss[e] = ok ? tab[(long)k * ld + half + r] : 0.f;
+    }
+}
+
+// (cos, sin) of 2 pi (k / n) d for the signed index k of a ramp; the phase is reduced in double before sincospi.  The Nyquist index
+// of an even side gives (cos(pi d), 0): the real part of the shifted image (see above; the caller treats the doubly-Nyquist bin)
+__device__ __forceinline__ void shift_ramp(int idx, int n, float d, float& c, float& s) {
+    const int k = centred(idx, n);
+    double t = (double)k * (double)d / (double)n;
+    t -= rint(t);
+    double sd, cd;
+    sincospi(2.0 * t, &sd, &cd);
+    c = (float)cd;
+    s = (2 * idx == n) ? 0.f : (float)sd;
+}
+
+// the half-spectrum inverse column pass: T[out][r][0..2Wh) = [T1 | T2], T1 = sum_u C[u][r] A' + S[u][r] B', T2 = sum_u C[u][r] B' - S[u][r] A',
+// r < R, for the table pair `tab` (+ n * tab_stride: per sample, or 0), k-major with row length ld = 2R.  The operand (A', B') is formed
+// from planes[img][2][H][Wh] while it is staged: csum: the sum over the C channels of sample n = out (in index order), else the plane
+// out with n = out / C;  then, with `shift`, times the ramp of fourier_shift for d = sign * shift[n];  then times m_v * scale.
+// scale is 1 / (HW) for the Fourier shift.  Phase correlation passes 1 and divides once behind the last sum: where Rn is 1 in every
+// bin (an image against itself) the operands are then small integers, every sum is exact and the peak is exactly 1
+__global__ __launch_bounds__(256) void hspec_inv_col_kernel(const float* __restrict__ planes, const float* __restrict__ tab, long tab_stride,
+                                                            int R, int ld, const float* __restrict__ shift, float sign, float scale,
+                                                            float* __restrict__ T, int H, int W, int Wh, int C, int csum) {
+#pragma clang fp contract(off)
+    __shared__ float Cs[PH_KC * PH_T], Ss[PH_KC * PH_T], Bs[2][PH_KC * PH_T];
+    __shared__ float gyc[1024], gys[1024];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long out = blockIdx.z;
+    const long n = csum ? out : out / C;
+    const int r0 = blockIdx.y * PH_T, v0 = blockIdx.x * PH_T;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
+    const long hwh = (long)H * Wh;
+    const float* pl = planes + (csum ? out * C : out) * 2 * hwh;
+    const int cn = csum ? C : 1;
+    const float* tb = tab + n * tab_stride;
+    const int sv = v0 + (tid & 63);
+    const float wv = sprof_mv(sv, W, Wh) * scale;
+    float gxc = 1.f, gxs = 0.f, gnn = 1.f;
+    if (shift) {
+        const float dy = sign * shift[2 * n], dx = sign * shift[2 * n + 1];
+        if (sv < Wh) shift_ramp(sv, W, dx, gxc, gxs);
+        if (2 * sv == W) {                                      // the bin that is Nyquist on both axes: cos(pi (d_y + d_x))
+            double t = 0.5 * ((double)dy + (double)dx);
+            t -= rint(t);
+            gnn = (float)cospi(2.0 * t);
+        }
+        for (int u = tid; u < H; u += 256) shift_ramp(u, H, dy, gyc[u], gys[u]);
+    }
+    f32x16 t1, t2;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t1[r] = t2[r] = 0.f;
+    for (int k0 = 0; k0 < H; k0 += PH_KC) {
+        __syncthreads();
+        stage_tables_ld(Cs, Ss, tb, H, R, ld, R, k0, r0, tid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int e = tid + 256 * i;
+            const int u = k0 + (e >> 6);
+            float a = 0.f, b = 0.f;
+            if (u < H && sv < Wh) {
+                const long o = (long)u * Wh + sv;
+                for (int c = 0; c < cn; ++c) {
+                    a += pl[c * 2 * hwh + o];
+                    b += pl[c * 2 * hwh + hwh + o];
+                }
+                if (shift) {
+                    // g = exp(-i (psi_y + psi_x)) = gr + i gi;  (A - iB) g = (A gr + B gi) - i (B gr - A gi)
+                    const float cy = gyc[u], sy = gys[u];
+                    const bool nn = 2 * u == H && 2 * sv == W;
+                    const float gr = nn ? gnn : cy * gxc - sy * gxs, gi = nn ? 0.f : -(sy * gxc + cy * gxs);
+                    const float a2 = a * gr + b * gi, b2 = b * gr - a * gi;
+                    a = a2;
+                    b = b2;
+                }
+                a = a * wv;
+                b = b * wv;
+            }
+            Bs[0][e] = a;
+            Bs[1][e] = b;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk0 = 0; kk0 < PH_KC; kk0 += 2) {
+            const int ao = (kk0 + lh) * PH_T + wm * 32 + l31, bo = (kk0 + lh) * PH_T + wn * 32 + l31;
+            const float ac = Cs[ao], as = Ss[ao], nas = -as;
+            const float a = Bs[0][bo], b = Bs[1][bo];
+            t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, a, t1, 0, 0, 0);
+            t2 = __builtin_amdgcn_mfma_f32_32x32x2f32(ac, b, t2, 0, 0, 0);
+            t1 = __builtin_amdgcn_mfma_f32_32x32x2f32(as, b, t1, 0, 0, 0);
+            t2 = __builtin_amdgcn_mfma_f32_32x32x2f32(nas, a, t2, 0, 0, 0);
+        }
+    }
+    const int v = v0 + wn * 32 + l31;
+    if (v < Wh) {
+        float* To = T + out * R * 2 * Wh;
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+            const int r = r0 + wm * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * lh;
+            if (r < R) {
+                const long o = (long)r * 2 * Wh + v;
+                To[o] = t1[rr];
+                To[o + Wh] = t2[rr];
+            }
+        }
+    }
+}
+
+// the better of two (value, index) candidates: the larger value, the lower index on a tie.  A NaN never enters (the caller's
+// comparison is false for it), so none is ever held
+__device__ __forceinline__ bool peak_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+// the block's best candidate by a tree in LDS; valid in thread 0
+__device__ __forceinline__ void peak_tree_256(double& v, int& i, double* rv, int* ri) {
+    const int tid = threadIdx.x;
+    rv[tid] = v;
+    ri[tid] = i;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o && peak_better(rv[tid + o], ri[tid + o], rv[tid], ri[tid])) {
+            rv[tid] = rv[tid + o];
+            ri[tid] = ri[tid + o];
+        }
+        __syncthreads();
+    }
+    v = rv[0];
+    i = ri[0];
+}
+
+// one block per sample: the first maximum of the surface in row-major order among the positions with |d_y| <= my, |d_x| <= mx
+// (positions > H/2, > W/2 wrap negative).  The surface comes unscaled (HW times its value).  Writes the signed peak, and shift / peak (the value over C) as they stand without a refinement.
+// A plane without a comparable value (all NaN) yields position 0
+__global__ __launch_bounds__(256) void pcorr_peak_kernel(const float* __restrict__ surf, int* __restrict__ coarse, float* __restrict__ shift,
+                                                         float* __restrict__ peak, int H, int W, int C, int my, int mx) {
+    __shared__ double rv[256];
+    __shared__ int ri[256];
+    const int tid = threadIdx.x, total = H * W;
+    const float* s = surf + (long)blockIdx.x * total;
+    double best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int e = tid; e < total; e += 256) {
+        const int y = e / W, x = e % W;
+        const int dy = y > H / 2 ? y - H : y, dx = x > W / 2 ? x - W : x;
+        if (dy < -my || dy > my || dx < -mx || dx > mx) continue;
+        const double v = (double)s[e];
+        if (peak_better(v, e, best, idx)) {
+            best = v;
+            idx = e;
+        }
+    }
+    peak_tree_256(best, idx, rv, ri);
+    if (tid == 0) {
+        if (idx < 0 || idx >= total) idx = 0;
+        const int y = idx / W, x = idx % W;
+        const int dy = y > H / 2 ? y - H : y, dx = x > W / 2 ? x - W : x;
+        coarse[2 * blockIdx.x] = dy;
+        coarse[2 * blockIdx.x + 1] = dx;
+        shift[2 * blockIdx.x] = (float)dy;
+        shift[2 * blockIdx.x + 1] = (float)dx;
+        peak[blockIdx.x] = (float)((double)s[idx] / ((double)H * (double)W * (double)C));
+    }
+}
+
+// the per-sample tables of the upsampled DFT around the coarse peak, built on the device from it:
+//   ey[n][u][j | T + j] = cos | sin of 2 pi u_c (s_y U + j - T/2) / (U H),   ex[n][0 | 1][v][i] likewise for the columns v < Wh.
+// The numerator is reduced mod U H (mod U W) in integers before sincospi
+__global__ __launch_bounds__(256) void pcorr_twiddle_kernel(const int* __restrict__ coarse, float* __restrict__ ey, float* __restrict__ ex, int H,
+                                                            int W, int Wh, int U, int T) {
+    const int n = blockIdx.y;
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    const long ny = (long)H * T, nx = (long)Wh * T;
+    if (e >= ny + nx) return;
+    const bool isy = e < ny;
+    const long e2 = isy ? e : e - ny;
+    const int f = (int)(e2 / T), j = (int)(e2 % T);
+    const int side = isy ? H : W;
+    const long den = (long)U * side;
+    long num = ((long)centred(f, side) * ((long)coarse[2 * n + (isy ? 0 : 1)] * U + j - T / 2)) % den;
+    if (num < 0) num += den;
+    double sd, cd;
+    sincospi(2.0 * (double)num / (double)den, &sd, &cd);
+    if (isy) {
+        float* o = ey + ((long)n * H + f) * 2 * T;
+        o[j] = (float)cd;
+        o[T + j] = (float)sd;
+    } else {
+        float* o = ex + (long)n * 2 * nx;
+        o[(long)f * T + j] = (float)cd;
+        o[nx + (long)f * T + j] = (float)sd;
+    }
+}
+
+// the surface as the caller sees it: the unscaled sum over HW
+__global__ __launch_bounds__(256) void pcorr_scale_kernel(float* __restrict__ surf, long n, float hw) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) surf[i] = surf[i] / hw;
+}
+
+// one block per sample: up[j][i] = sum_{v<Wh} T1[j][v] cos_x[v][i] + T2[j][v] sin_x[v][i] in double and index order, its first maximum
+// in row-major order, and from it shift = (s + (j* - T/2) / U) and peak = up[j*][i*] / (HW C) (the operand came unscaled)
+__global__ __launch_bounds__(256) void pcorr_refine_kernel(const float* __restrict__ up, const float* __restrict__ ex, const int* __restrict__ coarse,
+                                                           float* __restrict__ shift, float* __restrict__ peak, int Wh, double hwc, int U, int T) {
+#pragma clang fp contract(off)
+    __shared__ double rv[256];
+    __shared__ int ri[256];
+    const int tid = threadIdx.x, n = blockIdx.x;
+    const float* t = up + (long)n * T * 2 * Wh;
+    const float* cx = ex + (long)n * 2 * Wh * T;
+    const float* sx = cx + (long)Wh * T;
+    double best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int e = tid; e < T * T; e += 256) {
+        const int j = e / T, i = e % T;
+        const float* t1 = t + (long)j * 2 * Wh;
+        double acc = 0.0;
+        for (int v = 0; v < Wh; ++v) acc += (double)t1[v] * (double)cx[(long)v * T + i] + (double)t1[Wh + v] * (double)sx[(long)v * T + i];
+        if (peak_better(acc, e, best, idx)) {
+            best = acc;
+            idx = e;
+        }
+    }
+    peak_tree_256(best, idx, rv, ri);
+    if (tid == 0) {
+        if (idx < 0 || idx >= T * T) {                         // no comparable value: the coarse peak stands, the value says why
+            idx = (T / 2) * T + T / 2;
+            best = NAN;
+        }
+        const int j = idx / T, i = idx % T;
+        shift[2 * n] = (float)((double)(coarse[2 * n] * U + j - T / 2) / (double)U);
+        shift[2 * n + 1] = (float)((double)(coarse[2 * n + 1] * U + i - T / 2) / (double)U);
+        peak[n] = (float)(best / hwc);
+    }
+}
+
 }  // namespace faoctasr
 
 using namespace faoctasr;
@@ -1439,4 +1835,112 @@ extern "C" int faoctasr_frc_bwd(const float* g, int g_per_image, const float* sa
                                       stream);
     }
     return faoctasr_sgemm_batched(dx ? p.pq : p.pq + sT, stacked, dx ? dx : dy, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, 0, 0, 0, 1, stream);
+}
+
+static int pcorr_check(const char* what, int N, int C, int H, int W, int Wh, int K, int U) {
+    int rc = sprof_check(what, 2, N, C, H, W, Wh, K);
+    if (rc) return rc;
+    if (Wh != W / 2 + 1) return fail(FAOCTASR_EINVAL, "%s: Wh %d is not W/2 + 1 = %d", what, Wh, W / 2 + 1);
+    if (U < 1 || U > 100) return fail(FAOCTASR_EINVAL, "%s: upsample %d outside 1..100", what, U);
+    return FAOCTASR_OK;
+}
+
+// launches 5 to 8 of phase correlation: the coarse peak of the (unscaled) surface, the twiddles, the two contractions
+static int pcorr_peak(const PcorrWs& p, const float* surf, float* shift, float* peak, int N, int C, int H, int W, int Wh, int upsample,
+                      int max_shift_y, int max_shift_x, const float* tabH, hipStream_t st) {
+    int rc;
+    hipLaunchKernelGGL(pcorr_peak_kernel, dim3((unsigned)N), dim3(256), 0, st, (const float*)surf, p.coarse, shift, peak, H, W, C, max_shift_y,
+                       max_shift_x);
+    rc = check_launch("pcorr_fwd (peak)");
+    if (rc || upsample == 1) return rc;
+    const int T = pcorr_points(upsample);
+    const long tw = (long)(H + Wh) * T;
+    hipLaunchKernelGGL(pcorr_twiddle_kernel, dim3((unsigned)((tw + 255) / 256), (unsigned)N), dim3(256), 0, st, (const int*)p.coarse, p.ey, p.ex, H,
+                       W, Wh, upsample, T);
+    rc = check_launch("pcorr_fwd (twiddles)");
+    if (rc) return rc;
+    dim3 gridT((Wh + PH_T - 1) / PH_T, (T + PH_T - 1) / PH_T, (unsigned)N);
+    hipLaunchKernelGGL(hspec_inv_col_kernel, gridT, dim3(256), 0, st, (const float*)p.rn, (const float*)p.ey, (long)H * 2 * T, T, 2 * T,
+                       (const float*)nullptr, 0.f, 1.f, p.up, H, W, Wh, C, 1);
+    rc = check_launch("pcorr_fwd (T x H x Wh contraction)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(pcorr_refine_kernel, dim3((unsigned)N), dim3(256), 0, st, (const float*)p.up, (const float*)p.ex, (const int*)p.coarse,
+                       shift, peak, Wh, (double)H * (double)W * (double)C, upsample, T);
+    return check_launch("pcorr_fwd (T x Wh x T contraction)");
+}
+
+extern "C" long faoctasr_pcorr_workspace_floats(int N, int C, int H, int W, int Wh, int K, int upsample) {
+    if (pcorr_check("pcorr_workspace_floats", N, C, H, W, Wh, K, upsample)) return -1;
+    return pcorr_ws(nullptr, N, C, H, W, Wh, upsample).total;
+}
+
+extern "C" int faoctasr_pcorr_fwd(const float* a, const float* b, const float* tabH, const float* halfW, const short* binmap, double eps,
+                                  int k_max, int normalize, int upsample, int max_shift_y, int max_shift_x, float* shift, float* peak,
+                                  float* surface, float* workspace, int N, int C, int H, int W, int Wh, int K, faoctasr_stream_t stream) {
+    if (!a || !b || !tabH || !halfW || !binmap || !workspace) return fail(FAOCTASR_EINVAL, "pcorr_fwd: null pointer");
+    if (!shift != !peak || (!shift && !surface)) return fail(FAOCTASR_EINVAL, "pcorr_fwd: shift and peak go together, and without them the surface is the output");
+    int rc = pcorr_check("pcorr_fwd", N, C, H, W, Wh, K, upsample);
+    if (rc) return rc;
+    if (!(eps >= 0.0) || eps > 1.0e30) return fail(FAOCTASR_EINVAL, "pcorr_fwd: eps %g must be finite and >= 0", eps);
+    if (k_max < 0 || k_max > K - 1) return fail(FAOCTASR_EINVAL, "pcorr_fwd: k_max %d outside 0..%d", k_max, K - 1);
+    if (max_shift_y < 0 || max_shift_y > H / 2 || max_shift_x < 0 || max_shift_x > W / 2)
+        return fail(FAOCTASR_EINVAL, "pcorr_fwd: max_shift (%d, %d) outside 0..%d, 0..%d", max_shift_y, max_shift_x, H / 2, W / 2);
+    const long imgs = (long)N * C;
+    const hipStream_t st = (hipStream_t)stream;
+    const PcorrWs p = pcorr_ws(workspace, N, C, H, W, Wh, upsample);
+    const intptr_t d = (intptr_t)b - (intptr_t)a;
+    if (d % (intptr_t)sizeof(float)) return fail(FAOCTASR_EINVAL, "pcorr_fwd: a and b are not 4-byte aligned to each other");
+    rc = faoctasr_sgemm_batched(a, halfW, p.pq, (int)(imgs * H), 2 * Wh, W, W, 2 * Wh, 2 * Wh, (long)(d / (intptr_t)sizeof(float)), 0,
+                                imgs * H * 2 * Wh, 2, stream);
+    if (rc) return rc;
+    dim3 grid((Wh + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(pcorr_col_fwd_kernel, grid, dim3(256), 0, st, (const float*)p.pq, tabH, binmap, p.rn, H, W, Wh, imgs, (float)eps, k_max,
+                       normalize ? 1 : 0);
+    rc = check_launch("pcorr_fwd (column pass)");
+    if (rc) return rc;
+    // the inverse on the channel sum: [T1 | T2] over [P | Q], then X = [T1 | T2] [C_W[:, :Wh]^T ; S_W[:, :Wh]^T]
+    grid.z = (unsigned)N;
+    hipLaunchKernelGGL(hspec_inv_col_kernel, grid, dim3(256), 0, st, (const float*)p.rn, tabH, 0L, H, 2 * H, (const float*)nullptr, 0.f, 1.f, p.pq, H,
+                       W, Wh, C, 1);
+    rc = check_launch("pcorr_fwd (inverse column pass)");
+    if (rc) return rc;
+    float* surf = surface ? surface : p.surf;
+    rc = faoctasr_sgemm_batched(p.pq, halfW + 2L * W * Wh, surf, N * H, W, 2 * Wh, 2 * Wh, W, W, 0, 0, 0, 1, stream);
+    if (rc) return rc;
+    if (shift) rc = pcorr_peak(p, surf, shift, peak, N, C, H, W, Wh, upsample, max_shift_y, max_shift_x, tabH, st);
+    if (rc || !surface) return rc;
+    const long ns = (long)N * H * W;
+    hipLaunchKernelGGL(pcorr_scale_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, surface, ns, (float)(H * W));
+    return check_launch("pcorr_fwd (surface scale)");
+}
+
+// the Fourier shift has no rings, but shares sprof_check: the ring count of a legal shape, 0 (refused on the shape) otherwise
+static int fshift_bins(int H, int W) { return (H >= 2 && W >= 2 && H <= 1024 && W <= 1024) ? sprof_bins(H, W) : 0; }
+
+extern "C" long faoctasr_fourier_shift_workspace_floats(int N, int C, int H, int W) {
+    if (sprof_check("fourier_shift_workspace_floats", 1, N, C, H, W, W / 2 + 1, fshift_bins(H, W))) return -1;
+    return fshift_ws(nullptr, (long)N * C, H, W / 2 + 1).total;
+}
+
+extern "C" int faoctasr_fourier_shift(const float* x, const float* shift, float sign, const float* tabH, const float* halfW, float* out,
+                                      float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream) {
+    if (!x || !shift || !tabH || !halfW || !out || !workspace) return fail(FAOCTASR_EINVAL, "fourier_shift: null pointer");
+    const int Wh = W / 2 + 1;
+    int rc = sprof_check("fourier_shift", 1, N, C, H, W, Wh, fshift_bins(H, W));
+    if (rc) return rc;
+    if (sign != 1.f && sign != -1.f) return fail(FAOCTASR_EINVAL, "fourier_shift: sign %g is neither 1 nor -1", (double)sign);
+    const long imgs = (long)N * C;
+    const hipStream_t st = (hipStream_t)stream;
+    const FshiftWs p = fshift_ws(workspace, imgs, H, Wh);
+    rc = faoctasr_sgemm_batched(x, halfW, p.pq, (int)(imgs * H), 2 * Wh, W, W, 2 * Wh, 2 * Wh, 0, 0, 0, 1, stream);
+    if (rc) return rc;
+    dim3 grid((Wh + PH_T - 1) / PH_T, (H + PH_T - 1) / PH_T, (unsigned)imgs);
+    hipLaunchKernelGGL(sprof_col_fwd_kernel<1>, grid, dim3(256), 0, st, (const float*)p.pq, tabH, p.pw, p.planes, (float*)nullptr, H, W, Wh, imgs);
+    rc = check_launch("fourier_shift (column pass)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(hspec_inv_col_kernel, grid, dim3(256), 0, st, (const float*)p.planes, tabH, 0L, H, 2 * H, shift, sign,
+                       (float)(1.0 / ((double)H * (double)W)), p.pq, H, W, Wh, C, 0);
+    rc = check_launch("fourier_shift (inverse column pass)");
+    if (rc) return rc;
+    return faoctasr_sgemm_batched(p.pq, halfW + 2L * W * Wh, out, (int)(imgs * H), W, 2 * Wh, 2 * Wh, W, W, 0, 0, 0, 1, stream);
 }

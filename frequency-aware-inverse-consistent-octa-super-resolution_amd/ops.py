@@ -2783,6 +2783,157 @@ def frc_cutoff(curve, H, W, threshold=1 / 7, smooth=1, k_min=1, k_max=None):
 
 
 # ----------------------------------------------------------------------------------------
+# phase-correlation registration and the Fourier shift (csrc/spectral.hip, fifth section)
+# ----------------------------------------------------------------------------------------
+PCORR_MAX_UPSAMPLE = 100
+
+
+def check_pcorr_params(H, W, upsample=10, max_shift=None, k_max=None, eps=1e-16, normalization="phase"):
+    """``(upsample, (max_y, max_x), k_max, eps, normalize)`` of ``phase_correlation`` for H x W images, or ValueError: ``upsample`` an
+    int in 1..100; ``max_shift`` None (half the side), an int or a pair of ints, each in ``0..side // 2``; ``k_max`` None (every ring)
+    or an int in ``0..K - 1`` of ``radial_bins(H, W)``; ``eps`` finite and >= 0; ``normalization`` ``"phase"`` or None."""
+    if isinstance(upsample, bool) or not isinstance(upsample, int) or not 1 <= upsample <= PCORR_MAX_UPSAMPLE:
+        raise ValueError("phase_correlation: upsample must be an int in 1..%d, got %r" % (PCORR_MAX_UPSAMPLE, upsample))
+    if max_shift is None:
+        max_shift = (H // 2, W // 2)
+    elif isinstance(max_shift, int) and not isinstance(max_shift, bool):
+        max_shift = (max_shift, max_shift)
+    try:
+        my, mx = max_shift
+    except (TypeError, ValueError):
+        raise ValueError("phase_correlation: max_shift must be None, an int or a pair of ints, got %r" % (max_shift,))
+    for m, side in ((my, H), (mx, W)):
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= side // 2:
+            raise ValueError("phase_correlation: max_shift must lie in 0..side // 2 = (%d, %d), got %r" % (H // 2, W // 2, max_shift))
+    K = int(radial_bins(H, W)[1].numel())
+    if k_max is None:
+        k_max = K - 1
+    elif isinstance(k_max, bool) or not isinstance(k_max, int) or not 0 <= k_max <= K - 1:
+        raise ValueError("phase_correlation: k_max must be None or an int in 0..%d (a %d x %d spectrum has %d rings), got %r"
+                         % (K - 1, H, W, K, k_max))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not (math.isfinite(eps) and eps >= 0):
+        raise ValueError("phase_correlation: eps must be a finite number >= 0, got %r" % (eps,))
+    if normalization not in ("phase", None):
+        raise ValueError("phase_correlation: normalization must be \"phase\" or None, got %r" % (normalization,))
+    return upsample, (my, mx), k_max, float(eps), normalization == "phase"
+
+
+def _check_pcorr_shapes(what, a, b):
+    """What the parameter checks need of the operands, before them: two (N,C,H,W) fp32 tensors of one shape with legal sides."""
+    for x in (a, b):
+        if not torch.is_tensor(x) or x.dim() != 4:
+            raise _lib.KernelError("%s operands must be (N,C,H,W) tensors, got %s" % (what, tuple(getattr(x, "shape", ()))))
+        if x.dtype != torch.float32:
+            raise _lib.KernelError("%s operands must be fp32, got %s" % (what, x.dtype))
+        if not (2 <= x.shape[2] <= SPROF_MAX_SIDE and 2 <= x.shape[3] <= SPROF_MAX_SIDE):
+            raise _lib.KernelError("%s needs 2 <= H, W <= %d, got %s" % (what, SPROF_MAX_SIDE, tuple(x.shape)))
+    if a.shape != b.shape:
+        raise _lib.KernelError("%s operands must have one shape: %s vs %s" % (what, tuple(a.shape), tuple(b.shape)))
+
+
+def _pcorr_launch(a, b, upsample, max_shift, k_max, eps, normalize, want_shift, want_surface):
+    a, b = _c(a.detach()), _c(b.detach())
+    N, C, H, W = a.shape
+    tab_h, half_w, K, Wh, _, _, _, binmap = sprof_tables(H, W, a.device)
+    dev = a.device
+    n = _lib.load().faoctasr_pcorr_workspace_floats(N, C, H, W, Wh, K, upsample)
+    if n < 0:
+        raise _lib.KernelError("faoctasr_pcorr_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=dev)               # scratch of this call: free again behind it on the stream
+    shift = torch.empty((N, 2), dtype=torch.float32, device=dev) if want_shift else None
+    peak = torch.empty(N, dtype=torch.float32, device=dev) if want_shift else None
+    surface = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_surface else None
+    call("pcorr_fwd", ptr(a), ptr(b), ptr(tab_h), ptr(half_w), binmap.data_ptr(), eps, k_max, int(normalize), upsample, max_shift[0],
+         max_shift[1], ptr(shift), ptr(peak), ptr(surface), ptr(ws), N, C, H, W, Wh, K, stream_ptr())
+    return shift, peak, surface
+
+
+def phase_correlation_surface(a, b, k_max=None, eps=1e-16, normalization="phase"):
+    """The phase-correlation surface of a, b (N,C,H,W) fp32 on one GPU, (N, H, W): ``sum_c Re ifft2(Rn)`` of ``phase_correlation``.  Its
+    maximum lies at ``d`` when ``b(p) = a(p - d)``.  No gradient."""
+    _check_pcorr_shapes("phase_correlation_surface", a, b)
+    _, _, k_max, eps, normalize = check_pcorr_params(a.shape[2], a.shape[3], 1, None, k_max, eps, normalization)
+    _check_frc_operands("phase_correlation_surface", a, b)
+    with torch.no_grad():
+        return _pcorr_launch(a, b, 1, (0, 0), k_max, eps, normalize, False, True)[2]
+
+
+def phase_correlation(a, b, upsample=10, max_shift=None, k_max=None, eps=1e-16, normalization="phase"):
+    """The translation between a and b (N,C,H,W) fp32 on one GPU, 2 <= H, W <= 1024, by phase correlation (Kuglin & Hines 1975) with
+    the upsampled-DFT refinement of Guizar-Sicairos, Thurman & Fienup (2008): ``(shift (N, 2) fp32, peak (N,) fp32)``, one shift
+    ``(d_y, d_x)`` per sample for all its channels.  With ``F = fft2(a)``, ``G = fft2(b)``: ``R = G conj(F) / (HW)``,
+    ``Rn = R / sqrt(|R|^2 + eps)`` (``normalization="phase"``) or ``R`` (None), zero in every ring of ``radial_bins(H, W)`` above
+    ``k_max``; the surface is ``sum_c Re ifft2(Rn)``.  Its first maximum in row-major order with ``|d_y| <= max_shift[0]``,
+    ``|d_x| <= max_shift[1]`` is the coarse peak (positions > H//2, > W//2 wrap negative).  ``upsample = U > 1`` evaluates the inverse
+    transform at ``T = ceil(1.5 U)`` offsets ``(j - T//2) / U`` per axis around it and takes the first maximum there; the shift is a
+    multiple of ``1 / U``.  ``peak`` is the winning value, in (0, 1] under phase normalisation: a confidence.
+    SIGN: the shift is ``d`` when ``b(p) = a(p - d)``: ``b = torch.roll(a, (3, -2), (-2, -1))`` gives ``(3, -2)``, and
+    ``fourier_shift(b, -shift)`` lies on ``a``.  ``skimage.registration.phase_cross_correlation(a, b)`` returns ``-d``.
+    No gradient.  No host synchronisation: capturable, bit-reproducible, always exact fp32 (csrc/spectral.hip)."""
+    _check_pcorr_shapes("phase_correlation", a, b)
+    upsample, max_shift, k_max, eps, normalize = check_pcorr_params(a.shape[2], a.shape[3], upsample, max_shift, k_max, eps, normalization)
+    _check_frc_operands("phase_correlation", a, b)
+    with torch.no_grad():
+        shift, peak, _ = _pcorr_launch(a, b, upsample, max_shift, k_max, eps, normalize, True, False)
+    return shift, peak
+
+
+def _fourier_shift_launch(x, shift, sign):
+    x = _c(x)
+    N, C, H, W = x.shape
+    tab_h, half_w = dft_tables(H, x.device), sprof_half_tables(W, x.device)
+    n = _lib.load().faoctasr_fourier_shift_workspace_floats(N, C, H, W)
+    if n < 0:
+        raise _lib.KernelError("faoctasr_fourier_shift_workspace_floats failed: %s" % _lib.load().faoctasr_last_error().decode())
+    ws = torch.empty(max(n, 1), dtype=torch.float32, device=x.device)          # scratch of this call: free again behind it on the stream
+    out = torch.empty_like(x)
+    call("fourier_shift", ptr(x), ptr(shift), sign, ptr(tab_h), ptr(half_w), ptr(out), ptr(ws), N, C, H, W, stream_ptr())
+    return out
+
+
+class _FourierShift(Function):
+    @staticmethod
+    def forward(ctx, x, shift):
+        ctx.save_for_backward(shift)
+        return _fourier_shift_launch(x, shift, 1.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        shift, = ctx.saved_tensors
+        return _fourier_shift_launch(g, shift, -1.0), None             # the transpose of the shift by d is the shift by -d
+
+
+def fourier_shift(x, shift):
+    """``Re ifft2(fft2(x) exp(-2 pi i (f_u d_y + f_v d_x)))`` of x (N,C,H,W) fp32 on one GPU, 2 <= H, W <= 1024, ``f`` of
+    ``numpy.fft.fftfreq``: the content moves by ``+d`` (periodically), to a fraction of a pixel; an integer ``d`` is
+    ``torch.roll(x, d, (-2, -1))`` up to rounding.  ``shift``: an (N, 2) fp32 tensor on x's device, one ``(d_y, d_x)`` per sample as
+    ``phase_correlation`` returns it, or a pair of floats for the whole batch.  Differentiable in x (the backward is the shift by
+    ``-d``; only ``shift`` is kept); there is no gradient to ``shift``: asking for one raises (the open follow-up).  Always exact fp32
+    (csrc/spectral.hip)."""
+    if not torch.is_tensor(x) or x.dim() != 4 or x.dtype != torch.float32:
+        raise _lib.KernelError("fourier_shift: x must be an (N,C,H,W) fp32 tensor, got %s %s" % (tuple(getattr(x, "shape", ())), getattr(x, "dtype", None)))
+    N = x.shape[0]
+    if not torch.is_tensor(shift):
+        try:
+            dy, dx = (float(v) for v in shift)
+        except (TypeError, ValueError):
+            raise ValueError("fourier_shift: shift must be an (N, 2) tensor or a pair of floats, got %r" % (shift,))
+        if not (math.isfinite(dy) and math.isfinite(dx)):
+            raise ValueError("fourier_shift: shift must be finite, got %r" % (shift,))
+    _check_sprof_operands("fourier_shift", x)
+    if torch.is_tensor(shift):
+        if shift.requires_grad and torch.is_grad_enabled():
+            raise _lib.KernelError("fourier_shift has no gradient with respect to the shift (an open follow-up); detach it")
+        if shift.shape != (N, 2) or shift.dtype != torch.float32 or shift.device != x.device:
+            raise _lib.KernelError("fourier_shift: shift must be an (N, 2) = (%d, 2) fp32 tensor on %s, got %s %s on %s"
+                                   % (N, x.device, tuple(shift.shape), shift.dtype, shift.device))
+        shift = _c(shift.detach())
+    else:
+        shift = torch.tensor([[dy, dx]], dtype=torch.float32).expand(N, 2).contiguous().to(x.device)
+    return _FourierShift.apply(x, shift)
+
+
+# ----------------------------------------------------------------------------------------
 # differentiable mutual information (Gaussian Parzen windows, soft joint histogram; csrc/mi.hip)
 # ----------------------------------------------------------------------------------------
 MI_MAX_BINS = 64

@@ -43,6 +43,10 @@ class SSIM(torch.nn.Module):
         self.window_size, self.size_average, self.channel = window_size, size_average, 1
         self.window = create_window(window_size, self.channel)
 
+    def index(self, img1, img2, per_image):
+        """The index with ``per_image`` as given instead of ``not size_average`` (what ``Registered`` and ``evaluate_pairs_with`` call)."""
+        return ops.ssim(img1, img2, not per_image)
+
     def forward(self, img1, img2):
         return ops.ssim(img1, img2, self.size_average)
 
@@ -409,3 +413,68 @@ class FRCResolution(torch.nn.Module):
 
     def extra_repr(self):
         return "threshold={}, smooth={}, k_min={}, k_max={}, eps={}".format(self.threshold, self.smooth, self.k_min, self.k_max, self.eps)
+
+
+class Registered(torch.nn.Module):
+    """An index behind a sub-pixel registration: ``d = ops.phase_correlation(img1, img2, upsample, max_shift, k_max)`` (a constant:
+    taken without gradient), ``img2' = ops.fourier_shift(img2, -d)``, both cropped by the static margin ``max_shift + 1`` on all four
+    sides (the wrapped-around border never reaches the index, and no shape depends on data: capturable), then ``index.forward`` /
+    ``index.index`` on the crops.  Every full-reference index here assumes registered pairs; this is the wrapper for pairs that are
+    off by a pixel or so.  Gradients flow to ``img1`` and, through the shift's adjoint, to ``img2``.  ``index``: any module with
+    ``forward(a, b)`` and ``index(a, b, per_image)``.  Sides must exceed ``2 (max_shift + 1)``."""
+
+    def __init__(self, index, max_shift=8, upsample=10, k_max=None):
+        super().__init__()
+        if isinstance(max_shift, bool) or not isinstance(max_shift, int) or max_shift < 0:
+            raise ValueError("Registered: max_shift must be an int >= 0, got %r" % (max_shift,))
+        if isinstance(upsample, bool) or not isinstance(upsample, int) or not 1 <= upsample <= ops.PCORR_MAX_UPSAMPLE:
+            raise ValueError("Registered: upsample must be an int in 1..%d, got %r" % (ops.PCORR_MAX_UPSAMPLE, upsample))
+        if k_max is not None and (isinstance(k_max, bool) or not isinstance(k_max, int) or k_max < 0):
+            raise ValueError("Registered: k_max must be None or an int >= 0, got %r" % (k_max,))
+        self.wrapped = index
+        self.max_shift, self.upsample, self.k_max = max_shift, upsample, k_max
+
+    def shift(self, img1, img2):
+        """``(shift (N, 2), peak (N,))`` of ``ops.phase_correlation`` with this module's settings."""
+        m = self.max_shift + 1
+        if img1.dim() != 4 or min(img1.shape[-2:]) <= 2 * m:
+            raise ValueError("Registered: sides must exceed 2 (max_shift + 1) = %d, got %s" % (2 * m, tuple(img1.shape)))
+        return ops.phase_correlation(img1, img2, self.upsample, self.max_shift, self.k_max)
+
+    def register(self, img1, img2):
+        """The registered, cropped pair the wrapped index sees."""
+        d, _ = self.shift(img1, img2)
+        m = self.max_shift + 1
+        moved = ops.fourier_shift(img2, -d)
+        return img1[..., m:-m, m:-m].contiguous(), moved[..., m:-m, m:-m].contiguous()
+
+    def index(self, img1, img2, per_image=False):
+        return self.wrapped.index(*self.register(img1, img2), per_image)
+
+    def forward(self, img1, img2):
+        return self.wrapped(*self.register(img1, img2))
+
+    def extra_repr(self):
+        return "max_shift={}, upsample={}, k_max={}".format(self.max_shift, self.upsample, self.k_max)
+
+
+class RegistrationShift(torch.nn.Module):
+    """The length in pixels of the translation between two images (``ops.phase_correlation``), with an index's interface so that an
+    evaluation can report how far apart its pairs were: ``index(img1, img2, per_image)`` is ``|d|``, ``(N,)`` or the batch mean;
+    ``forward`` the batch mean.  No gradient."""
+
+    def __init__(self, max_shift=8, upsample=10, k_max=None):
+        super().__init__()
+        checked = Registered(None, max_shift, upsample, k_max)
+        self.max_shift, self.upsample, self.k_max = checked.max_shift, checked.upsample, checked.k_max
+
+    def index(self, img1, img2, per_image=False):
+        d, _ = ops.phase_correlation(img1, img2, self.upsample, min(self.max_shift, min(img1.shape[-2:]) // 2), self.k_max)
+        n = d.square().sum(1).sqrt()
+        return n if per_image else n.mean()
+
+    def forward(self, img1, img2):
+        return self.index(img1, img2, False)
+
+    def extra_repr(self):
+        return "max_shift={}, upsample={}, k_max={}".format(self.max_shift, self.upsample, self.k_max)

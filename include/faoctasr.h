@@ -340,6 +340,27 @@ int faoctasr_frc_fwd(const float* x, const float* y, const float* tabH, const fl
 int faoctasr_frc_bwd(const float* g, int g_per_image, const float* save, const float* tabH, const float* halfW, const short* binmap,
                      float* dx, float* dy, float* workspace, int N, int C, int H, int W, int Wh, int K, faoctasr_stream_t stream);
 
+/* ---- phase-correlation registration and the Fourier shift (Kuglin & Hines 1975; Guizar-Sicairos et al. 2008; not in the reference) ----
+ * a, b[N,C,H,W] fp32, the tables and limits of the spectral-profile loss (Wh = W/2 + 1; binmap: the int16 ring of every half-plane
+ * position).  F = fft2(a), G = fft2(b), R = G conj(F) / (HW), Rn = R / sqrt(|R|^2 + eps) (normalize) or R, zero in every ring above
+ * k_max; surface[N,H,W] = sum_c Re ifft2(Rn), whose peak lies at d when b(p) = a(p - d).  The coarse peak is the first maximum in
+ * row-major order among |d_y| <= max_shift_y, |d_x| <= max_shift_x (positions > H/2, > W/2 wrap negative); with upsample U > 1 the
+ * inverse transform is evaluated on T x T points, T = ceil(1.5 U), at the offsets (j - T/2) / U around it, and the first maximum
+ * there wins.  shift[N][2] = (d_y, d_x), peak[N] = the winning value over C.  Nothing waits for the host, nothing is allocated, every sum
+ * has a fixed order: capturable and bit-reproducible.
+ * workspace of one call; -1 on a bad shape or upsample outside 1..100 */
+long faoctasr_pcorr_workspace_floats(int N, int C, int H, int W, int Wh, int K, int upsample);
+/* shift and peak NULL: only the surface is computed (surface must be given); surface NULL: it stays in the workspace.
+ * eps finite and >= 0, 0 <= k_max <= K - 1, upsample 1..100, 0 <= max_shift_y <= H/2, 0 <= max_shift_x <= W/2. */
+int faoctasr_pcorr_fwd(const float* a, const float* b, const float* tabH, const float* halfW, const short* binmap, double eps, int k_max,
+                       int normalize, int upsample, int max_shift_y, int max_shift_x, float* shift, float* peak, float* surface,
+                       float* workspace, int N, int C, int H, int W, int Wh, int K, faoctasr_stream_t stream);
+/* out[N,C,H,W] = Re ifft2(fft2(x) exp(-2 pi i (f_u d_y + f_v d_x))), (d_y, d_x) = sign * shift[n], shift[N][2] on the device, f of
+ * numpy.fft.fftfreq: the content moves by +d.  sign is 1 or -1; the transpose of the operator is the call with the other sign. */
+long faoctasr_fourier_shift_workspace_floats(int N, int C, int H, int W);
+int faoctasr_fourier_shift(const float* x, const float* shift, float sign, const float* tabH, const float* halfW, float* out,
+                           float* workspace, int N, int C, int H, int W, faoctasr_stream_t stream);
+
 /* ---- differentiable mutual information (Gaussian Parzen windows; not part of the reference) ----
  * Per (n, c) plane of n_pix = H*W pixels, with K = bins, d = (hi - lo) / K, centres c_k = lo + (k + 1/2) d, sigma = sigma_ratio d:
  * Wa[p,k] = softmax_k(-(x_p - c_k)^2 / (2 sigma^2)) (evaluated stably: any finite x, in the range or not), Wb likewise from y,
