@@ -64,7 +64,10 @@ __global__ __launch_bounds__(256) void circulant_lowpass_kernel(float* __restric
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long)n * n) return;
     const int a = (int)(e / n), b = (int)(e % n);
-    const int j = ((a - b) % n + n) % n;
+    // c[j] == c[n - j]: both are evaluated at the smaller of the two, so that the matrix is symmetric to the bit (its transpose is
+    // used as its adjoint).  Summed at j and at n - j the phases differ, and where the taps cancel to ~1e-17 so did the two sums.
+    const int jj = ((a - b) % n + n) % n;
+    const int j = min(jj, n - jj);
     const int c0 = n / 2;
     double s = 0.0;
     for (int k = 0; k < n; ++k) {
@@ -87,6 +90,7 @@ extern "C" int faoctasr_sgemm_batched(const float* A, const float* B, float* C, 
     if (M < 0 || N < 0 || K < 0 || batch < 0 || lda < K || ldb < N || ldc < N) return fail(FAOCTASR_EINVAL, "sgemm_batched: bad shape");
     if (M == 0 || N == 0 || batch == 0) return FAOCTASR_OK;
     if (batch > 65535) return fail(FAOCTASR_EUNSUPPORTED, "sgemm_batched: batch %d > 65535", batch);
+    if (M > 65535 * 64) return fail(FAOCTASR_EUNSUPPORTED, "sgemm_batched: M %d > 65535 row tiles of 64", M);
     dim3 grid((N + 63) / 64, (M + 63) / 64, batch);
     hipLaunchKernelGGL(sgemm_batched_kernel, grid, dim3(256), 0, (hipStream_t)stream, A, B, C, M, N, K, lda, ldb, ldc, strideA, strideB,
                        strideC);

@@ -2246,7 +2246,7 @@ class _FreqSplit(Function):
         s_hp, s_lp, dx = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         call("freq_mix_bwd", ptr(x), ptr(low_hp), ptr(low_lp), ptr(_c(g_hf)) if g_hf is not None else None,
              ptr(_c(g_lf)) if g_lf is not None else None, ptr(s_hp), ptr(s_lp), ptr(dx), x.numel(), st)
-        # the circulants are symmetric, so the adjoint of x -> Ch x Cw is the same map
+        # the circulants are symmetric (to the bit: circulant_lowpass_kernel), so the adjoint of x -> Ch x Cw is the same map
         a = _lowpass2d(s_hp.view(B * C, H, W), mats[0], mats[1], st)
         b = _lowpass2d(s_lp.view(B * C, H, W), mats[2], mats[3], st)
         n = x.numel()

@@ -219,7 +219,8 @@ int faoctasr_haar_dfront_bwd(const float* dy, float* dx, int N, int H, int W, in
  * utils.high_pass / utils.low_pass (utils.py:71-117) as called at train.py:173-175,189-191,
  * 197-199,211-213.  The shifted Gaussian mask is separable, so ifft2(mask*fft2(x)) = Ch x Cw^T
  * with real symmetric circulant matrices built once per (n, radius) (faoctasr_circulant_lowpass).
- * Batched row-major SGEMM on f32 MFMA: for b in [0,batch): C_b = A_b(MxK) * B_b(KxN).         */
+ * Batched row-major SGEMM on f32 MFMA: for b in [0,batch): C_b = A_b(MxK) * B_b(KxN).
+ * batch <= 65535 and M <= 65535 * 64 (the grid's z and y extents); beyond either: FAOCTASR_EUNSUPPORTED, nothing launched. */
 int faoctasr_sgemm_batched(const float* A, const float* B, float* C, int M, int N, int K,
                            int lda, int ldb, int ldc, long strideA, long strideB, long strideC, int batch,
                            faoctasr_stream_t stream);
